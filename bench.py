@@ -19,13 +19,17 @@ checks   : the epoch loss of every timed step must be finite, and after the time
            step is validated (rows sum to 1, view 0 != view 1) and a checksum of it is printed ("validation").
 N > 1    : one process per GPU (torch.distributed, backend nccl == RCCL); no collective inside an epoch.
 
-At N = 1 the line also carries "fixed_job_8_voters": BASELINE.md section 3's FIXED cfg3 job (8 voters, predict + the [8, N] all-gather
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs DIR is given (dump_outputs) and prints the line.  Everything else it measures runs with --full only:
+
+At N = 1 a --full line also carries "fixed_job_8_voters": BASELINE.md section 3's FIXED cfg3 job (8 voters, predict + the [8, N] all-gather
 through the RCCL group of one) run on the one GPU after the headline region -- the like-for-like N = 1 anchor of the 1/2/4/8
 curve: the N >= 2 lines ("job": "cfg3 ...") compare with IT, not with the one-voter headline ("job": "cfg2 ...").
 
 Prints ONE JSON line (rank 0).  Extra objects: "roofline" (the hand-written vectoriser kernel, HBM bound), "roofline_epoch"
-(the encoder epoch, MFMA fp32 bound), "cpu_baseline" (oracle port on the host cores, bounded sample, rank 0 at N=1 only),
-"t_e2e" (FASTA text in the page cache -> last optimizer.step, N=1 only; never `value`).
+(the encoder epoch, MFMA fp32 bound); with --full also "cpu_baseline" (oracle port on the host cores, bounded sample, rank 0 at N=1 only),
+"t_e2e" (FASTA text in the page cache -> last optimizer.step, N=1 only; never `value`), "exchange_ms", the plane
+kernels alone, "k_sweep", "fp32_step_form", "predicted_fixed_job" and "cfg5_one_gpu".
 """
 import argparse
 import json
@@ -256,6 +260,44 @@ class HotPath:
         assert all(abs(c - n) < 1e-3 * n for c in chk), chk
         return {"epoch_loss_last_step": [float(x) for x in losses[-len(self.my_voters):]], "epoch_loss_first_timed": float(losses[0]),
                 "feats_checksum": chk, "rows_checked": int(rows.numel())}
+
+
+DUMP_BUDGET = 64 << 20          # --dump-outputs: bytes in all
+DUMP_SEED = 2024                # fixed sample of the outputs that exceed their share of it
+
+
+def _sample_axis(t, axis, max_bytes, seed):
+    """t itself when it fits in max_bytes, else a fixed, seeded sample of its entries along `axis` (sorted indices)."""
+    if t.numel() * t.element_size() <= max_bytes:
+        return t
+    per = t.numel() // t.shape[axis] * t.element_size()
+    keep = max(1, min(t.shape[axis], max_bytes // per))
+    idx = np.sort(np.random.default_rng(seed).choice(t.shape[axis], keep, replace=False))
+    return t.index_select(axis, torch.from_numpy(idx).to(t.device))
+
+
+def dump_outputs(hp, out_dir):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as <out_dir>/<name>.npy (float32 / float64): the
+    epoch loss of each of this rank's voters, the scaler (mean, scale), the feature store [views, N, 4^k] (a fixed sample of rows
+    when it is larger than 24 MB), the parameters of the last trained network and, when the exchange step is timed, the gathered
+    assignments [V, N] (as float32) or the cfg5 latent [N, 64] (both sampled along N past 16 MB).  64 MB at most in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"epoch_loss": torch.stack([l.reshape(()) for l in hp.losses[-len(hp.my_voters):]]).double(),
+           "scaler_mean": hp.mean, "scaler_scale": hp.scale,
+           "features": _sample_axis(hp.feats, 1, 24 << 20, DUMP_SEED)}
+    for name, p in hp.last_model.net.named_parameters():
+        out["net_" + name.replace(".", "_")] = _sample_axis(p.detach(), 0, 8 << 20, DUMP_SEED)
+    if hp.gathered is not None:
+        out["assignments"] = _sample_axis(hp.gathered.float(), 1, 16 << 20, DUMP_SEED)
+    if hp.latent is not None:
+        out["latent"] = _sample_axis(hp.latent, 0, 16 << 20, DUMP_SEED)
+    arrays = {k: v.cpu().numpy() for k, v in out.items()}
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET, f"--dump-outputs: {total} bytes over the {DUMP_BUDGET}-byte budget"
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def check_votes(gathered, voters, n, n_clusters):
@@ -791,16 +833,24 @@ def main():
                     help="optimizer steps timed (after one untimed step) with the reference's cpu_count()-2 torch threads, scaled to the epoch")
     ap.add_argument("--no-k-sweep", dest="k_sweep", action="store_false", help="skip the k = 4 / k = 5 vectorise-stage rooflines (cfg4)")
     ap.add_argument("--no-split16", "--no-fp32-form", dest="split16", action="store_false", help="skip the leg with the step's fp32 form (IDELUCS_PLANES=0)")
-    ap.add_argument("--no-cfg5", dest="cfg5_leg", action="store_false", help="skip the cfg5 job (10^6 x 5 kbp, 65.5 GB store) the default N = 1 run adds")
+    ap.add_argument("--no-cfg5", dest="cfg5_leg", action="store_false", help="skip the cfg5 job (10^6 x 5 kbp, 65.5 GB store) a --full N = 1 run adds")
     ap.add_argument("--no-prediction", dest="prediction", action="store_false", help="skip the 2- and 4-lane passes behind predicted_fixed_job")
     ap.add_argument("--no-cpu-baseline", dest="cpu_base", action="store_false")
     ap.add_argument("--no-e2e", dest="e2e", action="store_false")
     ap.add_argument("--no-fixed-job", dest="fixed_job", action="store_false",
-                    help="skip the fixed 8-voter job (cfg3) that the default N = 1 run adds after the headline region")
+                    help="skip the fixed 8-voter job (cfg3) that a --full N = 1 run adds after the headline region")
     ap.add_argument("--n-rate", dest="n_rate", type=float, default=0.0,
                     help="SURVEY 8(d) variant N: every synthetic base is an N with this probability (e.g. 1e-3); default 0 = BASELINE's input")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: the untimed exchange, the plane kernels alone, T_e2e, the fixed 8-voter job "
+                         "and its prediction, the k sweep, the fp32 step form, the cfg5 job and the CPU baseline (each still subject to its --no-* "
+                         "option); a plain run times the headline region only")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, 64 MB at most)")
     forwarded = os.environ.pop("IDELUCS_BENCH_ARGV", None)      # set by spawn_ranks for its ranks
     args = ap.parse_args(json.loads(forwarded) if forwarded is not None and "WORLD_SIZE" in os.environ else None)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     cfg5 = args.workload == "cfg5"
     args.n = args.n or (1_000_000 if cfg5 else 100_000)
@@ -880,6 +930,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     assert not bool(hp.edit_overflow.item()), "mimic edit buffer bound exceeded: the run is invalid"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(hp, args.dump_outputs)
     validation = hp.validate()
     exchange_ms = None
     if args.exchange:
@@ -889,7 +941,7 @@ def main():
                               latent_row_norm_max=float(hp.latent.norm(dim=1).max().item()))
         else:
             validation.update(check_votes(hp.gathered, args.voters, args.n, args.n_clusters))
-    else:
+    elif args.full:
         # the exchange step of the path, untimed at N = 1 with one voter: this rank's voter predicts, assignments are all-gathered
         from idelucs_amd.dist import all_gather_assignments
         all_gather_assignments(hp.predict(hp.model, hp._predict_inputs()))            # first call: library initialisation for the inference GEMM shapes (0.5 s)
@@ -918,7 +970,7 @@ def main():
         nce = args.n_mimics * 3 * (2 * B) * H2 * 2 * 2
         f_exec = args.n_mimics * 2 * (2 * 2 * F * H1 + 3 * 2 * (H1 * H2 + H2 * C)) + nce
         ach_exec = args.n * f_exec / (t_ep * 1e-3) / 1e12
-        plane_kernels = plane_kernel_leg(dev, 2 * B, H1, F) if world == 1 else None
+        plane_kernels = plane_kernel_leg(dev, 2 * B, H1, F) if world == 1 and args.full else None
         cfg_name = "configs[4] (cfg5)" if cfg5 else ("configs[1] (cfg2)" if V == 1 else "configs[2] (cfg3)")
         region = "device mimic sites + vectorise + scaler fit + 1 epoch per voter"
         if args.exchange:
@@ -941,7 +993,7 @@ def main():
                            "-- within 7e-7 of the product's largest entry on standardised operands, closer than the fp32 arithmetic on the step's long dense sums (2.4e-7 "
                            "against 2.6e-6; dW1 4.5e-7 against 1.5e-6), up to twice as far on sums carried by a few terms (tests/test_gpu_planes.py, "
                            "profiles/r06_planes_adversarial.txt); an operand beyond the planes' range is flagged and the voter retrained on the fp32 tiles; the plain "
-                           "fp32 form of the same step is timed in fp32_step_form"),
+                           "fp32 form of the same step is timed in fp32_step_form (--full)"),
             "config": {"workload": f"BASELINE {cfg_name}{' (variant N: every base an N w.p. %g)' % args.n_rate if args.n_rate > 0 else ''}: "
                                    f"synthetic {args.n} x {args.len} bp, k={args.k}, n_clusters={args.n_clusters}, "
                                    f"n_mimics={args.n_mimics} ({P} views), batch_sz={args.batch_sz}, NetLinear fp32, RMSprop; "
@@ -972,7 +1024,7 @@ def main():
                                        "dense FP32 matrix peak -- the arithmetic the results are equivalent to (tests/test_gpu_planes.py: fp32-grade "
                                        "against float64); frac_algorithmic = SURVEY 8(d)'s own count (3 x forward for every layer) over the same peak, kept for "
                                        "comparison with earlier rounds.  Neither is a fraction of the pipe the two big products run on: each is three fp16 "
-                                       "products (3 x 4.29 GFLOP a step) on the fp16 matrix cores -- plane_kernels has each kernel's time alone and its "
+                                       "products (3 x 4.29 GFLOP a step) on the fp16 matrix cores -- plane_kernels (--full) has each kernel's time alone and its "
                                        "fraction of the 2.5 PFLOP/s fp16 peak; profiles/r06_step_kernels.txt their times inside the step"},
             "roofline_dominant": "roofline_epoch" if t_ep * len(hp.my_voters) > 0.5 * ms_step else "roofline",
             "roofline_dominant_note": ("`roofline` is the north_star's named kernel (the hand-written HBM-bound vectoriser); the epoch is "
@@ -983,12 +1035,12 @@ def main():
         }
         if exchange_ms is not None:
             out["exchange_ms"] = exchange_ms
-        if world == 1 and args.e2e and not cfg5 and V == 1:
+        if world == 1 and args.full and args.e2e and not cfg5 and V == 1:
             del hp.feats, hp.store.feats
             hp.model.store = None
             torch.cuda.empty_cache()
             out["t_e2e"] = t_e2e(args, dev)
-        if world == 1 and args.fixed_job and not cfg5 and V == 1 and not args.exchange:
+        if world == 1 and args.full and args.fixed_job and not cfg5 and V == 1 and not args.exchange:
             # (after t_e2e dropped the headline's feature store: the fixed job allocates its own)
             if "t_e2e" not in out:
                 del hp.feats, hp.store.feats
@@ -997,15 +1049,15 @@ def main():
             out["fixed_job_8_voters"] = fixed_job_8_voters(din, args, dev, rank, world)
             if args.prediction:
                 out["predicted_fixed_job"] = predicted_fixed_job(din, args, dev, rank, world, out["fixed_job_8_voters"]["stage_ms"], t_ep, lane_model=hp.model)
-        if world == 1 and args.k_sweep and not cfg5 and V == 1:
+        if world == 1 and args.full and args.k_sweep and not cfg5 and V == 1:
             out["k_sweep"] = k_sweep(din, args, dev)
-        if world == 1 and args.split16 and not cfg5 and V == 1 and args.k == 6:
+        if world == 1 and args.full and args.split16 and not cfg5 and V == 1 and args.k == 6:
             out["fp32_step_form"] = fp32_form_leg(din, args, dev, rank, world)
-        if world == 1 and args.cfg5_leg and not cfg5 and V == 1 and not args.exchange and args.fixed_job:
+        if world == 1 and args.full and args.cfg5_leg and not cfg5 and V == 1 and not args.exchange and args.fixed_job:
             del din, hp
             torch.cuda.empty_cache()
             out["cfg5_one_gpu"] = cfg5_one_gpu(args, dev, rank, world)
-        if world == 1 and args.cpu_base:
+        if world == 1 and args.full and args.cpu_base:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out))
     if dist.is_initialized():

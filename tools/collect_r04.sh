@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/r04_f}
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_default.json 2> $out/bench_default.err
 echo "bench rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-fixed-job > $out/trace_bench.json 2> $out/trace.err
 cp $out/trace/*/*kernel_stats.csv $out/bench_kernel_stats.csv

@@ -8,7 +8,7 @@ timeout -k 10 300 python tools/mfma_clock.py > $O/mfma_clock.txt 2> $O/mfma_cloc
 cat $O/mfma_clock.txt
 timeout -k 10 400 python tools/sweep_ingest_threads.py > $O/ingest_threads.txt 2> $O/ingest_threads.err || { tail -20 $O/ingest_threads.err; exit 1; }
 cat $O/ingest_threads.txt
-timeout -k 10 500 python bench.py --steps 10 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err || { tail -30 $O/bench_default.err; exit 1; }
+timeout -k 10 500 python bench.py --steps 10 --warmup 3 --full > $O/bench_default.json 2> $O/bench_default.err || { tail -30 $O/bench_default.err; exit 1; }
 python - <<'PY'
 import json
 j = json.load(open("gpurun_out/r04_a/bench_default.json"))

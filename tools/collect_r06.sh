@@ -5,7 +5,7 @@ out=${1:-gpurun_out/r06_f}
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 if [ -z "$SKIP_BENCH" ]; then
-( time python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/bench_default.time
+( time python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/bench_default.time
 echo "bench rc=$? $(grep real $out/bench_default.time)"
 fi
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-fixed-job --no-k-sweep --no-fp32-form --no-cfg5 > $out/trace_bench.json 2> $out/trace.err
