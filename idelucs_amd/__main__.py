@@ -234,11 +234,15 @@ def build_parser():
     p.add_argument("--rng", action="store", type=str, default=None, choices=[None, "philox", "compat"],
                    help="mimic RNG: device Philox (default) or the reference's host numpy/random streams")
     p.add_argument("--seed", action="store", type=int, default=0)
+    p.add_argument("--small_step", action="store", type=str, default=None, choices=["autograd", "native"],
+                   help="model_size='small': train on torch autograd (the default) or on the native HIP step (RMSprop only)")
     return p
 
 
 def main(argv=None):
     args = vars(build_parser().parse_args(argv))
+    if args["small_step"] is None:          # (absent: the printed parameters and the results table stay as they were)
+        del args["small_step"]
     if int(os.environ.get("RANK", "0")) == 0:
         print("\nTraining Parameters:")
         for key in args:

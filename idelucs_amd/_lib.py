@@ -146,6 +146,13 @@ SIGNATURES = {
     "idl_plan_end": (_int, []),
     "idl_plan_launch": (_int, [_vp, _vp, _int, _vp]),
     "idl_rmsprop_step": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _int, _c.c_float, _c.c_float, _vp, _vp]),
+    "idl_small_l1_fwd": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
+    "idl_small_mid_fwd": (_int, [_vp] * 8 + [_int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "idl_small_mid_bwd": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_float, _c.c_uint64,
+                                 _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "idl_small_wgrad_rms": (_int, [_vp] * 5 + [_vp] * 8 + [_int, _int, _int, _vp, _c.c_float, _c.c_float, _vp,
+                                   _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "idl_small_dropout_masks": (_int, [_c.c_uint64, _i64, _int, _vp, _vp, _vp]),
 }
 
 if not os.path.exists(LIB_PATH):

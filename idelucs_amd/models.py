@@ -106,6 +106,21 @@ class IID_model():
         self._fused = None
         self._use_fused = (args['model_size'] == 'linear' and args['optimizer'] == 'RMSprop'
                            and args['n_clusters'] <= 256 and _fused_on())
+        # model_size='small': autograd (the default) or, opt-in, the explicit step of fused_small.FusedSmallTrainer
+        self._small = None
+        self._use_small = args['model_size'] == 'small' and self._small_step(args) == 'native'
+
+    @staticmethod
+    def _small_step(args):
+        """args['small_step'] of a model_size='small' model: 'autograd' (absent or None) or 'native' (RMSprop, n_clusters <= 256,
+        batch_sz <= 1024); anything else raises ValueError."""
+        mode = args.get('small_step') or 'autograd'
+        if mode not in ('autograd', 'native'):
+            raise ValueError(f"small_step must be 'autograd' or 'native', not {mode!r}")
+        if mode == 'native' and (args['optimizer'] != 'RMSprop' or not 1 <= args['n_clusters'] <= 256 or not 1 <= args['batch_sz'] <= 1024):
+            raise ValueError("small_step='native' supports optimizer='RMSprop', n_clusters in 1..256 and batch_sz in 1..1024 "
+                             f"(got optimizer={args['optimizer']!r}, n_clusters={args['n_clusters']}, batch_sz={args['batch_sz']})")
+        return mode
 
     def _make_scheduler(self):
         if self.schedule == 'Plateau':                          # models.py:96-99
@@ -169,6 +184,8 @@ class IID_model():
             self._make_scheduler()
         if self._fused is not None:
             self._fused.begin_voter(self._voter, keep_state=carry)
+        if self._small is not None:
+            self._small.begin_voter(self._voter, keep_state=carry)
 
     def _step(self, x):
         """One optimizer step on a [2b, F] batch (rows [0,b) "true", [b,2b) "modified")."""
@@ -200,6 +217,14 @@ class IID_model():
                 self._fused.begin_voter(self._voter)
             self._fused.set_lr(self.optimizer.param_groups[0]['lr'])       # schedulers act on the torch optimizer
             total, n_batches = self._fused.run_epoch(st, self.batch_sz, generator=self._gen)
+            return total / (n_batches - 1)                                  # models.py:135 quirk (divide by last index)
+        if self._use_small:
+            if self._small is None:
+                from .fused_small import FusedSmallTrainer
+                self._small = FusedSmallTrainer(self.net, self.lr, self.weight, self.l, seed=self.seed)
+                self._small.begin_voter(self._voter)
+            self._small.set_lr(self.optimizer.param_groups[0]['lr'])       # schedulers act on the torch optimizer
+            total, n_batches = self._small.run_epoch(st, self.batch_sz, generator=self._gen)
             return total / (n_batches - 1)                                  # models.py:135 quirk (divide by last index)
         running_loss = torch.zeros((), device=self.device)
         perm = torch.randperm(st.n_pairs, device=self.device, generator=self._gen)
