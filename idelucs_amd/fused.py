@@ -1,24 +1,26 @@
 """idelucs_amd.fused -- the explicit, fused optimizer step for the default configuration
 (NetLinear encoder + RMSprop), replayed as a HIP graph.
 
-One step of reference idelucs/models.py:117-133 is 6 launches by default: the layer-1 product on hipBLASLt (torch.mm with
-out=, no allocation) and five fused HIP kernels from csrc/train_step.hip + nce_fused.hip + wgrad_device.h --
-    W1 x^T  ->  idl_mid_fwd_gather  ->  idl_nce_fused_iic_z (two launches)  ->  idl_mid_bwd_gather
-            ->  idl_wgrad_rmsprop_step (dW1 = dr1^T x as MFMA tiles with RMSprop in their epilogue + the rest of the optimizer)
-(DESIGN.md 4.4 has the table of what each launch carries).  The unfused building blocks idl_relu_dropout_fwd, idl_head_fwd,
-idl_nce_rows, idl_iic_core, idl_head_bwd, idl_bias_grads, idl_rmsprop_step remain for the shapes the fused kernels do not take
-(n_clusters > 48, partial batches) and as their test references.  Batches are assembled from the HBM feature store at a
-device-resident offset that the optimizer kernel advances, the next batch while the current step is between its two big GEMMs
-(two x buffers), so an epoch is n_batches / 2 replays of one captured two-step graph with no host work between.
+One step of reference idelucs/models.py:117-133 takes one of five launch sequences (FusedLinearTrainer._form picks it once per step):
+    planes       (default, n_clusters <= 48) the two big products on the fp16 matrix cores from two-plane operands:
+                 idl_l1_planes -> idl_reduce_parts_rms -> idl_mid_fwd_gather_planes -> idl_nce_fused_iic_z -> idl_mid_bwd_gather_planes
+                 -> idl_wgrad_xplanes_rms (dW1 with RMSprop in the tiles' epilogue, the optimizer's tail on their loader waves)
+    planes_rows  the same for n_clusters > 48 (the fine-grained mode's 200 output units: joint + IIC core with z dP0, dW3 on idl_at_b)
+    tiles        IDELUCS_PLANES=0 (or shapes the planes do not take): own fp32 tiles, idl_l1_fwd -> idl_mid_fwd_gather -> InfoNCE + IIC ->
+                 idl_mid_bwd_gather -> idl_wgrad_rmsprop; the optimizer's tail rides in the NEXT step's layer-1 launch (idl_l1_fwd_rms)
+    record_planes the planes sequence recorded for BatchedLinearTrainer
+    general      everything else on library GEMMs + the unfused kernels: a lockstep step on batched fp32 GEMMs, n_clusters > 48 in fp32,
+                 partial batches and the shapes the own tiles do not take
+(DESIGN.md 4.4 has the table of what each launch carries).  Batches are assembled from the HBM feature store at a device-resident
+offset that the step advances, the next batch by spare workgroups of the middle launches into the other of two x buffers, so an
+epoch is replays of one captured single-stream graph of several steps with no host work between.
 
 The parameters remain the nn.Parameters of model.net (state_dict / predict / weights_init unchanged).
 RMSprop state lives here; begin_voter() clears it (every voter is an independent run, models.IID_model.begin_voter).
 
 BatchedLinearTrainer steps several voters of one ensemble in lockstep: the layer-1 product becomes a batched GEMM and each of
-the five kernels ONE launch with the voter index in its grid (recorded launches, idl_plan_*; the dW1 tiles ride at the head of
-every voter's share of the optimizer launch as they do for a single voter: 5 voters 94.9 -> 91.7 ms an epoch of 50 000 sequences), so the latency-bound
-launches -- 51 of the 116 us of a step, mostly launch boundaries and dependent-load chains on a quarter of the CUs -- are paid
-once per step of the whole batch of voters instead of once per voter.
+the other kernels ONE launch with the voter index in its grid (recorded launches, idl_plan_*; in the two-plane form all six
+launches), so the latency-bound launches are paid once per step of the whole batch of voters instead of once per voter.
 """
 import ctypes
 import os
@@ -46,24 +48,19 @@ def planes_default():
     return os.environ.get("IDELUCS_PLANES", "1") != "0" and not _PLANES_DISABLED
 
 
-# Launch-sequence variants kept because tests compare them with the default form (each was measured and not adopted: DESIGN, History).  They are
-# NOT environment switches (round 6: 27 of them used to be): a test sets an entry with monkeypatch.setitem(fused.VARIANTS, ...) before it builds a trainer.
+# Launch-sequence variants kept because tests or the training policy compare them with the default form (each was measured and not adopted:
+# DESIGN, History).  They are NOT environment switches: a test sets an entry with monkeypatch.setitem(fused.VARIANTS, ...) before it builds a trainer.
 VARIANTS = {
-    "nce_fused": "1",        # 0: S = f f^T as a GEMM + row kernels instead of the fused InfoNCE passes
-    "dw3_partial": "1",      # 0: dW3 as a GEMM instead of stacked partials from the middle-backward launch (n_clusters <= 48)
     "test_cold": "0",        # 1: a 512 MB fill in front of the hand-scheduled launches (tests/test_gpu_planes.py::test_cold_caches_*)
     "lockstep_planes": "1",  # 0: a rank's voters in lockstep on batched fp32 library GEMMs
     "planes_wgrad": "1",     # 0: dW1 on the fp32 tiles (writing W1's planes) beside the two-plane layer 1
     "planes_tail": "wgrad",  # reduce: the optimizer tail beside the next step's partial sums instead of on the dW1 tiles' loader waves
-    "mid_fused": "1", "pipeline": "1", "dw2_inlaunch": "1", "overlap": "0", "early_gather": "1", "gather_split": "4", "transposed_l1": "1",
-    "l1_fused": "0",         # bare: the fp32 form's own layer-1 tiles as a plain product without the riding tail (the comparison of test_tail_riding_*)
-    "joint_inlaunch": "1", "wgrad_fused": "1", "keep_w1_grad": "0", "steps_per_graph": "16",
-    "tail_l1": "1",          # 0 (fp32 form): the optimizer tail behind the dW1 tiles instead of riding in the next step's layer-1 launch
+    "fused": "1",            # 0: models.IID_model trains NetLinear + RMSprop through torch autograd instead of the fused explicit step
 }
-
-
-VARIANTS["fused"] = "1"      # 0: models.IID_model trains NetLinear + RMSprop through torch autograd instead of the fused explicit step
 VARIANTS.update({k: v for k, v in _lib.DEV.items() if k in VARIANTS})
+STEPS_PER_GRAPH = 16         # steps a replayed graph carries (between two replays the GPU idles ~9 us)
+GATHER_SPLIT = 4             # eighths of the next batch's tiles the mid-forward launch assembles (the rest: mid-backward) at n_clusters <= 48
+PLANES_MAX_ROWS = 60_000_000  # feature-store rows the two-plane form's batch assembly takes
 
 
 def _v(name):
@@ -80,6 +77,39 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _launch(fn, *args):
+    """One kernel launch, performed now (the launcher of launch_losses outside a recording)."""
+    _lib.check(fn(*args))
+
+
+def launch_losses(k, bf, lamb, weight, out, dz=False):
+    """InfoNCE on bf.f and IIC on bf.z of one step (FusedLinearTrainer and fused_small.FusedSmallTrainer), each kernel through the
+    launcher k(fn, *args).  dz: the IIC core writes z dP0 to bf.dzs (idl_iic_core_dz) instead of dP0 to bf.P0, for a middle backward
+    that takes it per row."""
+    m, C = bf.m, bf.P0.shape[0]
+    if bf.nce_fused and C <= 48:
+        # the IIC workgroup of InfoNCE pass 1 forms the joint z1^T z2 itself (MFMA tiles) before the core
+        k(_L.idl_nce_fused_iic_z, _p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _p(bf.z), _p(bf.P0), C,
+          lamb, EPS, weight, _p(bf.iic_scratch), _p(out), _stream())
+    elif bf.nce_fused and dz:
+        # the joint's 16 x 16 tiles ride in InfoNCE pass 1 as spare workgroups; then the IIC core's first launch and z dP0 with the
+        # gradient's shift in its epilogue (no shift launch, no library GEMM)
+        k(_L.idl_nce_fused_joint, _p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _p(bf.z), _p(bf.P0), C, _stream())
+        k(_L.idl_iic_core_dz, _p(bf.P0), C, lamb, EPS, weight, _p(bf.iic_scratch), _p(out), _p(bf.z), m, _p(bf.dzs), _stream())
+    else:
+        k(_L.idl_iic_joint, _p(bf.z), m, C, _p(bf.P0), _stream())       # (a library GEMM here: 118 us untuned at C = 200)
+        if dz:
+            k(_L.idl_iic_core_dz, _p(bf.P0), C, lamb, EPS, weight, _p(bf.iic_scratch), _p(out), _p(bf.z), m, _p(bf.dzs), _stream())
+        else:
+            k(_L.idl_iic_core, _p(bf.P0), C, lamb, EPS, weight, _p(bf.iic_scratch), _p(out), _stream())
+        if bf.nce_fused:       # S = f f^T, lse, E + E^T and (E + E^T) f in two MFMA kernels, S never written
+            k(_L.idl_nce_fused, _p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _stream())
+        else:                  # (m not a multiple of 32, or above the fused kernels' 2048 rows)
+            torch.mm(bf.f, bf.f.t(), out=bf.S)
+            k(_L.idl_nce_rows, _p(bf.S), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _stream())
+            torch.mm(bf.S, bf.f, out=bf.G[0])                            # (E + E^T) f
+
+
 class _Buffers:
     """Activations / gradients of one batch shape (m = 2*B rows)."""
 
@@ -93,7 +123,7 @@ class _Buffers:
         self.x = self.xs[0]
         self.r1 = sh['r1'] if 'r1' in sh else torch.empty((m, H1), **f32)        # Linear1 output, then ReLU+Dropout in place
         self.r1T = self.r1.view(H1, m)                # the same memory as the transposed image [H1, m] (one of the two is in use)
-        # tail-in-layer-1 (FusedLinearTrainer._tail_l1): the layer-1 launch of step t + 1 writes its activations while riders of the
+        # tail-in-layer-1 (FusedLinearTrainer's tiles form): the layer-1 launch of step t + 1 writes its activations while riders of the
         # same launch still read step t's (dW2 = dlat^T r1), so the steps alternate between two images; made on first use
         self._r1_other = None
         self._H1 = H1
@@ -103,12 +133,12 @@ class _Buffers:
         self.inv = torch.empty((m,), **f32)
         self.r2 = torch.empty((m, H2), **f32)
         self.z = torch.empty((m, C), **f32)
-        self.S = torch.empty((m, m) if not (_L.idl_nce_fused_workspace(m) > 0 and _v("nce_fused") != "0") else (1, 1), **f32)
+        self.nce_ws_bytes = _L.idl_nce_fused_workspace(m)            # -1: shape not supported by the fused InfoNCE kernels
+        self.nce_fused = self.nce_ws_bytes > 0
+        self.S = torch.empty((1, 1) if self.nce_fused else (m, m), **f32)
         self.lse = torch.empty((m,), **f32)
         self.loss_rows = torch.empty((m,), **f32)
         self.nce_parts = _L.idl_nce_fused_parts()
-        self.nce_ws_bytes = _L.idl_nce_fused_workspace(m)            # -1: shape not supported by the fused InfoNCE kernels
-        self.nce_fused = self.nce_ws_bytes > 0 and _v("nce_fused") != "0"
         self.G = torch.empty((self.nce_parts if self.nce_fused else 1, m, H2), **f32)
         self.nce_ws = torch.empty(max(self.nce_ws_bytes, 4) // 4, **f32)
         self.P0 = torch.empty((C, C), **f32)
@@ -169,13 +199,12 @@ class FusedLinearTrainer:
         self.params = [self.W1, self.b1, self.W2, self.b2, self.W3, self.b3]
         self.dev = self.W1.device
         self.F, self.H1, self.H2, self.C = lin1.in_features, lin1.out_features, lin2.out_features, lin3.out_features
-        if self.H2 != 64 or self.C > 256 or lin2.in_features != self.H1 or lin3.in_features != 64:
-            raise ValueError("FusedLinearTrainer needs NetLinear (latent 64) and n_clusters <= 256")
+        if self.H1 != 512 or self.H2 != 64 or self.C > 256 or lin2.in_features != self.H1 or lin3.in_features != 64:
+            raise ValueError("FusedLinearTrainer needs NetLinear (hidden 512, latent 64) and n_clusters <= 256")
         # bias gradients are kept as COL_PARTS stacked partial column sums, added up inside idl_rmsprop_step
         self.parts = [1 if p.dim() == 2 else _L.idl_col_sum_parts() for p in self.params]
-        # the last layer's weight gradient (C x 64) is produced as partials by the bias-gradient launch when C <= 48
-        self._dw3_partial = self.C <= 48 and _v("dw3_partial") != "0"
-        if self._dw3_partial:
+        # the last layer's weight gradient (C x 64) is produced as partials by the middle-backward launch when C <= 48
+        if self.C <= 48:
             self.parts[4] = _L.idl_col_sum_parts()
         self.grads = [torch.zeros((q,) + tuple(p.shape), dtype=p.dtype, device=p.device) if q > 1 else torch.zeros_like(p)
                       for p, q in zip(self.params, self.parts)]
@@ -191,7 +220,6 @@ class FusedLinearTrainer:
         self.out = torch.zeros(4, dtype=torch.float32, device=self.dev)      # [step loss, running sum, nce, iic]
         self._bufs = {}
         self._graphs = {}
-        self._side = torch.cuda.Stream(device=self.dev)     # second branch of the step (see step_on_batch)
         # TEST HOOK (IDELUCS_DEV=test_cold=1; tests/test_gpu_planes.py): a 512 MB fill in front of the step's middle and of each plane kernel, so that every load of
         # the hand-scheduled kernels comes from HBM instead of a warm L2/MALL -- a load consumed before its wait is right when it landed
         # early and wrong when it did not (DESIGN.md History, round 5), and only cold caches show that
@@ -200,10 +228,9 @@ class FusedLinearTrainer:
         # Round 5, default (IDELUCS_PLANES=0: the fp32 tiles below; csrc/planes.h): the two big products on the fp16 matrix cores from operands kept
         # as two fp16 planes (22 significand bits a factor, three products, fp32 accumulators: closer to a float64 product than an fp32 GEMM) --
         # the batch's planes written by the workgroups that assemble it, W1's by the epilogue of the dW1 tiles that update it.  A step
-        # 100.6 us against 111.0 at cfg2 (tools/bench_planes.py).  Needs the default launch sequence of a single voter (tail-in-layer-1),
+        # 100.6 us against 111.0 at cfg2 (tools/bench_planes.py).  Needs a single voter's pipelined step,
         # m % 128 == 0 and F % 512 == 0; any other step runs the fp32 tiles.
         self._planes = planes_default()
-        self._planes_reduce_launch = True        # (round 6: the variant in which mid_fwd added the eight partial sums itself -- +8 us -- was removed)
         # ... and the same for a rank's voters in lockstep (BatchedLinearTrainer; IDELUCS_DEV=lockstep_planes=0: their products as batched fp32
         # library GEMMs instead): the six launches of the two-plane step recorded per voter and run once for all of them, blockIdx.y = voter
         # -- the lone voters' steps bit for bit (tests/test_gpu_planes.py), 47.5 / 45.4 / 43.6 ms a voter-epoch in batches of 2 / 4 / 8
@@ -221,45 +248,12 @@ class FusedLinearTrainer:
         self._dr1_scale = torch.zeros(int(_L.idl_dr1_scale_words()), dtype=torch.int32, device=self.dev)
         self._dr1_scale[1:2].fill_(int(_L.idl_planes_exponent(2)))
         self._w1_planes_fresh = False
-        # the layers between the two big GEMMs as one 1024-thread MFMA kernel per direction (idl_mid_fwd / idl_mid_bwd)
-        self._mid_fused = self.H1 == 512 and _v("mid_fused") != "0"
-        self._pipeline = _v("pipeline") != "0"   # optimizer launch also assembles the next batch
-        # dW2 = dlat^T r1 as 16 x 16 MFMA tiles inside the optimizer launch (idl_rmsprop_step_gather_wgrad) instead of a GEMM launch
-        self._dw2_inlaunch = self.H1 % 16 == 0 and _v("dw2_inlaunch") != "0"
-        self._overlap = _v("overlap") != "0"   # measured: no gain inside a HIP graph on ROCm 7.2
-        # the NEXT batch is assembled by spare workgroups of the mid-forward / mid-backward launches into a second x buffer (instead
-        # of by the optimizer launch, where it competed with RMSprop for HBM): needs the fused middle kernels and n_clusters <= 48
-        self._early_gather = (self._pipeline and self._mid_fused and self.C <= 48 and self.F % 4 == 0
-                              and _v("early_gather") != "0")
-        self._early_split = _v("early_gather") != "2"       # 2: all of it in the mid-backward launch
-        # n_clusters > 48 (fine-grained mode, 200 outputs): the backward runs as separate kernels, so ALL of the next batch's tiles ride
-        # in the mid-forward launch
-        self._early_fwd = (self._pipeline and self._mid_fused and self.C > 48 and self.F % 4 == 0 and self._dw2_inlaunch
-                           and _v("early_gather") != "0")
-        self._gsplit = min(max(int(_v("gather_split")), 0), 8)   # eighths of the tiles the mid-forward launch takes
-        # layer-1 activations kept transposed ([512, m]) between the layer-1 product and its consumers
-        self._transposed_l1 = _v("transposed_l1") != "0"
-        # IDELUCS_DEV=l1_fused=bare: the fp32 form's own layer-1 tiles as a plain product (no riding tail) in place of the library GEMM, mid_fwd unchanged.
-        # (Round 4's variant with bias / ReLU / Dropout and the K-split of Linear(512, 64) in those tiles' epilogue -- 114.7 us a step against 111.8: the
-        #  mid-forward launch is as long as the batch assembly riding in it, not as its head -- left the library in round 6: DESIGN, History.)
-        self._l1_bare = _v("l1_fused") == "bare"
-        # opt-in: InfoNCE pass 2 + IIC core inside the mid-backward launch (one boundary less, but the InfoNCE tiles then run on
-        # the 64 CUs of that launch instead of 256: the fused launch takes 32.8 us against 9.5 + 13.5 -- measured +8 us per step)
-        self._nce_bwd_fused = False              # (round 6: InfoNCE pass 2 + the IIC core inside the mid-backward launch -- +8 us a step -- was removed)
-        self._joint_inlaunch = _v("joint_inlaunch") != "0"   # IIC joint inside the InfoNCE pass-1 launch
-        # dW1 on this package's own MFMA tiles with RMSprop in their epilogue, as the head of the optimizer launch
-        # (csrc/wgrad_device.h, idl_wgrad_rmsprop_step): one launch instead of hipBLASLt's GEMM + the optimizer launch, and the 8 MB
-        # gradient never goes to memory.  IDELUCS_DEV=wgrad_fused=0: hipBLASLt + optimizer launch; =2: the tiles as a launch of their own
-        self._wgrad_fused = _v("wgrad_fused") != "0"
-        self._wgrad_own_launch = _v("wgrad_fused") == "2"
-        self._keep_w1_grad = _v("keep_w1_grad") != "0"       # tests: also write dW1 to grads[0]
-        self._steps_per_graph = max(2, int(_v("steps_per_graph")) // 2 * 2)
-        # Round 5 (IDELUCS_DEV=tail_l1, default on): the layer-1 product on this package's own tiles (idl_l1_fwd: no library build decides
+        self._keep_w1_grad = False               # tests: the dW1 tiles also write dW1 to grads[0]
+        # Round 5, tail-in-layer-1 (the tiles form): the layer-1 product on this package's own tiles (idl_l1_fwd: no library build decides
         # its speed) and the optimizer's TAIL -- the dW2 tiles, the small tensors, step loss, step counter: 5.8 us behind the dW1 tiles
         # of the optimizer launch, where they cannot become resident beside a tile -- riding in the layer-1 launch of the NEXT step
         # (idl_l1_fwd_rms), where they have 30 us of slack.  A step then ends with the dW1 tiles alone; its tail is pending until the
-        # next step's first launch, or flush_tail().  Only the default launch sequence of a single voter takes it.
-        self._tail_l1 = _v("tail_l1") != "0"
+        # next step's first launch, or flush_tail().
         self._pending = None                     # (buffers, parity) of the step whose tail has not run yet
         self._perm = None
         n = len(self.params)
@@ -309,360 +303,306 @@ class FusedLinearTrainer:
             torch.mm(a, b, out=out)
 
     # ------------------------------------------------------------------ one step on a filled bf.x
+    def _form(self, bf, st):
+        """The launch sequence of a step on bf with next_from = st (module docstring): 'record_planes', 'planes', 'planes_rows', 'tiles'
+        or 'general'."""
+        m, H1, F = bf.m, self.H1, self.F
+        if st is None or m % 16 != 0 or F % 4 != 0:      # only a pipelined step's middle launches assemble the next batch
+            return "general"
+        planes = self._planes and st.n < PLANES_MAX_ROWS
+        xplanes = bool(_L.idl_wgrad_xplanes_supported(m, H1, F))
+        wide = 144 <= (H1 // 64) * (F // 128) <= self._cus      # (a dW1 tile per CU, and one for each block of the tail on its loader waves)
+        if self._rec is not None:
+            if (self.C <= 48 and planes and self._planes_lockstep and bf.nce_fused and bool(_L.idl_l1_planes_supported(m, H1, F)) and xplanes
+                    and wide):
+                return "record_planes"
+            return "general"
+        if self._shared_buffers:
+            return "general"
+        if self.C <= 48:
+            if not (_L.idl_l1_fwd_supported(m, H1, F) and _L.idl_wgrad_supported(m, H1, F)):
+                return "general"
+            return "planes" if planes and bool(_L.idl_l1_planes_supported(m, H1, F)) else "tiles"
+        if (planes and self._planes_wgrad and self._planes_tail_wgrad and bool(_L.idl_l1_planes_supported(H1, m, F)) and xplanes and wide):
+            return "planes_rows"
+        return "general"
+
     @torch.no_grad()
     def step_on_batch(self, bf, train=True, batch_advance=0, next_from=None, xi=0, defer_tail=False):
-        """Forward, backward and RMSprop update for the [m, F] batch in bf.x (rows [0,m/2) "true",
-        [m/2,m) "modified").  Only enqueues work on the current stream.  next_from = a FeatureStore: the batch
-        offset is advanced in the middle of the step and the optimizer launch also assembles the NEXT batch into
-        bf.x (both are memory-bound and independent: one launch instead of two)."""
-        m, C, tr = bf.m, self.C, 1 if train else 0
-        x = bf.xs[xi]
-        tl = (self._transposed_l1 and next_from is not None and self._early_gather and self._early_split and m % 16 == 0
-              and self._dw2_inlaunch)
-        early = next_from is not None and self._early_gather and m % 16 == 0   # next batch -> bf.xs[1 - xi] by the mid launches
-        early_f = next_from is not None and self._early_fwd and m % 16 == 0    # ... by the mid-forward launch alone
-        if (self._rec is not None and self._planes and self._planes_lockstep and tl and early and self._early_split and not self._nce_bwd_fused
-                and not self._l1_bare and self._wgrad_fused and not self._wgrad_own_launch and not self._overlap
-                and self._joint_inlaunch and self._dw3_partial and bf.nce_fused and C <= 48
-                and bool(_L.idl_l1_planes_supported(m, self.H1, self.F)) and bool(_L.idl_wgrad_xplanes_supported(m, self.H1, self.F))
-                and 144 <= (self.H1 // 64) * (self.F // 128) <= self._cus and next_from.n < 60_000_000):
-            return self._record_planes_step(bf, tr, next_from, xi)
-        # tail-in-layer-1: own layer-1 tiles, the dW1 tiles as the step's last launch, the rest of the optimizer in the NEXT layer-1 launch
-        tm = (self._tail_l1 and tl and early and self._early_split and self._rec is None and not self._l1_bare
-              and not self._nce_bwd_fused and self._wgrad_fused and not self._wgrad_own_launch and not self._shared_buffers
-              and self._dw2_inlaunch and not self._overlap
-              and bool(_L.idl_l1_fwd_supported(m, self.H1, self.F)) and bool(_L.idl_wgrad_supported(m, self.H1, self.F)))
-        if not tm:
+        """Forward, backward and RMSprop update for the [m, F] batch in bf.xs[xi] (rows [0,m/2) "true", [m/2,m) "modified").
+        Only enqueues work on the current stream.  next_from = a FeatureStore: the step advances the batch offset and also
+        assembles the NEXT batch (into bf.xs[1 - xi] where its middle launches do it, else into bf.x).  defer_tail: a step of the
+        planes / tiles forms may leave its optimizer tail pending for the next step's first launch (flush_tail)."""
+        tr, st = 1 if train else 0, next_from
+        form = self._form(bf, st)
+        if form == "record_planes":
+            return self._record_planes_step(bf, tr, st, xi)
+        if form not in ("planes", "tiles"):
             self.flush_tail()                   # (a step of another form: whatever is pending goes first)
-        # ... with the layer-1 product from two-plane operands (IDELUCS_PLANES=1)
-        pl = (tm and self._planes and bool(_L.idl_l1_planes_supported(m, self.H1, self.F)) and next_from.n < 60_000_000)
-        plw = pl and self._planes_wgrad and bool(_L.idl_wgrad_xplanes_supported(m, self.H1, self.F))
-        dpl = plw                              # ... with dr1 written as planes by mid_bwd: both operands of dW1 reach its tiles by LDS-DMA (m % 128 == 0 here)
-        # ... and the same two products in the step of n_clusters > 48 (the fine-grained mode's 200 output units: separate backward kernels, the
-        # whole batch assembled by the mid-forward launch, activations NOT transposed): the layer-1 tiles with the operands' roles swapped
-        # give part[8][m][512]; the dW1 kernel with the tail on its loader waves ends the step
-        plf = (self._planes and self._planes_wgrad and self._planes_reduce_launch and self._planes_tail_wgrad and early_f and not early
-               and not tm and self._rec is None and self._wgrad_fused and not self._wgrad_own_launch and self._dw2_inlaunch
-               and not self._shared_buffers and bool(_L.idl_l1_planes_supported(self.H1, m, self.F))
-               and bool(_L.idl_wgrad_xplanes_supported(m, self.H1, self.F)) and 144 <= (self.H1 // 64) * (self.F // 128) <= self._cus
-               and next_from.n < 60_000_000)
-        pb = _planes_of(bf, self.F) if (pl or plf) else None
-        if not (plw or plf) and getattr(bf, "_planes", None) is not None and not bf._planes["x32"][xi]:
-            raise RuntimeError("the batch in this buffer was assembled as planes only: a step of another form cannot read it")
-        if pl:
-            r1 = pb["part"][xi][0]              # [H1, m]: slab 0 of the partial sums, where mid_fwd leaves the activations
-            self._prepare_planes(bf, pb, xi)
-        elif plf:
-            r1 = pb["part"][xi].view(-1, m, self.H1)[0]      # [m, H1]: slab 0 of part[8][m][512]
-            self._prepare_planes(bf, pb, xi)
+        if form == "planes":
+            self._step_planes(bf, tr, st, xi, defer_tail)
+        elif form == "planes_rows":
+            self._step_planes_rows(bf, tr, st, xi)
+        elif form == "tiles":
+            self._step_tiles(bf, tr, st, xi, defer_tail)
         else:
-            r1 = _r1_of(bf, xi) if tm else bf.r1
-            self._w1_planes_fresh = False       # (this step updates W1 without its planes)
-            if getattr(bf, "_planes", None) is not None:
-                bf._planes["valid"][1 - xi] = False      # (... and assembles the next batch without its planes)
-        r1T = r1.view(self.H1, m)
-        chk = _lib.check
-        main = torch.cuda.current_stream()
-        side = self._side if self._overlap else main
+            self._step_general(bf, tr, batch_advance, st, xi)
+
+    def _next_batch(self, st, m):
+        """The arguments with which a middle launch assembles its share of the next batch: the store, the pair list and the offset."""
+        return (_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
+                _p(st.mean), _p(st.scale), _p(st.inv_scale))
+
+    def _tail(self, bf, sizes=None):
+        """The leading arguments of an optimizer launch: every tensor's RMSprop (sizes: self._sz, or without W1), the step loss."""
+        return (len(self.params), self._pp, self._gp, self._parts, self._vp, self._sz if sizes is None else sizes, _p(self.hyper),
+                _p(self.ctl), _p(bf.loss_rows), bf.m, 1.0 - self.weight, self.weight, _p(self.out))
+
+    def _wg(self, bf, r1, transposed, advance):
+        """The trailing arguments of an optimizer launch: the dW2 = dlat^T r1 tiles, the batch offset's advance, the stream."""
+        m = bf.m
+        return (2, _p(bf.dlat), _p(r1), transposed, m, self.H2, self.H1, _p(self.grads[2]), advance, _stream())
+
+    def _mid_fwd_args(self, bf, tr):
+        return (_p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3), bf.m, self.C, tr, self.seed, _p(self.ctl),
+                _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z))
+
+    def _mid_bwd_args(self, bf, tr, r1, gW3):
+        _, gb1, _, gb2, _, gb3 = self.grads
+        m = bf.m
+        return (_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), _p(self.W2), _p(r1), m, self.C, tr,
+                (1.0 - self.weight) / (m * TEMPERATURE), _p(bf.dlogits), _p(bf.dlat), _p(bf.dr1), _p(gb1), _p(gb2), _p(gb3), _p(gW3))
+
+    def _gw1(self):
+        return _p(self.grads[0]) if self._keep_w1_grad else None
+
+    def _reduce(self, part, m):
+        """The sum of idl_l1_planes' eight K-slice partial sums, with no optimizer tail beside it."""
+        _launch(_L.idl_reduce_parts_rms, _p(part), self.H1 * m, _p(self.ctl), _p(self._ctl_snap), 0, None, None, None, None, None, None, None, None,
+                0, 0.0, 0.0, None, 0, -1, None, None, 0, 0, 0, 0, None, 0, _stream())
+
+    def _check_x32(self, bf, xi):
+        if getattr(bf, "_planes", None) is not None and not bf._planes["x32"][xi]:
+            raise RuntimeError("the batch in this buffer was assembled as planes only: a step of another form cannot read it")
+
+    def _fp32_step(self, bf, xi):
+        """A step that updates W1 without its planes and assembles the next batch without them."""
+        self._check_x32(bf, xi)
+        self._w1_planes_fresh = False
+        if getattr(bf, "_planes", None) is not None:
+            bf._planes["valid"][1 - xi] = False
+
+    def _leave_tail_pending(self, bf, xi, r1, defer_tail):
+        """The dW1 tiles ended the step: the rest of the optimizer is pending for the next step's first launch."""
+        self._pending = (bf, xi, r1)
+        if not defer_tail:
+            self.flush_tail()
+
+    def _step_planes(self, bf, tr, st, xi, defer_tail):
+        """n_clusters <= 48, the two big products from two-plane operands: a1^T = W1 x^T as eight K-slice partial sums on the fp16 matrix
+        cores, ONE launch that adds them up on every CU (beside the previous step's pending tail, if any), mid_fwd (its spare workgroups
+        assemble the first half of the next batch AND its planes), InfoNCE + IIC, mid_bwd (the other half; dr1 as planes), the dW1 tiles."""
+        m, H1, F = bf.m, self.H1, self.F
+        pb = _planes_of(bf, F)
+        plw = self._planes_wgrad and bool(_L.idl_wgrad_xplanes_supported(m, H1, F))     # dW1 from the batch's planes: both operands by LDS-DMA
+        if not plw:
+            self._check_x32(bf, xi)
+        part, x = pb["part"][xi], bf.xs[xi]
+        r1 = part[0]                            # [H1, m]: slab 0 of the partial sums, where mid_fwd leaves the activations
+        self._prepare_planes(bf, pb, xi)
+        wh, wl, flag = self._w1_planes
+        if self._cold:
+            self._evict()
+        _launch(_L.idl_l1_planes, _p(wh), _p(wl), F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, _p(part), _stream())
+        if self._pending is not None:
+            self._tail_launch(*self._pending, red=(part, H1 * m))
+        else:
+            self._reduce(part, m)
+        if self._cold:
+            self._evict()
+        nxt = (None if plw else _p(bf.xs[1 - xi]), _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
+        _launch(_L.idl_mid_fwd_gather_planes, _p(part), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
+                0, GATHER_SPLIT, 8, _stream())
+        launch_losses(_launch, bf, self.lamb, self.weight, self.out)
+        _launch(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), *nxt,
+                GATHER_SPLIT, 8, 8, 1, *self._dr1_planes_args(pb, plw), _stream())
+        pb["valid"][1 - xi] = True
+        pb["x32"][1 - xi] = not plw
+        w1 = (self._gw1(), _p(self.W1), _p(self.square_avg[0]))
+        if plw and self._planes_tail_wgrad and 144 <= (H1 // 64) * (F // 128) <= self._cus:
+            # ... and THIS step's optimizer tail is run by the tiles' loader waves under the tiles' epilogue: nothing is pending
+            if self._cold:
+                self._evict()
+            _launch(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, *w1, _p(wh), _p(wl), _p(flag),
+                    *self._tail(bf), 0, *self._wg(bf, r1, 1, m // 2))
+            return
+        if plw:
+            _launch(_L.idl_wgrad_rmsprop_xplanes, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, *w1, _p(self.hyper),
+                    _p(wh), _p(wl), _p(flag), _stream())
+        else:       # dW1 on the fp32 tiles; their epilogue writes the updated W1's planes for the next layer-1 product
+            _launch(_L.idl_wgrad_rmsprop_planes, _p(bf.dr1), _p(x), m, H1, F, *w1, _p(self.hyper), _p(wh), _p(wl), _p(flag), _stream())
+        self._leave_tail_pending(bf, xi, r1, defer_tail)
+
+    def _step_planes_rows(self, bf, tr, st, xi):
+        """n_clusters > 48 (the fine-grained mode's 200 output units), the two big products from two-plane operands: the layer-1 tiles with
+        the operands' roles swapped give part[8][m][512] (activations NOT transposed), mid_fwd assembles the whole next batch as planes
+        only, the IIC core writes z dP0, ONE launch for the rest of the middle backward (softmax / Linear(64,C) / normalise backward per
+        row, dr1 = dlat W2 as planes for the dW1 tiles, every bias gradient), dW3 on idl_at_b, and the dW1 tiles with the whole
+        optimizer tail on their loader waves end the step."""
+        m, C, H1, F = bf.m, self.C, self.H1, self.F
+        pb = _planes_of(bf, F)
+        part = pb["part"][xi]
+        r1 = part.view(-1, m, H1)[0]            # [m, H1]: slab 0 of part[8][m][512]
+        self._prepare_planes(bf, pb, xi)
+        wh, wl, flag = self._w1_planes
+        if self._cold:
+            self._evict()
+        _launch(_L.idl_l1_planes, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, _p(wh), _p(wl), F, H1, m, F, _p(part), _stream())
+        self._reduce(part, m)
+        if self._cold:
+            self._evict()
+        nxt = (None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
+        # (the bias of Linear(F,512) is added here)
+        _launch(_L.idl_mid_fwd_gather_planes, _p(r1), _p(self.b1), 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
+                0, GATHER_SPLIT, 8, _stream())
+        dz = 48 < C <= 200
+        launch_losses(_launch, bf, self.lamb, self.weight, self.out, dz=dz)
+        if not dz:
+            torch.mm(bf.z, bf.P0, out=bf.dzs)
+        _launch(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, None), *self._next_batch(st, m), *nxt,
+                GATHER_SPLIT, 8, 8, 0, *self._dr1_planes_args(pb, True, bf.dzs), _stream())
+        pb["valid"][1 - xi] = True
+        pb["x32"][1 - xi] = False
+        _launch(_L.idl_at_b, _p(bf.dlogits), C, _p(bf.r2), self.H2, m, C, self.H2, _p(self.grads[4]), self.H2, _stream())      # dW3 = dlogits^T r2
+        if self._cold:
+            self._evict()
+        _launch(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, self._gw1(), _p(self.W1),
+                _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *self._tail(bf), 0, *self._wg(bf, r1, 0, m // 2))
+
+    def _step_tiles(self, bf, tr, st, xi, defer_tail):
+        """n_clusters <= 48 on the fp32 tiles: a1^T = W1 x^T on own tiles (the previous step's optimizer tail rides in the same launch),
+        mid_fwd + its share of the next batch, InfoNCE + IIC, mid_bwd + the rest of the next batch, the dW1 tiles with RMSprop."""
+        m, H1, F = bf.m, self.H1, self.F
+        self._fp32_step(bf, xi)
+        x, r1 = bf.xs[xi], _r1_of(bf, xi)
+        if self._pending is not None:
+            self._tail_launch(*self._pending, l1=(x, m, r1.view(H1, m)))
+        else:
+            _launch(_L.idl_l1_fwd, _p(self.W1), _p(x), m, F, _p(r1.view(H1, m)), _stream())
+        if self._cold:
+            self._evict()
+        _launch(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
+                0, GATHER_SPLIT, 8, _stream())
+        launch_losses(_launch, bf, self.lamb, self.weight, self.out)
+        _launch(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
+                GATHER_SPLIT, 8, 8, 1, _stream())
+        _launch(_L.idl_wgrad_rmsprop, _p(bf.dr1), _p(x), m, H1, F, self._gw1(), _p(self.W1), _p(self.square_avg[0]), _p(self.hyper), _stream())
+        self._leave_tail_pending(bf, xi, r1, defer_tail)
+
+    def _step_general(self, bf, tr, batch_advance, st, xi):
+        """Library GEMMs and the unfused kernels where a shape needs them.  A pipelined step with m % 16 == 0 has the next batch
+        assembled by its middle launches (n_clusters <= 48: both, the launches recordable for BatchedLinearTrainer; else the forward
+        alone); any other pipelined step assembles it into bf.x in its optimizer launch."""
+        m, C, H1, F = bf.m, self.C, self.H1, self.F
+        early = st is not None and m % 16 == 0 and F % 4 == 0
+        both = early and C <= 48
+        k = self._k if early else _launch
+        self._fp32_step(bf, xi)
+        x, r1 = bf.xs[xi], bf.r1
+        gW1, gb1, gW2, gb2, gW3, gb3 = self.grads
         # ---- forward
-        # shares (eighths) of the next batch's assembly: [0, g2) the mid-forward launch, [g2, 8) mid-backward
-        g1 = 0
-        g2 = self._gsplit
-        if pl:
-            # a1^T = W1 x^T as eight K-slice partial sums on the fp16 matrix cores, then ONE launch that adds the eight up on every CU (and, in the
-            # variant that keeps the tail off the dW1 tiles' loader waves, runs the previous step's optimizer tail beside that)
-            wh, wl, _ = self._w1_planes
-            if self._cold:
-                self._evict()
-            chk(_L.idl_l1_planes(_p(wh), _p(wl), self.F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), self.F, m, self.H1, self.F, _p(pb["part"][xi]), _stream()))
-            if self._pending is not None:
-                pbf, pxi, pr1 = self._pending
-                self._tail_launch(pbf, pxi, pr1, red=(pb["part"][xi], self.H1 * m))
-            else:
-                chk(_L.idl_reduce_parts_rms(_p(pb["part"][xi]), self.H1 * m, _p(self.ctl), _p(self._ctl_snap), 0, None, None, None, None, None, None, None, None, 0, 0.0, 0.0, None, 0,
-                                            -1, None, None, 0, 0, 0, 0, None, 0, _stream()))
-        elif tm:    # a1^T = W1 x^T on own tiles; the previous step's optimizer tail rides in the same launch
-            if self._pending is not None:
-                pbf, pxi, pr1 = self._pending
-                self._tail_launch(pbf, pxi, pr1, l1=(x, m, r1T))
-            else:
-                chk(_L.idl_l1_fwd(_p(self.W1), _p(x), m, self.F, _p(r1T), _stream()))
-        elif plf:   # a1 = x W1^T as eight K-slice partial sums [8][m][512] (the tiles of idl_l1_planes with the operands' roles swapped), then their sum
-            wh, wl, _ = self._w1_planes
-            if self._cold:
-                self._evict()
-            chk(_L.idl_l1_planes(_p(pb["xh"][xi]), _p(pb["xl"][xi]), self.F, _p(wh), _p(wl), self.F, self.H1, m, self.F, _p(pb["part"][xi]), _stream()))
-            chk(_L.idl_reduce_parts_rms(_p(pb["part"][xi]), self.H1 * m, _p(self.ctl), _p(self._ctl_snap), 0, None, None, None, None, None, None, None, None, 0, 0.0, 0.0, None, 0,
-                                        -1, None, None, 0, 0, 0, 0, None, 0, _stream()))
-        elif tl and self._l1_bare and self._rec is None and bool(_L.idl_l1_fwd_supported(m, self.H1, self.F)):
-            chk(_L.idl_l1_fwd(_p(self.W1), _p(x), m, self.F, _p(r1), _stream()))
-        elif tl:    # a1^T = W1 x^T: the orientation hipBLASLt runs this product fastest in; mid_fwd adds the bias
-            self._mm(self.W1, x.t(), r1T)
+        if both:    # a1^T = W1 x^T: the orientation hipBLASLt runs this product fastest in; mid_fwd adds the bias
+            self._mm(self.W1, x.t(), r1.view(H1, m))
         else:
             torch.addmm(self.b1, x, self.W1.t(), out=r1)
         if self._cold:
             self._evict()
-        if pl:      # mid_fwd adds the eight partial sums; its spare workgroups assemble the first half of the next batch AND its planes
-            st = next_from
-            chk(_L.idl_mid_fwd_gather_planes(_p(pb["part"][xi]), _p(self.b1), 1, _p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3),
-                                             m, C, tr, self.seed, _p(self.ctl), _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
-                                             _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                                             _p(st.mean), _p(st.scale), _p(st.inv_scale), None if plw else _p(bf.xs[1 - xi]), _p(pb["xh"][1 - xi]),
-                                             _p(pb["xl"][1 - xi]), _p(self._w1_planes[2]), g1, g2, 8, _stream()))
-        elif early and self._early_split:         # ... and the first half of the next batch's tiles in its spare workgroups
-            st = next_from
-            self._k(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1) if tl else None,
-                    1 if tl else 0, _p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3),
-                    m, C, tr, self.seed, _p(self.ctl),
-                    _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
-                    _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                    _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.xs[1 - xi]), g1, g2, 8, _stream())
-        elif plf:   # (the bias of Linear(F,512) is added here; the whole next batch assembled as planes only)
-            st = next_from
-            # (round 6: the fused middle-backward of this mode carries the other half of the next batch's assembly, as at n_clusters <= 48)
-            chk(_L.idl_mid_fwd_gather_planes(_p(r1), _p(self.b1), 0, _p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3),
-                                             m, C, tr, self.seed, _p(self.ctl), _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
-                                             _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                                             _p(st.mean), _p(st.scale), _p(st.inv_scale), None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]),
-                                             _p(self._w1_planes[2]), 0, self._gsplit, 8, _stream()))
-        elif early_f:
-            st = next_from
-            chk(_L.idl_mid_fwd_gather(_p(r1), None, 0, _p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3),
-                                      m, C, tr, self.seed, _p(self.ctl),
-                                      _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
-                                      _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                                      _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.xs[1 - xi]), 0, 8, 8, _stream()))
-        elif self._mid_fused and m % 16 == 0:   # ReLU/Dropout + Linear(512,64) + head in one MFMA kernel
-            chk(_L.idl_mid_fwd(_p(r1), _p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3), m, C, tr, self.seed, _p(self.ctl),
-                               _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z), _stream()))
+        if both:
+            k(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
+              0, GATHER_SPLIT, 8, _stream())
+        elif early:     # (n_clusters > 48: ALL of the next batch's tiles ride in the mid-forward launch)
+            k(_L.idl_mid_fwd_gather, _p(r1), None, 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]), 0, 8, 8, _stream())
+        elif m % 16 == 0:   # ReLU/Dropout + Linear(512,64) + head in one MFMA kernel
+            k(_L.idl_mid_fwd, _p(r1), *self._mid_fwd_args(bf, tr), _stream())
         else:
-            chk(_L.idl_relu_dropout_fwd(_p(r1), r1.numel(), tr, self.seed, _p(self.ctl), 1, _stream()))
+            k(_L.idl_relu_dropout_fwd, _p(r1), r1.numel(), tr, self.seed, _p(self.ctl), 1, _stream())
             torch.addmm(self.b2, r1, self.W2.t(), out=bf.lat)
-            chk(_L.idl_head_fwd(_p(bf.lat), _p(self.W3), _p(self.b3), m, C, tr, self.seed, _p(self.ctl),
-                                _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z), _stream()))
-        # ---- the two losses are independent: with the fused InfoNCE kernels the IIC core rides along as one extra workgroup
-        if bf.nce_fused and C <= 48 and not self._overlap and self._joint_inlaunch:
-            # the IIC workgroup of InfoNCE pass 1 forms the joint z1^T z2 itself (MFMA tiles) before the core
-            self._k(_L.idl_nce_fused_iic_z, _p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _p(bf.z),
-                    _p(bf.P0), C, self.lamb, EPS, self.weight, _p(bf.iic_scratch), _p(self.out), _stream())
-        elif bf.nce_fused and C <= 48 and not self._overlap:
-            torch.mm(bf.z[:m // 2].t(), bf.z[m // 2:], out=bf.P0)            # IIC joint, one [C,B]x[B,C] GEMM
-            chk(_L.idl_nce_fused_iic(_p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws),
-                                     _p(bf.P0), C, self.lamb, EPS, self.weight, _p(bf.iic_scratch), _p(self.out), _stream()))
-        elif plf and bf.nce_fused and 48 < C <= 200:
-            # n_clusters > 48, round 6: the joint's 16 x 16 tiles ride in InfoNCE pass 1 as spare workgroups; then the IIC core's first launch and z dP0
-            # with the gradient's shift in its epilogue (no shift launch, no library GEMM)
-            chk(_L.idl_nce_fused_joint(_p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _p(bf.z), _p(bf.P0), C, _stream()))
-            chk(_L.idl_iic_core_dz(_p(bf.P0), C, self.lamb, EPS, self.weight, _p(bf.iic_scratch), _p(self.out), _p(bf.z), m, _p(bf.dzs), _stream()))
-        else:
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                chk(_L.idl_iic_joint(_p(bf.z), m, C, _p(bf.P0), _stream()))       # (a library GEMM here: 118 us untuned at C = 200)
-                if plf and 48 < C <= 200:    # the core's first launch, then z dP0 with the gradient's shift in its epilogue (no shift launch, no library GEMM)
-                    chk(_L.idl_iic_core_dz(_p(bf.P0), C, self.lamb, EPS, self.weight, _p(bf.iic_scratch), _p(self.out), _p(bf.z), m, _p(bf.dzs), _stream()))
-                else:
-                    chk(_L.idl_iic_core(_p(bf.P0), C, self.lamb, EPS, self.weight, _p(bf.iic_scratch), _p(self.out), _stream()))
-            if bf.nce_fused:       # S = f f^T, lse, E + E^T and (E + E^T) f in two MFMA kernels, S never written
-                chk(_L.idl_nce_fused(_p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _stream()))
-            else:
-                torch.mm(bf.f, bf.f.t(), out=bf.S)
-                chk(_L.idl_nce_rows(_p(bf.S), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _stream()))
-                torch.mm(bf.S, bf.f, out=bf.G[0])                            # (E + E^T) f
-        main.wait_stream(side)
+            k(_L.idl_head_fwd, _p(bf.lat), _p(self.W3), _p(self.b3), m, C, tr, self.seed, _p(self.ctl), _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
+              _stream())
+        launch_losses(k, bf, self.lamb, self.weight, self.out)
+        # ---- backward
+        adv_ctl, adv = (_p(self.ctl), batch_advance) if (st is not None and not early) else (None, 0)
         nce_coef = (1.0 - self.weight) / (m * TEMPERATURE)
-        gW1, gb1, gW2, gb2, gW3, gb3 = self.grads
-        adv_ctl = _p(self.ctl) if (next_from is not None and not early and not early_f) else None
-        adv = batch_advance if (next_from is not None and not early and not early_f) else 0
-        if pl:
-            st = next_from
-            chk(_L.idl_mid_bwd_gather_planes(_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), _p(self.W2),
-                                             _p(r1), m, C, tr, nce_coef, _p(bf.dlogits), _p(bf.dlat), _p(bf.dr1), _p(gb1), _p(gb2), _p(gb3),
-                                             _p(gW3) if self._dw3_partial else None,
-                                             _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                                             _p(st.mean), _p(st.scale), _p(st.inv_scale), None if plw else _p(bf.xs[1 - xi]), _p(pb["xh"][1 - xi]),
-                                             _p(pb["xl"][1 - xi]), _p(self._w1_planes[2]), g2, 8, 8, 1, *self._dr1_planes_args(pb, dpl), _stream()))
-            pb["valid"][1 - xi] = True
-            pb["x32"][1 - xi] = not plw
-            if not self._dw3_partial:
-                torch.mm(bf.dlogits.t(), bf.r2, out=gW3)
-        elif early:
-            st = next_from
-            self._k(_L.idl_mid_bwd_gather, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), _p(self.W2),
-                    _p(r1), m, C, tr, nce_coef, _p(bf.dlogits), _p(bf.dlat), _p(bf.dr1), _p(gb1), _p(gb2), _p(gb3),
-                    _p(gW3) if self._dw3_partial else None,
-                    _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                    _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.xs[1 - xi]), g2 if self._early_split else 0,
-                    8, 8, 1 if tl else 0, _stream())
-            if not self._dw3_partial:
-                torch.mm(bf.dlogits.t(), bf.r2, out=gW3)
-            if not self._dw2_inlaunch:
+        if both:
+            k(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, gW3), *self._next_batch(st, m), _p(bf.xs[1 - xi]), GATHER_SPLIT, 8, 8, 1, _stream())
+        elif C <= 48:   # head backward + dr1 = dlat W2 (MFMA) + ReLU/Dropout backward + every bias gradient + dW3 in one launch
+            k(_L.idl_mid_bwd, *self._mid_bwd_args(bf, tr, r1, gW3), adv_ctl, adv, _stream())
+            if st is None:
                 torch.mm(bf.dlat.t(), r1, out=gW2)
-        elif plf:
-            # n_clusters > 48 (the CLI's default mode: 200 output units), round 6: z dP0 for all rows as one GEMM, then ONE launch for the rest of the
-            # middle backward -- softmax / Linear(64,C) / normalise backward per row with W3 in LDS, dr1 = dlat W2 on MFMA tiles masked by the layer-1
-            # ReLU / Dropout and written as two fp16 planes for the dW1 tiles, every bias gradient as stacked partial sums, the second half of the
-            # next batch assembled by spare workgroups -- in place of idl_head_bwd_dz + a library GEMM + idl_bias_grads (11.8 + 9.0 + 4.9 us)
-            st = next_from
-            if not 48 < C <= 200:
+        else:           # (at n_clusters = 200 the per-row C x C products want all 256 CUs: separate kernels)
+            if C > 64:      # z_partner dP0 for all rows as one GEMM instead of 40 000 FMAs per row inside the kernel
                 torch.mm(bf.z, bf.P0, out=bf.dzs)
-            dplf = True                        # (m % 128 == 0 in this form)
-            chk(_L.idl_mid_bwd_gather_planes(_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), _p(self.W2),
-                                             _p(r1), m, C, tr, nce_coef, _p(bf.dlogits), _p(bf.dlat), _p(bf.dr1), _p(gb1), _p(gb2), _p(gb3), None,
-                                             _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                                             _p(st.mean), _p(st.scale), _p(st.inv_scale), None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]),
-                                             _p(self._w1_planes[2]), self._gsplit, 8, 8, 0, *self._dr1_planes_args(pb, dplf, bf.dzs), _stream()))
-            pb["valid"][1 - xi] = True
-            pb["x32"][1 - xi] = False
-            chk(_L.idl_at_b(_p(bf.dlogits), C, _p(bf.r2), self.H2, m, C, self.H2, _p(gW3), self.H2, _stream()))      # dW3 = dlogits^T r2 (the library's kernel: 9 us)
-        elif self._mid_fused and C <= 48:     # (at n_clusters = 200 the per-row C x C products want all 256 CUs: separate kernels)
-            # ---- head backward + dr1 = dlat W2 (MFMA) + ReLU/Dropout backward + every bias gradient (+ dW3) in one launch
-            chk(_L.idl_mid_bwd(_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), _p(self.W2),
-                               _p(r1), m, C, tr, nce_coef, _p(bf.dlogits), _p(bf.dlat), _p(bf.dr1), _p(gb1), _p(gb2), _p(gb3),
-                               _p(gW3) if self._dw3_partial else None, adv_ctl, adv, _stream()))
-            if not self._dw3_partial:
-                torch.mm(bf.dlogits.t(), bf.r2, out=gW3)
-            if not (self._dw2_inlaunch and next_from is not None):
-                torch.mm(bf.dlat.t(), r1, out=gW2)
-        else:
-            if C > 64:      # fine-grained mode: z_partner dP0 for all rows as one GEMM instead of 40 000 FMAs per row inside the kernel
-                torch.mm(bf.z, bf.P0, out=bf.dzs)
-                chk(_L.idl_head_bwd_dz(_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.dzs), _p(self.W3), m, C, tr,
-                                       nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream()))
+                k(_L.idl_head_bwd_dz, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.dzs), _p(self.W3), m, C, tr,
+                  nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream())
             else:
-                chk(_L.idl_head_bwd(_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), m, C, tr,
-                                    nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream()))
-            # ---- parameter gradients (one launch for the three bias gradients + the ReLU/Dropout backward of layer 1)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                if not self._dw3_partial:
-                    torch.mm(bf.dlogits.t(), bf.r2, out=gW3)
-                if not (self._dw2_inlaunch and next_from is not None):
-                    torch.mm(bf.dlat.t(), r1, out=gW2)
+                k(_L.idl_head_bwd, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), m, C, tr,
+                  nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream())
+            torch.mm(bf.dlogits.t(), bf.r2, out=gW3)
+            if st is None:
+                torch.mm(bf.dlat.t(), r1, out=gW2)
             torch.mm(bf.dlat, self.W2, out=bf.dr1)
-            chk(_L.idl_bias_grads(_p(bf.dr1), _p(r1), self.H1, _p(gb1), _p(bf.dlat), self.H2, _p(gb2), _p(bf.dlogits), C, _p(gb3),
-                                  m, tr, adv_ctl, adv, _p(bf.r2) if self._dw3_partial else None,
-                                  _p(gW3) if self._dw3_partial else None, _stream()))
-        if tm:      # the dW1 tiles end the step; everything else of the optimizer rides in the next step's layer-1 launch
-            if plw:     # dW1 from the batch's planes on the fp16 matrix cores; the epilogue writes the updated W1 and its planes
-                wh, wl, flag = self._w1_planes
-                # (a tile per CU, and a tile for each of the tail's blocks: 128 dW2 tiles + at most 16 blocks for the small tensors)
-                if self._planes_tail_wgrad and self._planes_reduce_launch and 144 <= (self.H1 // 64) * (self.F // 128) <= self._cus:
-                    # ... and THIS step's optimizer tail is run by the tiles' loader waves under the tiles' epilogue: nothing is pending
-                    tail = (len(self.params), self._pp, self._gp, self._parts, self._vp, self._sz, _p(self.hyper),
-                            _p(self.ctl), _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out))
-                    wg = (2, _p(bf.dlat), _p(r1), 1, m, self.H2, self.H1, _p(self.grads[2]), m // 2, _stream())
-                    if self._cold:
-                        self._evict()
-                    chk(_L.idl_wgrad_xplanes_rms(*self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), self.F, m, self.H1, self.F,
-                                                 _p(gW1) if self._keep_w1_grad else None, _p(self.W1), _p(self.square_avg[0]),
-                                                 _p(wh), _p(wl), _p(flag), *tail, 0, *wg))
-                    self._pending = None
-                    return
-                chk(_L.idl_wgrad_rmsprop_xplanes(*self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), self.F, m, self.H1, self.F,
-                                                 _p(gW1) if self._keep_w1_grad else None, _p(self.W1), _p(self.square_avg[0]), _p(self.hyper),
-                                                 _p(wh), _p(wl), _p(flag), _stream()))
-            elif pl:    # ... and write the updated W1's planes for the next layer-1 product
-                wh, wl, flag = self._w1_planes
-                chk(_L.idl_wgrad_rmsprop_planes(_p(bf.dr1), _p(x), m, self.H1, self.F, _p(gW1) if self._keep_w1_grad else None, _p(self.W1),
-                                                _p(self.square_avg[0]), _p(self.hyper), _p(wh), _p(wl), _p(flag), _stream()))
-            else:
-                chk(_L.idl_wgrad_rmsprop(_p(bf.dr1), _p(x), m, self.H1, self.F, _p(gW1) if self._keep_w1_grad else None, _p(self.W1),
-                                         _p(self.square_avg[0]), _p(self.hyper), _stream()))
-            self._pending = (bf, xi, r1)
-            if not defer_tail:
-                self.flush_tail()
-            return
-        if plf:     # dW1 from the batch's planes with RMSprop and W1's planes in the epilogue; the rest of the optimizer on the loader waves
-            main.wait_stream(side)
-            wh, wl, flag = self._w1_planes
-            tail = (len(self.params), self._pp, self._gp, self._parts, self._vp, self._sz, _p(self.hyper),
-                    _p(self.ctl), _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out))
-            wg = (2, _p(bf.dlat), _p(r1), 0, m, self.H2, self.H1, _p(gW2), m // 2, _stream())
-            if self._cold:
-                self._evict()
-            chk(_L.idl_wgrad_xplanes_rms(*self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), self.F, m,
-                                         self.H1, self.F, _p(gW1) if self._keep_w1_grad else None, _p(self.W1), _p(self.square_avg[0]),
-                                         _p(wh), _p(wl), _p(flag), *tail, 0, *wg))
-            return
-        w1_fusable = self._wgrad_fused and bool(_L.idl_wgrad_supported(m, self.H1, self.F))
-        # the tiles ride at the head of the optimizer launch where that launch has the form below; else as a launch of their own
-        w1_head = w1_fusable and (early or early_f) and self._dw2_inlaunch and not self._wgrad_own_launch
-        w1_done = w1_fusable and not w1_head and self._rec is None     # (a recorded step takes the tiles only inside its optimizer launch)
-        gw1_out = _p(gW1) if self._keep_w1_grad else None
-        if w1_done:
-            chk(_L.idl_wgrad_rmsprop(_p(bf.dr1), _p(x), m, self.H1, self.F, gw1_out, _p(self.W1), _p(self.square_avg[0]), _p(self.hyper),
-                                     _stream()))
-        elif not w1_head:
+            # (one launch for the three bias gradients + the ReLU/Dropout backward of layer 1)
+            k(_L.idl_bias_grads, _p(bf.dr1), _p(r1), H1, _p(gb1), _p(bf.dlat), self.H2, _p(gb2), _p(bf.dlogits), C, _p(gb3),
+              m, tr, adv_ctl, adv, None, None, _stream())
+        # ---- dW1 on own MFMA tiles with RMSprop in their epilogue: at the head of the optimizer launch of a pipelined step, else a
+        # launch of its own (a recorded step takes the tiles only inside its optimizer launch); dW1 as a GEMM where the tiles do not apply
+        w1_tiles = bool(_L.idl_wgrad_supported(m, H1, F))
+        sizes = self._sz
+        if w1_tiles and not early and self._rec is None:
+            _launch(_L.idl_wgrad_rmsprop, _p(bf.dr1), _p(x), m, H1, F, self._gw1(), _p(self.W1), _p(self.square_avg[0]), _p(self.hyper), _stream())
+            sizes = self._sz_no_w1
+        elif not (w1_tiles and early):
             self._mm(bf.dr1.t(), x, gW1)
-        sz = self._sz_no_w1 if w1_done else self._sz
-        main.wait_stream(side)
         # ---- RMSprop (and advance the device-side step counter / batch offset)
-        if w1_head:
-            self._k(_L.idl_wgrad_rmsprop_step, len(self.params), self._pp, self._gp, self._parts, self._vp, sz, _p(self.hyper),
-                    _p(self.ctl), _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out),
-                    0, _p(bf.dr1), _p(x), m, self.H1, self.F, gw1_out,
-                    2, _p(bf.dlat), _p(r1), 1 if tl else 0, m, self.H2, self.H1, _p(gW2), m // 2, _stream())
-        elif (early or early_f) and self._dw2_inlaunch:      # no batch assembly here; the offset moves on at the end of the step
-            self._k(_L.idl_rmsprop_step_gather_wgrad, len(self.params), self._pp, self._gp, self._parts, self._vp, sz, _p(self.hyper),
-                    _p(self.ctl), _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out),
-                    None, 0, 0, 0, None, 0, 0, None, None, None, None,
-                    2, _p(bf.dlat), _p(r1), 1 if tl else 0, m, self.H2, self.H1, _p(gW2), m // 2, _stream())
-        elif early:
-            chk(_L.idl_rmsprop_step(len(self.params), self._pp, self._gp, self._parts, self._vp, sz, _p(self.hyper),
-                                    _p(self.ctl), m // 2, _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out), _stream()))
-        elif next_from is not None and self._dw2_inlaunch:
-            st = next_from
-            chk(_L.idl_rmsprop_step_gather_wgrad(len(self.params), self._pp, self._gp, self._parts, self._vp, sz, _p(self.hyper),
-                                                 _p(self.ctl), _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out),
-                                                 _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs, m // 2,
-                                                 _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.x),
-                                                 2, _p(bf.dlat), _p(r1), 0, m, self.H2, self.H1, _p(gW2), 0, _stream()))
-        elif next_from is not None:
-            st = next_from
-            chk(_L.idl_rmsprop_step_gather(len(self.params), self._pp, self._gp, self._parts, self._vp, sz, _p(self.hyper),
-                                           _p(self.ctl), _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out),
-                                           _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs, m // 2,
-                                           _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.x), _stream()))
+        if w1_tiles and early:
+            k(_L.idl_wgrad_rmsprop_step, *self._tail(bf, sizes), 0, _p(bf.dr1), _p(x), m, H1, F, self._gw1(), *self._wg(bf, r1, int(both), m // 2))
+        elif early:     # no batch assembly here; the offset moves on at the end of the step
+            k(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, sizes), None, 0, 0, 0, None, 0, 0, None, None, None, None,
+              *self._wg(bf, r1, int(both), m // 2))
+        elif st is not None:
+            _launch(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, sizes), _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs,
+                    m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.x), *self._wg(bf, r1, 0, 0))
         else:
-            chk(_L.idl_rmsprop_step(len(self.params), self._pp, self._gp, self._parts, self._vp, sz, _p(self.hyper),
-                                    _p(self.ctl), batch_advance, _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out),
-                                    _stream()))
+            _launch(_L.idl_rmsprop_step, len(self.params), self._pp, self._gp, self._parts, self._vp, sizes, _p(self.hyper), _p(self.ctl),
+                    batch_advance, _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out), _stream())
 
-    def _record_planes_step(self, bf, tr, st, xi):
-        """The two-plane step (step_on_batch's default form of a lone voter: layer-1 tiles, the sum of their partials, mid_fwd, InfoNCE + IIC,
-        mid_bwd, the dW1 tiles with the tail on their loader waves) as six RECORDED launches: BatchedLinearTrainer runs each once for all the
-        voters of a rank.  Nothing is launched here but what allocates this voter's plane buffers."""
-        m, C = bf.m, self.C
-        pb = _planes_of(bf, self.F)
+    def _w1_planes_of(self):
+        """W1's planes and the planes' overflow flag, made on first use."""
         if self._w1_planes is None:
             self._w1_planes = (torch.empty(self.W1.shape, dtype=torch.int16, device=self.dev), torch.empty(self.W1.shape, dtype=torch.int16, device=self.dev),
                                torch.zeros(1, dtype=torch.int32, device=self.dev))
-        wh, wl, flag = self._w1_planes
+        return self._w1_planes
+
+    def _record_planes_step(self, bf, tr, st, xi):
+        """The two-plane step (the planes form of a lone voter: layer-1 tiles, the sum of their partials, mid_fwd, InfoNCE + IIC,
+        mid_bwd, the dW1 tiles with the tail on their loader waves) as six RECORDED launches: BatchedLinearTrainer runs each once for all the
+        voters of a rank.  Nothing is launched here but what allocates this voter's plane buffers."""
+        m, H1, F = bf.m, self.H1, self.F
+        pb = _planes_of(bf, F)
+        wh, wl, flag = self._w1_planes_of()
         part = pb["part"][xi]
         r1 = part[0]
-        gW1, gb1, gW2, gb2, gW3, gb3 = self.grads
-        nce_coef = (1.0 - self.weight) / (m * TEMPERATURE)
-        g2 = self._gsplit
-        dpl = True
-        self._k(_L.idl_l1_planes, _p(wh), _p(wl), self.F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), self.F, m, self.H1, self.F, _p(part), _stream())
-        self._k(_L.idl_reduce_parts_rms, _p(part), self.H1 * m, _p(self.ctl), _p(self._ctl_snap), 0, None, None, None, None, None, None, None, None, 0, 0.0, 0.0,
+        nxt = (None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
+        self._k(_L.idl_l1_planes, _p(wh), _p(wl), F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, _p(part), _stream())
+        self._k(_L.idl_reduce_parts_rms, _p(part), H1 * m, _p(self.ctl), _p(self._ctl_snap), 0, None, None, None, None, None, None, None, None, 0, 0.0, 0.0,
                 None, 0, -1, None, None, 0, 0, 0, 0, None, 0, _stream())
-        self._k(_L.idl_mid_fwd_gather_planes, _p(part), _p(self.b1), 1, _p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3),
-                m, C, tr, self.seed, _p(self.ctl), _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
-                _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                _p(st.mean), _p(st.scale), _p(st.inv_scale), None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag), 0, g2, 8, _stream())
-        self._k(_L.idl_nce_fused_iic_z, _p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _p(bf.z),
-                _p(bf.P0), C, self.lamb, EPS, self.weight, _p(bf.iic_scratch), _p(self.out), _stream())
-        self._k(_L.idl_mid_bwd_gather_planes, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), _p(self.W2),
-                _p(r1), m, C, tr, nce_coef, _p(bf.dlogits), _p(bf.dlat), _p(bf.dr1), _p(gb1), _p(gb2), _p(gb3), _p(gW3),
-                _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                _p(st.mean), _p(st.scale), _p(st.inv_scale), None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag), g2, 8, 8, 1,
-                *self._dr1_planes_args(pb, dpl), _stream())
-        tail = (len(self.params), self._pp, self._gp, self._parts, self._vp, self._sz, _p(self.hyper),
-                _p(self.ctl), _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out))
-        wg = (2, _p(bf.dlat), _p(r1), 1, m, self.H2, self.H1, _p(gW2), m // 2, _stream())
-        self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), self.F, m, self.H1, self.F, None, _p(self.W1),
-                _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *tail, 0, *wg)
+        self._k(_L.idl_mid_fwd_gather_planes, _p(part), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
+                0, GATHER_SPLIT, 8, _stream())
+        launch_losses(self._k, bf, self.lamb, self.weight, self.out)
+        self._k(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), *nxt, GATHER_SPLIT, 8, 8, 1,
+                *self._dr1_planes_args(pb, True), _stream())
+        self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, None, _p(self.W1),
+                _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *self._tail(bf), 0, *self._wg(bf, r1, 1, m // 2))
 
     def _dr1_planes_args(self, pb, on, dzs=None):
         """idl_mid_bwd_gather_planes' last arguments: dr1's planes and the words of their scale (or none of them: dr1 in fp32), and z dP0 as an
@@ -685,19 +625,15 @@ class FusedLinearTrainer:
         """The optimizer's tail of the step that ran on (bf, xi) with the activations r1: dW2 tiles + RMSprop on every tensor but W1 + step
         loss + step counter -- behind the layer-1 tiles of the next step (l1 = (x, m, r1T) of THAT step), beside the workgroups that add up the next
         step's layer-1 partial sums (red), or as a launch of its own."""
-        m = bf.m
-        tail = (len(self.params), self._pp, self._gp, self._parts, self._vp, self._sz, _p(self.hyper),
-                _p(self.ctl), _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out))
-        wg = (2, _p(bf.dlat), _p(r1), 1, m, self.H2, self.H1, _p(self.grads[2]), m // 2, _stream())
+        wg = self._wg(bf, r1, 1, bf.m // 2)
         if red is not None:       # beside the workgroups that add up the next step's layer-1 partial sums (red = (part, elements of a slab))
             part, slab = red
-            _lib.check(_L.idl_reduce_parts_rms(_p(part), slab, None, None, *tail, 0, *wg))
+            _launch(_L.idl_reduce_parts_rms, _p(part), slab, None, None, *self._tail(bf), 0, *wg)
         elif l1 is not None:
             x, m1, r1T = l1
-            _lib.check(_L.idl_l1_fwd_rms(_p(self.W1), _p(x), m1, self.F, _p(r1T), *tail, 0, *wg))
+            _launch(_L.idl_l1_fwd_rms, _p(self.W1), _p(x), m1, self.F, _p(r1T), *self._tail(bf), 0, *wg)
         else:       # (sizes without W1: the tiles' own launch updated it)
-            tail = tail[:5] + (self._sz_no_w1,) + tail[6:]
-            _lib.check(_L.idl_rmsprop_step_gather_wgrad(*tail, None, 0, 0, 0, None, 0, 0, None, None, None, None, *wg))
+            _launch(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, self._sz_no_w1), None, 0, 0, 0, None, 0, 0, None, None, None, None, *wg)
         self._pending = None
 
     def flush_tail(self):
@@ -710,16 +646,13 @@ class FusedLinearTrainer:
     def _prepare_planes(self, bf, pb, xi):
         """Before a step of the two-plane form: W1's planes (made once; afterwards the dW1 tiles' epilogue keeps them) and the planes of the
         batch in bf.xs[xi] unless the step that assembled it wrote them."""
-        if self._w1_planes is None:
-            self._w1_planes = (torch.empty(self.W1.shape, dtype=torch.int16, device=self.dev), torch.empty(self.W1.shape, dtype=torch.int16, device=self.dev),
-                               torch.zeros(1, dtype=torch.int32, device=self.dev))
+        wh, wl, flag = self._w1_planes_of()
         if not self._w1_planes_fresh:
-            wh, wl, flag = self._w1_planes
             _lib.check(_L.idl_split_planes(_p(self.W1), self.W1.numel(), int(_L.idl_planes_exponent(1)), _p(wh), _p(wl), _p(flag), _stream()))
             self._w1_planes_fresh = True
         if not pb["valid"][xi]:
             x = bf.xs[xi]
-            _lib.check(_L.idl_split_planes(_p(x), x.numel(), int(_L.idl_planes_exponent(0)), _p(pb["xh"][xi]), _p(pb["xl"][xi]), _p(self._w1_planes[2]), _stream()))
+            _lib.check(_L.idl_split_planes(_p(x), x.numel(), int(_L.idl_planes_exponent(0)), _p(pb["xh"][xi]), _p(pb["xl"][xi]), _p(flag), _stream()))
             pb["valid"][xi] = True
 
     def _evict(self):
@@ -759,11 +692,10 @@ class FusedLinearTrainer:
 
     def _full_step(self, store, bf, train=True, pipelined=False, xi=0, defer_tail=False):
         """pipelined: bf.xs[xi] already holds this batch (assembled by the previous step, or by the prologue gather);
-        this step assembles the next one (into bf.xs[1 - xi] when the mid-backward launch does it, else into bf.xs[xi]).
+        this step assembles the next one (into bf.xs[1 - xi] when the middle launches do it, else into bf.x).
         defer_tail (run_epoch's steps): the step's optimizer tail may wait for the next step's first launch (flush_tail)."""
         if pipelined:
-            self.step_on_batch(bf, train=train, batch_advance=bf.m // 2, next_from=store,
-                               xi=xi if (self._early_gather or self._early_fwd) else 0, defer_tail=defer_tail)
+            self.step_on_batch(bf, train=train, batch_advance=bf.m // 2, next_from=store, xi=xi if self.F % 4 == 0 else 0, defer_tail=defer_tail)
         else:
             self._gather(store, bf)
             self.step_on_batch(bf, train=train, batch_advance=bf.m // 2)
@@ -784,25 +716,23 @@ class FusedLinearTrainer:
         self.ctl[1:2].zero_()
         self.out[1:2].zero_()
         n_full, rem = divmod(n_pairs, batch_sz)
-        pipe = self._pipeline
         if n_full:
             bf = self.buffers(2 * batch_sz)
-            if pipe:
-                self._gather(store, bf)         # prologue: batch 0; every later batch is assembled by the previous step
-                if (self._planes and self._tail_l1 and bool(_L.idl_l1_planes_supported(bf.m, self.H1, self.F))):
-                    self._prepare_planes(bf, _planes_of(bf, self.F), 0)      # (a replayed graph starts from valid planes)
+            self._gather(store, bf)             # prologue: batch 0; every later batch is assembled by the previous step
+            if self._planes and bool(_L.idl_l1_planes_supported(bf.m, self.H1, self.F)):
+                self._prepare_planes(bf, _planes_of(bf, self.F), 0)      # (a replayed graph starts from valid planes)
             # steps per graph replay: an even number when two x buffers alternate.  Between two replays the GPU idles ~9 us
             # (profiles/r02_f: kernel trace), so a replay carries several steps
-            per = self._steps_per_graph if pipe else 1
+            per = STEPS_PER_GRAPH
             while per > 2 and n_full < 2 + 2 * per:      # short epochs: the capture itself runs 2 + per real steps
                 per = max(2, per // 4 * 2)
             # every address the captured launches bake in is part of the key (a store refitted in place keeps its graph)
             key = (2 * batch_sz, store.feats.data_ptr(), store.mean.data_ptr(), store.scale.data_ptr(), store.inv_scale.data_ptr(),
-                   self._perm.data_ptr(), store.n, store.f, store.n_views, pipe, self._early_gather, self._early_fwd, per)
+                   self._perm.data_ptr(), store.n, store.f, store.n_views, per)
             if use_graph and n_full >= 8:
                 g = self._graphs.get(key)
                 if g is None:
-                    g = self._capture(store, bf, pipe, per)
+                    g = self._capture(store, bf, per)
                     self._graphs = {key: g}             # one store at a time: drop graphs of older stores
                     n_done = 2 + per                     # the warm-up + capture already ran real steps (an even number when per == 2)
                 else:
@@ -810,24 +740,24 @@ class FusedLinearTrainer:
                 for _ in range((n_full - n_done) // per):
                     g.replay()
                 for i in range((n_full - n_done) % per):
-                    self._full_step(store, bf, pipelined=pipe, xi=i % 2, defer_tail=True)
+                    self._full_step(store, bf, pipelined=True, xi=i % 2, defer_tail=True)
             else:
                 for i in range(n_full):
-                    self._full_step(store, bf, pipelined=pipe, xi=i % 2, defer_tail=True)
+                    self._full_step(store, bf, pipelined=True, xi=i % 2, defer_tail=True)
         self.flush_tail()                       # (the last eager step's tail; a replayed graph ends with its own)
         if rem:
             self._full_step(store, self.buffers(2 * rem))
         return self.out[1], n_full + (1 if rem else 0)
 
     @torch.no_grad()
-    def _capture(self, store, bf, pipe, per=1):
+    def _capture(self, store, bf, per):
         """Warm up on a side stream (2 real steps), then capture the next `per` real steps into a HIP graph.
         Every launch is a genuine optimizer step on the next batch, so nothing is wasted or repeated."""
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for i in range(2):
-                self._full_step(store, bf, pipelined=pipe, xi=i % 2, defer_tail=True)
+                self._full_step(store, bf, pipelined=True, xi=i % 2, defer_tail=True)
             self.flush_tail()
         torch.cuda.current_stream().wait_stream(s)
         # (tail-in-layer-1: a replay is self-contained -- its first step has nothing pending in front of it, its last step's tail is
@@ -835,7 +765,7 @@ class FusedLinearTrainer:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             for i in range(per):
-                self._full_step(store, bf, pipelined=pipe, xi=i % 2, defer_tail=True)
+                self._full_step(store, bf, pipelined=True, xi=i % 2, defer_tail=True)
             self.flush_tail()
         g.replay()          # capture does not execute: run the captured step(s) once
         self.n_captures = getattr(self, "n_captures", 0) + 1
@@ -850,10 +780,12 @@ class BatchedLinearTrainer:
     The step of voter l is the launch sequence of FusedLinearTrainer.step_on_batch; here each of its launches is issued ONCE for
     all voters: the two big products as batched GEMMs over stacked operands ([L, 512, F] weights, [L, m, F] batches), the five
     kernels as recorded launches (idl_plan_*: every voter's launch is recorded through the ordinary launcher, the records
-    live on the device, the kernels take the voter index from blockIdx.y / .z).  Needs the default launch sequence
-    (n_clusters <= 48, batch 2 x 512 rows assembled by the middle launches)."""
+    live on the device, the kernels take the voter index from blockIdx.y / .z).  Needs n_clusters <= 48 (the middle launches
+    assemble the next batch)."""
 
     def __init__(self, nets, lr, weight, lamb, seed=0):
+        if nets[0].classifier[2].out_features > 48:
+            raise ValueError("BatchedLinearTrainer needs n_clusters <= 48")
         self.L = L = len(nets)
         lin1 = [n.layers[0] for n in nets]
         self.dev = dev = lin1[0].weight.device
@@ -870,10 +802,6 @@ class BatchedLinearTrainer:
         self.trainers = []
         for l, net in enumerate(nets):
             self.trainers.append(FusedLinearTrainer(net, lr, weight, lamb, seed=seed, grad_w1=self.gW1s[l], shared_buffers=_SharedViews(self, l)))
-        t0 = self.trainers[0]
-        if not (t0._early_gather and t0._early_split and t0._transposed_l1 and t0._dw2_inlaunch and t0._mid_fused and t0._dw3_partial
-                and t0._joint_inlaunch and t0._pipeline and not t0._nce_bwd_fused and not t0._overlap):
-            raise ValueError("BatchedLinearTrainer needs the default launch sequence (n_clusters <= 48, no opt-in variants)")
         self._programs = {}
         self._graphs = {}
         self._w1_in_launch = False
@@ -968,7 +896,7 @@ class BatchedLinearTrainer:
                     t._w1_planes_fresh = False
                     bf = t.buffers(m)
                     t._prepare_planes(bf, _planes_of(bf, t.F), 0)
-            per = self.trainers[0]._steps_per_graph
+            per = STEPS_PER_GRAPH
             while per > 2 and n_full < 2 + 2 * per:
                 per = max(2, per // 4 * 2)
             done = 0
@@ -996,7 +924,7 @@ class BatchedLinearTrainer:
         elif n_full:
             for t in self.trainers:
                 for i in range(n_full):
-                    t._full_step(store, t.buffers(m), pipelined=t._pipeline, xi=i % 2)
+                    t._full_step(store, t.buffers(m), pipelined=True, xi=i % 2)
         if rem:                                           # the partial last batch: voter by voter, the single-voter kernels
             for t in self.trainers:
                 t._full_step(store, t.buffers(2 * rem))

@@ -12,26 +12,16 @@ even number of steps (one stream, no forked branches); the steps that do not fil
 The parameters are the nn.Parameters of model.net (state_dict / predict / weights_init unchanged); RMSprop state lives here.
 """
 import ctypes
-import sys
 
 import torch
 
 from . import _lib
 from ._lib import lib as _L
+from .fused import TEMPERATURE, _launch, _p, _stream, launch_losses
 
-EPS = sys.float_info.epsilon
-TEMPERATURE = 0.85          # hard-coded at the reference call site, models.py:128
 H1, H2, LAT = 400, 128, 64  # myNet's widths (reference PytorchUtils.py:12-18)
 MAX_C = 256
 STEPS_PER_GRAPH = 16
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class _SmallBuffers:
@@ -136,25 +126,11 @@ class FusedSmallTrainer:
         chk(_L.idl_small_l1_fwd(_p(x), _p(W1), m, F, _p(bf.a1), _stream()))
         chk(_L.idl_small_mid_fwd(_p(bf.a1), _p(b1), _p(W2), _p(b2), _p(Wi), _p(bi), _p(Wc), _p(bc), m, C, tr, self.seed, _p(self.ctl),
                                  _p(bf.a2), _p(bf.d2), _p(bf.f), _p(bf.inv), _p(bf.z), _stream()))
-        # ---- the losses: the existing InfoNCE / IIC launches on f and z
-        dP0, dzs = bf.P0, None
-        if bf.nce_fused and C <= 48:         # the IIC joint and core ride in the two InfoNCE passes
-            chk(_L.idl_nce_fused_iic_z(_p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _p(bf.z), _p(bf.P0), C,
-                                       self.lamb, EPS, self.weight, _p(bf.iic_scratch), _p(self.out), _stream()))
-        elif bf.nce_fused and C <= 200:      # the joint in InfoNCE pass 1; the IIC core's rows, then z dP0 for every row
-            chk(_L.idl_nce_fused_joint(_p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _p(bf.z), _p(bf.P0), C,
-                                       _stream()))
-            chk(_L.idl_iic_core_dz(_p(bf.P0), C, self.lamb, EPS, self.weight, _p(bf.iic_scratch), _p(self.out), _p(bf.z), m, _p(bf.dzs), _stream()))
-            dP0, dzs = None, bf.dzs
-        else:
-            if bf.nce_fused:
-                chk(_L.idl_nce_fused(_p(bf.f), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _p(bf.G), _p(bf.nce_ws), _stream()))
-            else:                             # (m not a multiple of 32: a partial last batch)
-                torch.mm(bf.f, bf.f.t(), out=bf.S)
-                chk(_L.idl_nce_rows(_p(bf.S), m, TEMPERATURE, _p(bf.lse), _p(bf.loss_rows), _stream()))
-                torch.mm(bf.S, bf.f, out=bf.G[0])                               # (E + E^T) f
-            chk(_L.idl_iic_joint(_p(bf.z), m, C, _p(bf.P0), _stream()))
-            chk(_L.idl_iic_core(_p(bf.P0), C, self.lamb, EPS, self.weight, _p(bf.iic_scratch), _p(self.out), _stream()))
+        # ---- the losses: the existing InfoNCE / IIC launches on f and z (with the fused InfoNCE kernels, 48 < C <= 200: the IIC core's
+        # rows, then z dP0 for every row)
+        dz = bf.nce_fused and 48 < C <= 200
+        launch_losses(_launch, bf, self.lamb, self.weight, self.out, dz=dz)
+        dP0, dzs = (None, bf.dzs) if dz else (bf.P0, None)
         nce_coef = (1.0 - self.weight) / (m * TEMPERATURE)
         adv = m // 2 if next_from is not None else 0
         chk(_L.idl_small_mid_bwd(_p(bf.z), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(dP0), _p(dzs), _p(bf.a1), _p(bf.a2),

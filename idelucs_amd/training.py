@@ -81,10 +81,8 @@ def can_batch(model):
     """Voters can be batched when the model runs the default fused launch sequence (NetLinear + RMSprop, n_clusters <= 48, full
     batches a multiple of 16 rows) and no scheduler reads the epoch loss on the host between epochs."""
     # (the CLI hands the scheduler over as the reference does, as a string: "None" unless Plateau / Triangle was asked for)
-    from . import fused
     return bool(model._use_fused and model.n_clusters <= 48 and model.batch_sz % 16 == 0
-                and model.schedule not in ('Plateau', 'Triangle')
-                and fused.VARIANTS["pipeline"] != "0" and fused.VARIANTS["early_gather"] == "1" and fused.VARIANTS["mid_fused"] != "0")
+                and model.schedule not in ('Plateau', 'Triangle'))
 
 
 def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=True):
@@ -116,7 +114,7 @@ def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=Tr
             lane_models = [model.lane() for _ in wave]
             try:
                 batched = BatchedLinearTrainer([m.net for m in lane_models], model.lr, model.weight, model.l, seed=model.seed)
-            except ValueError:       # an opt-in launch variant (IDELUCS_DEV=overlap, IDELUCS_DEV=wgrad_fused, ...) the batched step does not take
+            except ValueError:       # a network the batched step does not take (n_clusters > 48)
                 for v in voters[w:]:
                     out[v] = train_voter(model, n_epochs, v, n_voters, progress)
                 return out

@@ -369,11 +369,6 @@ def test_default_fused_step_at_cfg2_shape_vs_autograd(dev, C):
     store, net = _cfg2_store_and_net(dev, 2000, C=C)
     ref_net = copy.deepcopy(net)
     tr = FusedLinearTrainer(net, lr=1e-3, weight=0.25, lamb=2.8, seed=5)
-    if C == 20:
-        assert tr._early_gather and tr._early_split and tr._transposed_l1 and tr._dw2_inlaunch and tr._mid_fused and tr._dw3_partial \
-            and tr._joint_inlaunch and not tr._nce_bwd_fused and tr._wgrad_fused and not tr._wgrad_own_launch, "not the default launch sequence"
-    else:
-        assert tr._early_fwd and not tr._early_gather and tr._dw2_inlaunch and tr._mid_fused and not tr._dw3_partial
     tr._keep_w1_grad = True                                     # the tiles also write dW1 out (the timed step never does)
     B = 512
     gen = torch.Generator(device=dev); gen.manual_seed(9)
@@ -381,6 +376,10 @@ def test_default_fused_step_at_cfg2_shape_vs_autograd(dev, C):
     tr.ctl[1] = 0; tr.out[1] = 0.0
     bf = tr.buffers(2 * B)
     assert bf.nce_fused
+    # the form the dispatch picks: C = 20 the two-plane step (IDELUCS_PLANES=0: the fp32 tiles with the tail in layer 1); C = 200 the
+    # two-plane step of n_clusters > 48 (IDELUCS_PLANES=0: the general form, whose sequence is the one listed above)
+    want_form = ("planes" if tr._planes else "tiles") if C == 20 else ("planes_rows" if tr._planes else "general")
+    assert tr._form(bf, store) == want_form, "not the default launch sequence"
     tr._gather(store, bf)                                       # prologue: batch 0 into bf.xs[0]
     x = bf.xs[0].clone()
     tr._full_step(store, bf, train=False, pipelined=True, xi=0)
@@ -919,11 +918,11 @@ def test_head_bwd_with_precomputed_product(dev):
     assert torch.allclose(res[0][0], res[1][0], rtol=1e-4, atol=1e-7) and torch.allclose(res[0][1], res[1][1], rtol=1e-4, atol=1e-7)
 
 
-def test_opt_in_step_variants_agree_with_the_default(dev):
-    """The opt-in / fallback ways of running the step (dW1 on hipBLASLt + a plain optimizer launch, the dW1 tiles as a launch of
-    their own, batch assembly in the optimizer launch,
-    row-major layer-1 activations, dW2 and the IIC joint as GEMM launches) train to the same parameters as the default launch
-    sequence -- same batches, same dropout streams; only the summation orders inside the products differ."""
+def test_general_step_form_agrees_with_the_default(dev):
+    """The general form of the step (library GEMMs + the unfused kernels, dW1 tiles and the optimizer as launches of their own, the
+    batch gathered in front of each step: what partial batches and the shapes the own tiles do not take run), stepped batch by batch
+    over the same permutation, trains to the same parameters as the default epoch (the tiles form at this shape) -- same batches,
+    same dropout streams; only the summation orders inside the products differ."""
     import copy
     import torch
     from idelucs_amd import utils as U, models
@@ -936,14 +935,22 @@ def test_opt_in_step_variants_agree_with_the_default(dev):
     store = U.FeatureStore(None, None, feats, mean, scale, 4, False)
     net0 = NetLinear(F, 6).to(dev); net0.apply(models.weights_init)
 
-    def run(**flags):
-        net = copy.deepcopy(net0)
-        tr = FusedLinearTrainer(net, lr=1e-3, weight=0.25, lamb=2.8, seed=11)
-        for k, v in flags.items():
-            assert hasattr(tr, k), k
-            setattr(tr, k, v)
+    def run(general=False):
+        tr = FusedLinearTrainer(copy.deepcopy(net0), lr=1e-3, weight=0.25, lamb=2.8, seed=11)
         gen = torch.Generator(device=dev); gen.manual_seed(77)
-        total, nb = tr.run_epoch(store, B, generator=gen)
+        if general:         # run_epoch's permutation, each full batch gathered and stepped on its own, then the partial one
+            tr._perm = torch.empty(store.n_pairs, dtype=torch.int64, device=dev)
+            torch.randperm(store.n_pairs, device=dev, generator=gen, out=tr._perm)
+            n_full, rem = divmod(store.n_pairs, B)
+            assert tr._form(tr.buffers(2 * B), None) == "general"
+            for _ in range(n_full):
+                tr._full_step(store, tr.buffers(2 * B), pipelined=False)
+            if rem:
+                tr._full_step(store, tr.buffers(2 * rem))
+            total = tr.out[1]
+        else:
+            assert tr._form(tr.buffers(2 * B), store) == "tiles"
+            total, nb = tr.run_epoch(store, B, generator=gen)
         torch.cuda.synchronize()
         return [p.detach().clone() for p in tr.params], total.item()
 
@@ -953,13 +960,10 @@ def test_opt_in_step_variants_agree_with_the_default(dev):
     # (measured: the own layer-1 tiles, whose head adds lat up in another order, against the default 3.5e-4; the joint as a GEMM
     # against the default 3.5e-4 in one run and 2.5e-7 in another; dW1 on hipBLASLt: bit-identical at this shape), max 5e-3.  A wrong kernel
     # moves the weights (scale 3e-2) by >= 1e-2.  Bar: mean <= 1e-3, max <= 1e-2, epoch loss within 2e-3.
-    variants = (dict(_wgrad_fused=False), dict(_wgrad_own_launch=True), dict(_early_gather=False), dict(_transposed_l1=False),
-                dict(_dw2_inlaunch=False, _early_gather=False), dict(_joint_inlaunch=False), dict(_pipeline=False, _early_gather=False))
-    for flags in variants:
-        p, l = run(**flags)
-        assert abs(l - ref_l) <= 2e-3 * abs(ref_l), (flags, l, ref_l)
-        for a, b in zip(p, ref_p):
-            assert (a - b).abs().max().item() <= 1e-2 and (a - b).abs().mean().item() <= 1e-3, flags
+    p, l = run(general=True)
+    assert abs(l - ref_l) <= 2e-3 * abs(ref_l), (l, ref_l)
+    for a, b in zip(p, ref_p):
+        assert (a - b).abs().max().item() <= 1e-2 and (a - b).abs().mean().item() <= 1e-3
     again, l2 = run()
     assert l2 == ref_l and all(torch.equal(a, b) for a, b in zip(again, ref_p)), "the default step is not deterministic"
 
@@ -1145,10 +1149,10 @@ def test_iic_joint_kernel_equals_the_product(m, C):
 def test_tail_riding_in_the_layer1_launch_changes_no_bit(dev, monkeypatch, n, use_graph):
     """Round 5: by default the layer-1 product runs on this package's own tiles and the optimizer's tail (dW2 tiles, RMSprop on the
     small tensors, step loss, step counter / batch offset) rides in the NEXT step's layer-1 launch (idl_l1_fwd_rms), a replayed
-    graph ending with its last step's tail as a launch of its own.  Against the same step with the tail where it was -- behind
-    the dW1 tiles of the optimizer launch -- and the same own layer-1 tiles (IDELUCS_TAIL_L1=0, IDELUCS_L1_FUSED=bare): every
-    product is formed by the same instructions in the same order, so a whole epoch (8 or 24 full batches + a partial one,
-    dropout on) leaves the SAME bits in every parameter, every running average, the loss sum and the counters."""
+    graph ending with its last step's tail as a launch of its own.  Against the same epoch stepped with defer_tail=False -- each
+    step's tail as a launch of its own right behind its dW1 tiles: every product is formed by the same instructions in the same
+    order, so a whole epoch (8 or 24 full batches + a partial one, dropout on) leaves the SAME bits in every parameter, every running
+    average, the loss sum and the counters."""
     import copy
     import torch
     from idelucs_amd.fused import FusedLinearTrainer
@@ -1156,15 +1160,30 @@ def test_tail_riding_in_the_layer1_launch_changes_no_bit(dev, monkeypatch, n, us
     B = 512
     out = []
     monkeypatch.setenv("IDELUCS_PLANES", "0")       # (the fp32 form of the step: the two-plane form has its own tests, test_gpu_planes.py)
-    for tail, bare in (("1", "0"), ("0", "bare")):
-        monkeypatch.setitem(__import__("idelucs_amd.fused", fromlist=["VARIANTS"]).VARIANTS, "tail_l1", tail)
-        monkeypatch.setitem(__import__("idelucs_amd.fused", fromlist=["VARIANTS"]).VARIANTS, "l1_fused", bare)
+
+    def epoch_tail_after_each_step(tr, gen):
+        """run_epoch's steps, eager, none of them leaving its tail pending."""
+        if tr._perm is None:
+            tr._perm = torch.empty(store.n_pairs, dtype=torch.int64, device=dev)
+        torch.randperm(store.n_pairs, device=dev, generator=gen, out=tr._perm)
+        tr.ctl[1:2].zero_()
+        tr.out[1:2].zero_()
+        n_full, rem = divmod(store.n_pairs, B)
+        bf = tr.buffers(2 * B)
+        tr._gather(store, bf)
+        for i in range(n_full):
+            tr._full_step(store, bf, pipelined=True, xi=i % 2, defer_tail=False)
+        if rem:
+            tr._full_step(store, tr.buffers(2 * rem))
+        return tr.out[1]
+
+    for riding in (True, False):
         net = copy.deepcopy(net0)
         tr = FusedLinearTrainer(net, lr=1e-3, weight=0.25, lamb=2.8, seed=5)
-        assert tr._tail_l1 == (tail == "1") and tr._l1_bare == (bare == "bare")
+        assert tr._form(tr.buffers(2 * B), store) == "tiles"
         gen = torch.Generator(device=dev); gen.manual_seed(123)
-        total, nb = tr.run_epoch(store, B, use_graph=use_graph, generator=gen)
-        total2, _ = tr.run_epoch(store, B, use_graph=use_graph, generator=gen)          # a second epoch: the graph replayed from its start
+        for _ in range(2):          # a second epoch: the graph replayed from its start
+            total2 = tr.run_epoch(store, B, use_graph=use_graph, generator=gen)[0] if riding else epoch_tail_after_each_step(tr, gen)
         torch.cuda.synchronize()
         assert tr._pending is None
         out.append(([p.detach().clone() for p in tr.params], [v.clone() for v in tr.square_avg], total2.item(), tr.ctl.tolist(), tr.out.tolist()))
@@ -1173,7 +1192,6 @@ def test_tail_riding_in_the_layer1_launch_changes_no_bit(dev, monkeypatch, n, us
     for a, b in zip(pa + va, pb + vb):
         assert torch.equal(a, b)
     # a step taken alone (tests, callers outside run_epoch) is complete when it returns: nothing stays pending
-    monkeypatch.setitem(__import__("idelucs_amd.fused", fromlist=["VARIANTS"]).VARIANTS, "tail_l1", "1"); monkeypatch.setitem(__import__("idelucs_amd.fused", fromlist=["VARIANTS"]).VARIANTS, "l1_fused", "0")
     tr = FusedLinearTrainer(copy.deepcopy(net0), lr=1e-3, weight=0.25, lamb=2.8, seed=5)
     tr._perm = torch.randperm(store.n_pairs, device=dev)
     bf = tr.buffers(2 * B)
