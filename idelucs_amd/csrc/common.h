@@ -27,17 +27,19 @@ int device_info(DeviceInfo *out);
 constexpr int PLAN_BYTES = 1024;       // one record: PlanHead + the kernel's parameter struct at PLAN_PARAMS
 constexpr int PLAN_PARAMS = 64;
 enum { PLAN_MID_FWD = 1, PLAN_NCE = 2, PLAN_MID_BWD = 3, PLAN_RMSPROP = 4, PLAN_WGRAD_RMSPROP = 5, PLAN_L1_FWD = 6,
-       PLAN_L1_PLANES = 7, PLAN_REDUCE = 8, PLAN_WGRAD_XPLANES = 9 };      // (7-9: the launches of the step's two-plane form)
+       PLAN_L1_PLANES = 7, PLAN_REDUCE = 8, PLAN_WGRAD_XPLANES = 9,        // (7-9: the launches of the step's two-plane form)
+       PLAN_IIC_CORE_DZ = 10, PLAN_AT_B = 11 };                            // (10-11: the step of 48 < n_clusters <= 200)
 struct PlanHead {
-    int32_t kind, variant;
-    uint32_t grid[3], block, lds;      // of one voter's launch
-    uint32_t grid2[3];                 // second launch of the record (InfoNCE pass 2)
+    int32_t kind, variant;             // variant: PLAN_MID_FWD 1 = transposed activations; PLAN_MID_BWD 1 = the n_clusters > 48 body
+    uint32_t grid[3], block, lds;      // of one voter's launch (lds: dynamic LDS bytes)
+    uint32_t grid2[3];                 // second launch of the record (InfoNCE pass 2, idl_iic_core_dz's z dP0 tiles)
 };
 static_assert(sizeof(PlanHead) <= PLAN_PARAMS, "plan header does not fit");
 // the record the next supporting launcher on this thread fills instead of launching (and clears); NULL = launch normally
 void *take_plan();
 // the batched launches of the other translation units
 int nce_plan_launch(const PlanHead &h, const void *dev_plans, int n_voters, hipStream_t stream);
+int at_b_plan_launch(const PlanHead &h, const void *dev_plans, int n_voters, hipStream_t stream);
 
 }  // namespace idl
 

@@ -306,36 +306,20 @@ __global__ __launch_bounds__(256) void iic_joint_kernel(const float *__restrict_
 __global__ __launch_bounds__(256) void at_b_kernel(const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb, int K, int M, int N,
                                                    float *__restrict__ out, int ldo)
 {
-    __shared__ float part[3][64][4];
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, l = lane & 15, q = lane >> 4;
-    const int c1 = blockIdx.x * 16, c2 = blockIdx.y * 16;
-    const bool ok1 = c1 + l < M, ok2 = c2 + l < N;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    for (int kb = 128 * wv; kb < K; kb += 512) {             // the contraction index is dealt to the four waves in blocks of 128 (32 MFMA steps, every load in flight first)
-        const float *pa = A + (ok1 ? c1 + l : 0), *pb = B + (ok2 ? c2 + l : 0);
-        float av[32], bv[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {                       // (clamped, not predicated)
-            const int k = kb + 4 * u + q, kk = k < K ? k : K - 1;
-            av[u] = pa[(size_t)kk * lda]; bv[u] = pb[(size_t)kk * ldb];
-        }
-#pragma unroll
-        for (int u = 0; u < 32; u += 2) {
-            const bool in0 = kb + 4 * u + q < K, in1 = kb + 4 * (u + 1) + q < K;
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32((ok1 && in0) ? av[u] : 0.f, (ok2 && in0) ? bv[u] : 0.f, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32((ok1 && in1) ? av[u + 1] : 0.f, (ok2 && in1) ? bv[u + 1] : 0.f, acc1, 0, 0, 0);
-        }
-    }
-    f32x4 acc = acc0 + acc1;
-    if (wv > 0) { part[wv - 1][lane][0] = acc[0]; part[wv - 1][lane][1] = acc[1]; part[wv - 1][lane][2] = acc[2]; part[wv - 1][lane][3] = acc[3]; }
-    __syncthreads();
-    if (wv == 0 && ok2) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int r = c1 + 4 * q + reg;
-            if (r < M) out[(size_t)r * ldo + c2 + l] = ((acc[reg] + part[0][lane][reg]) + part[1][lane][reg]) + part[2][lane][reg];
-        }
-    }
+#include "at_b_tile.inc"
+}
+
+// several voters in one launch: the tile grid of one product, voter blockIdx.z takes its operands from its plan record
+struct AtBParams { const float *A; int lda; const float *B; int ldb, K, M, N; float *out; int ldo; };
+static_assert(sizeof(AtBParams) + idl::PLAN_PARAMS <= idl::PLAN_BYTES, "AtBParams does not fit a plan record");
+
+__global__ __launch_bounds__(256) void at_b_batched_kernel(const unsigned char *__restrict__ plans)
+{
+    const AtBParams &p = *(const AtBParams *)(plans + (size_t)blockIdx.z * idl::PLAN_BYTES + idl::PLAN_PARAMS);
+    const float *__restrict__ const A = p.A, *__restrict__ const B = p.B;
+    float *__restrict__ const out = p.out;
+    const int lda = p.lda, ldb = p.ldb, K = p.K, M = p.M, N = p.N, ldo = p.ldo;
+#include "at_b_tile.inc"
 }
 
 }  // namespace
@@ -347,7 +331,16 @@ extern "C" {
 int idl_at_b(const float *A, int lda, const float *B, int ldb, int K, int M, int N, float *out, int ldo, void *stream)
 {
     IDL_REQUIRE(A && B && out && K >= 1 && M >= 1 && N >= 1 && lda >= M && ldb >= N && ldo >= N && M <= 65535 * 16 && N <= 65535 * 16, "at_b: NULL buffer or bad shape");
-    hipLaunchKernelGGL(at_b_kernel, dim3((unsigned)((M + 15) / 16), (unsigned)((N + 15) / 16)), dim3(256), 0, (hipStream_t)stream, A, lda, B, ldb, K, M, N, out, ldo);
+    const dim3 grid((unsigned)((M + 15) / 16), (unsigned)((N + 15) / 16));
+    if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin)
+        idl::PlanHead h{};
+        h.kind = idl::PLAN_AT_B; h.grid[0] = grid.x; h.grid[1] = grid.y; h.grid[2] = 1; h.block = 256;
+        memcpy(plan, &h, sizeof(h));
+        const AtBParams p{A, lda, B, ldb, K, M, N, out, ldo};
+        memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
+        return IDL_OK;
+    }
+    hipLaunchKernelGGL(at_b_kernel, grid, dim3(256), 0, (hipStream_t)stream, A, lda, B, ldb, K, M, N, out, ldo);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }
@@ -381,8 +374,7 @@ static int nce_launch(const float *f, int m, float temperature, float *lse, floa
     const dim3 grid1((unsigned)(m / 16 + (iic.P0 != nullptr ? (iic.cols > 0 ? iic.cols : 1) : 0)), NCE_SPLIT);
     const bool core2 = iic.z != nullptr && iic.cols == 0;    // the core as the spare workgroup of pass 2 (n_clusters <= 48)
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin): both passes in one record
-        IDL_REQUIRE(iic.cols == 0, "nce_fused: the joint of n_clusters > 48 cannot be recorded");
-        const dim3 g2 = iic.z != nullptr ? grid1 : grid;
+        const dim3 g2 = core2 ? grid1 : grid;     // (n_clusters > 48: the joint's tiles ride in pass 1 alone, the core is idl_iic_core_dz's record)
         idl::PlanHead h{};
         h.kind = idl::PLAN_NCE; h.grid[0] = grid1.x; h.grid[1] = grid1.y; h.grid[2] = 1; h.block = 256;
         h.grid2[0] = g2.x; h.grid2[1] = g2.y; h.grid2[2] = 1;
@@ -443,6 +435,13 @@ int idl::nce_plan_launch(const idl::PlanHead &h, const void *dev_plans, int n_vo
     const unsigned char *dp = (const unsigned char *)dev_plans;
     hipLaunchKernelGGL(nce_pass1_batched_kernel, dim3(h.grid[0], h.grid[1], (unsigned)n_voters), dim3(h.block), 0, stream, dp);
     hipLaunchKernelGGL(nce_pass2_batched_kernel, dim3(h.grid2[0], h.grid2[1], (unsigned)n_voters), dim3(h.block), 0, stream, dp);
+    IDL_HIP_TRY(hipGetLastError());
+    return IDL_OK;
+}
+
+int idl::at_b_plan_launch(const idl::PlanHead &h, const void *dev_plans, int n_voters, hipStream_t stream)
+{
+    hipLaunchKernelGGL(at_b_batched_kernel, dim3(h.grid[0], h.grid[1], (unsigned)n_voters), dim3(h.block), 0, stream, (const unsigned char *)dev_plans);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }

@@ -391,10 +391,15 @@ __global__ __launch_bounds__(256) void nce_esym_kernel(float *S, int m, float in
 }
 
 // ---------------------------------------------------------------- IIC on the C x C joint (one workgroup): iic_device.h
-__global__ __launch_bounds__(1024) void iic_core_rows_kernel(const float *P0, int C, float lamb, float eps, float *grad, double *part)
+__device__ __forceinline__ void iic_core_rows_body(const float *P0, int C, float lamb, float eps, float *grad, double *part)
 {
     extern __shared__ float iic_L[];
     iic_core_rows_multi(P0, C, lamb, eps, grad, part, iic_L);
+}
+
+__global__ __launch_bounds__(1024) void iic_core_rows_kernel(const float *P0, int C, float lamb, float eps, float *grad, double *part)
+{
+    iic_core_rows_body(P0, C, lamb, eps, grad, part);
 }
 
 __global__ __launch_bounds__(256) void iic_core_shift_kernel(float *P0, int C, float w_iic, float *out, const float *grad, const double *part, int n_part)
@@ -406,8 +411,8 @@ __global__ __launch_bounds__(256) void iic_core_shift_kernel(float *P0, int C, f
 // the rows launch's unshifted gradient g moved by the global sum gp -- for a softmax row (its entries add up to 1)
 // so the shift launch and the library GEMM behind it (5.1 + 5.0 us at 200 classes) are ONE launch of 16 x 16 MFMA tiles that takes g - gp as its B operand
 // (rounded exactly as the shift launch rounds it; C <= 256: 64 K-steps).  LossFunctions.py:20-62.
-__global__ __launch_bounds__(256) void iic_dz_kernel(const float *__restrict__ z, int m, int C, const float *__restrict__ grad, const double *__restrict__ part,
-                                                     int n_part, float w_iic, float *__restrict__ dzs, float *__restrict__ out)
+__device__ __forceinline__ void iic_dz_body(const float *__restrict__ z, int m, int C, const float *__restrict__ grad, const double *__restrict__ part,
+                                            int n_part, float w_iic, float *__restrict__ dzs, float *__restrict__ out)
 {
     // a workgroup: 16 rows of z (staged in LDS by coalesced loads, once) x 4 column tiles, a wave each; every B operand of a tile (a column of g: 64-byte
     // segments) requested before the first product.  g enters as g - gp, rounded as iic_core_shift rounds it.
@@ -453,6 +458,29 @@ __global__ __launch_bounds__(256) void iic_dz_kernel(const float *__restrict__ z
         const int r = r0 + 4 * q + reg;
         if (r < m && okc) dzs[(int64_t)r * C + c0 + l] = sc * (acc0[reg] + acc1[reg]);
     }
+}
+
+__global__ __launch_bounds__(256) void iic_dz_kernel(const float *__restrict__ z, int m, int C, const float *__restrict__ grad, const double *__restrict__ part,
+                                                     int n_part, float w_iic, float *__restrict__ dzs, float *__restrict__ out)
+{
+    iic_dz_body(z, m, C, grad, part, n_part, w_iic, dzs, out);
+}
+
+// several voters in one launch (idl_iic_core_dz recorded: ONE record for its two launches): both kernels keep one voter's grid in blockIdx.x -- the rows
+// launch reads its number of workgroups from gridDim.x -- and take the voter from blockIdx.y
+struct IicDzParams { const float *P0; int C; float lamb, eps, w_iic; float *grad; double *part; int n_part; const float *z; int m; float *dzs, *out; };
+static_assert(sizeof(IicDzParams) + idl::PLAN_PARAMS <= idl::PLAN_BYTES, "IicDzParams does not fit a plan record");
+
+__global__ __launch_bounds__(1024) void iic_core_rows_batched_kernel(const unsigned char *__restrict__ plans)
+{
+    const IicDzParams &p = *(const IicDzParams *)(plans + (size_t)blockIdx.y * idl::PLAN_BYTES + idl::PLAN_PARAMS);
+    iic_core_rows_body(p.P0, p.C, p.lamb, p.eps, p.grad, p.part);
+}
+
+__global__ __launch_bounds__(256) void iic_dz_batched_kernel(const unsigned char *__restrict__ plans)
+{
+    const IicDzParams &p = *(const IicDzParams *)(plans + (size_t)blockIdx.y * idl::PLAN_BYTES + idl::PLAN_PARAMS);
+    iic_dz_body(p.z, p.m, p.C, p.grad, p.part, p.n_part, p.w_iic, p.dzs, p.out);
 }
 
 template <int NT>
@@ -914,6 +942,14 @@ __global__ __launch_bounds__(64 * MID_WAVES) void mid_bwd_batched_kernel(const u
     const MidBwdParams &p = *(const MidBwdParams *)(plans + (size_t)blockIdx.x * idl::PLAN_BYTES + idl::PLAN_PARAMS);
     if (p.a.dr1h != nullptr) mid_bwd_body<false, true>(p.a, p.tile0, p.tile1, p.gth, (int)blockIdx.y);
     else mid_bwd_body<false, false>(p.a, p.tile0, p.tile1, p.gth, (int)blockIdx.y);
+}
+
+// ... and the n_clusters > 48 body with dr1 as planes (the step of the fine-grained mode in lockstep): a kernel of its own, so that the small form above
+// keeps its registers, has no scratch and no dynamic LDS; W3 in dynamic LDS as in mid_bwd_kernel<true, true>
+__global__ __launch_bounds__(64 * MID_WAVES) void mid_bwd_big_batched_kernel(const unsigned char *__restrict__ plans)
+{
+    const MidBwdParams &p = *(const MidBwdParams *)(plans + (size_t)blockIdx.x * idl::PLAN_BYTES + idl::PLAN_PARAMS);
+    mid_bwd_body<true, true>(p.a, p.tile0, p.tile1, p.gth, (int)blockIdx.y);
 }
 
 // ---------------------------------------------------------------- RMSprop over all parameter tensors
@@ -1507,8 +1543,17 @@ int idl_iic_core_dz(const float *P0, int C, float lamb, float eps, float w_iic, 
     }
     const int G = (C + IIC_RPW - 1) / IIC_RPW;
     double *part = (double *)(scratch + ((C * C + 3) & ~3));
-    hipLaunchKernelGGL(iic_core_rows_kernel, dim3(G), dim3(1024), lds, (hipStream_t)stream, P0, C, lamb, eps, scratch, part);
     const int groups = ((C + 15) / 16 + 3) / 4;              // (a workgroup: 16 rows x 4 column tiles)
+    if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin): both launches in one record
+        idl::PlanHead h{};
+        h.kind = idl::PLAN_IIC_CORE_DZ; h.grid[0] = (unsigned)G; h.grid[1] = 1; h.grid[2] = 1; h.block = 1024; h.lds = (unsigned)lds;
+        h.grid2[0] = (unsigned)(((m + 15) / 16) * groups); h.grid2[1] = 1; h.grid2[2] = 1;
+        memcpy(plan, &h, sizeof(h));
+        const IicDzParams p{P0, C, lamb, eps, w_iic, scratch, part, G, z, m, dzs, out};
+        memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
+        return IDL_OK;
+    }
+    hipLaunchKernelGGL(iic_core_rows_kernel, dim3(G), dim3(1024), lds, (hipStream_t)stream, P0, C, lamb, eps, scratch, part);
     hipLaunchKernelGGL(iic_dz_kernel, dim3((unsigned)(((m + 15) / 16) * groups)), dim3(256), 0, (hipStream_t)stream, z, m, C, (const float *)scratch, (const double *)part, G, w_iic,
                        dzs, out);
     IDL_HIP_TRY(hipGetLastError());
@@ -1595,8 +1640,10 @@ static int mid_bwd_gather_impl(const float *z, const float *r2, const float *f, 
         t0 = ng * part / parts; t1 = ng * part_end / parts;
     }
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin)
-        IDL_REQUIRE(C <= 48, "mid_bwd_gather: only the n_clusters <= 48 form can be recorded");
+        IDL_REQUIRE(C <= 48 || (dr1h != nullptr && dzs != nullptr),
+                    "mid_bwd_gather: beyond 48 classes only the form with dr1 as planes and z dP0 given can be recorded");
         idl::PlanHead h{};
+        if (C > 48) { h.variant = 1; h.lds = (unsigned)(C * H2 * (int)sizeof(float)); }      // (the BIG body: W3 in dynamic LDS)
         h.kind = idl::PLAN_MID_BWD; h.grid[0] = (unsigned)(COL_PARTS + (t1 - t0 + 3) / 4); h.grid[1] = 1; h.grid[2] = 1; h.block = 64 * MID_WAVES;
         memcpy(plan, &h, sizeof(h));
         const MidBwdParams p{a, (int)t0, (int)t1, g};
@@ -2032,8 +2079,34 @@ int idl_plan_launch(const void *host_plans, const void *dev_plans, int n_voters,
         else hipLaunchKernelGGL(mid_fwd_batched_kernel<false>, dim3((unsigned)n_voters, h.grid[0]), dim3(h.block), 0, st, dp);
         break;
     case idl::PLAN_MID_BWD:
-        hipLaunchKernelGGL(mid_bwd_batched_kernel, dim3((unsigned)n_voters, h.grid[0]), dim3(h.block), 0, st, dp);
+        if (h.variant) {                         // n_clusters > 48: W3 in dynamic LDS beside the static arrays, the limit raised once per device
+            static bool attr_set[64] = {};
+            int dev = 0;
+            IDL_HIP_TRY(hipGetDevice(&dev));
+            IDL_REQUIRE(h.lds >= 49u * H2 * sizeof(float) && h.lds <= 64u * MAX_CPL * H2 * sizeof(float), "plan_launch: not the record of a middle backward beyond 48 classes");
+            if (dev >= 0 && dev < 64 && !attr_set[dev]) {
+                IDL_HIP_TRY(hipFuncSetAttribute((const void *)mid_bwd_big_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * MAX_CPL * H2 * (int)sizeof(float)));
+                attr_set[dev] = true;
+            }
+            hipLaunchKernelGGL(mid_bwd_big_batched_kernel, dim3((unsigned)n_voters, h.grid[0]), dim3(h.block), h.lds, st, dp);
+        }
+        else hipLaunchKernelGGL(mid_bwd_batched_kernel, dim3((unsigned)n_voters, h.grid[0]), dim3(h.block), 0, st, dp);
         break;
+    case idl::PLAN_IIC_CORE_DZ: {                // the rows launch (every workgroup keeps the joint in dynamic LDS), then the z dP0 tiles
+        static bool attr_set[64] = {};
+        int dev = 0;
+        IDL_HIP_TRY(hipGetDevice(&dev));
+        IDL_REQUIRE(h.lds <= 200u * 201u * 4u && h.block == 1024u, "plan_launch: not the record of idl_iic_core_dz");
+        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
+            IDL_HIP_TRY(hipFuncSetAttribute((const void *)iic_core_rows_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 200 * 201 * 4));
+            attr_set[dev] = true;
+        }
+        hipLaunchKernelGGL(iic_core_rows_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), h.lds, st, dp);
+        hipLaunchKernelGGL(iic_dz_batched_kernel, dim3(h.grid2[0], (unsigned)n_voters), dim3(256), 0, st, dp);
+        break;
+    }
+    case idl::PLAN_AT_B:
+        return idl::at_b_plan_launch(h, dev_plans, n_voters, st);
     case idl::PLAN_RMSPROP:
         hipLaunchKernelGGL(rmsprop_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), 0, st, dp);
         break;

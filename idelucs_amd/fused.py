@@ -9,6 +9,7 @@ One step of reference idelucs/models.py:117-133 takes one of five launch sequenc
     tiles        IDELUCS_PLANES=0 (or shapes the planes do not take): own fp32 tiles, idl_l1_fwd -> idl_mid_fwd_gather -> InfoNCE + IIC ->
                  idl_mid_bwd_gather -> idl_wgrad_rmsprop; the optimizer's tail rides in the NEXT step's layer-1 launch (idl_l1_fwd_rms)
     record_planes the planes sequence recorded for BatchedLinearTrainer
+    record_planes_rows  the planes_rows sequence (48 < n_clusters <= 200) recorded for BatchedLinearTrainer
     general      everything else on library GEMMs + the unfused kernels: a lockstep step on batched fp32 GEMMs, n_clusters > 48 in fp32,
                  partial batches and the shapes the own tiles do not take
 (DESIGN.md 4.4 has the table of what each launch carries).  Batches are assembled from the HBM feature store at a device-resident
@@ -20,7 +21,8 @@ RMSprop state lives here; begin_voter() clears it (every voter is an independent
 
 BatchedLinearTrainer steps several voters of one ensemble in lockstep: the layer-1 product becomes a batched GEMM and each of
 the other kernels ONE launch with the voter index in its grid (recorded launches, idl_plan_*; in the two-plane form all six
-launches), so the latency-bound launches are paid once per step of the whole batch of voters instead of once per voter.
+launches, at 48 < n_clusters <= 200 all eight), so the latency-bound launches are paid once per step of the whole batch of voters
+instead of once per voter.
 """
 import ctypes
 import os
@@ -75,6 +77,19 @@ def disable_planes():
 
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def rows_shape_applies(m, H1, F, cus):
+    """Whether a batch shape takes the two-plane step of n_clusters > 48 (FusedLinearTrainer._step_planes_rows and its recorded form): the layer-1
+    tiles with the operands' roles swapped, dW1 from the batch's planes, a dW1 tile per CU with one for each block of the tail on its loader waves."""
+    return bool(_L.idl_l1_planes_supported(H1, m, F)) and bool(_L.idl_wgrad_xplanes_supported(m, H1, F)) and 144 <= (H1 // 64) * (F // 128) <= cus
+
+
+def rows_lockstep_applies(m, H1, F, C, n_rows, cus):
+    """Whether the voters of a NetLinear(F, C) trained on full batches of m rows can run in lockstep at 48 < C <= 200 (the form 'record_planes_rows' of
+    a trainer built now): decided from the shape and the process's settings alone, before any trainer exists (training.can_batch)."""
+    return (48 < C <= 200 and planes_default() and _v("lockstep_planes") != "0" and _v("planes_wgrad") != "0" and _v("planes_tail") != "reduce"
+            and m % 16 == 0 and F % 4 == 0 and n_rows < PLANES_MAX_ROWS and _L.idl_nce_fused_workspace(m) > 0 and rows_shape_applies(m, H1, F, cus))
 
 
 def _launch(fn, *args):
@@ -234,7 +249,8 @@ class FusedLinearTrainer:
         # ... and the same for a rank's voters in lockstep (BatchedLinearTrainer; IDELUCS_DEV=lockstep_planes=0: their products as batched fp32
         # library GEMMs instead): the six launches of the two-plane step recorded per voter and run once for all of them, blockIdx.y = voter
         # -- the lone voters' steps bit for bit (tests/test_gpu_planes.py), 47.5 / 45.4 / 43.6 ms a voter-epoch in batches of 2 / 4 / 8
-        # against 54.2 alone (fp32 GEMMs: 58.9 / 54.8 / 52.6)
+        # against 54.2 alone (fp32 GEMMs: 58.9 / 54.8 / 52.6); at 48 < n_clusters <= 200 the eight launches of _step_planes_rows the same way
+        # (_record_planes_rows_step: 58.1 / 53.9 / 51.4 ms at 200 output units against 74.6 alone, tools/bench_lockstep_rows.py)
         self._planes_lockstep = _v("lockstep_planes") != "0"
         # ... and dW1 from the batch's planes too (csrc/wgrad_planes.hip); the assembling workgroups then write the planes ONLY
         self._planes_wgrad = _v("planes_wgrad") != "0"
@@ -304,8 +320,8 @@ class FusedLinearTrainer:
 
     # ------------------------------------------------------------------ one step on a filled bf.x
     def _form(self, bf, st):
-        """The launch sequence of a step on bf with next_from = st (module docstring): 'record_planes', 'planes', 'planes_rows', 'tiles'
-        or 'general'."""
+        """The launch sequence of a step on bf with next_from = st (module docstring): 'record_planes', 'record_planes_rows', 'planes',
+        'planes_rows', 'tiles' or 'general'."""
         m, H1, F = bf.m, self.H1, self.F
         if st is None or m % 16 != 0 or F % 4 != 0:      # only a pipelined step's middle launches assemble the next batch
             return "general"
@@ -316,6 +332,9 @@ class FusedLinearTrainer:
             if (self.C <= 48 and planes and self._planes_lockstep and bf.nce_fused and bool(_L.idl_l1_planes_supported(m, H1, F)) and xplanes
                     and wide):
                 return "record_planes"
+            if (48 < self.C <= 200 and planes and self._planes_lockstep and self._planes_wgrad and self._planes_tail_wgrad and bf.nce_fused
+                    and rows_shape_applies(m, H1, F, self._cus)):
+                return "record_planes_rows"
             return "general"
         if self._shared_buffers:
             return "general"
@@ -323,7 +342,7 @@ class FusedLinearTrainer:
             if not (_L.idl_l1_fwd_supported(m, H1, F) and _L.idl_wgrad_supported(m, H1, F)):
                 return "general"
             return "planes" if planes and bool(_L.idl_l1_planes_supported(m, H1, F)) else "tiles"
-        if (planes and self._planes_wgrad and self._planes_tail_wgrad and bool(_L.idl_l1_planes_supported(H1, m, F)) and xplanes and wide):
+        if planes and self._planes_wgrad and self._planes_tail_wgrad and rows_shape_applies(m, H1, F, self._cus):
             return "planes_rows"
         return "general"
 
@@ -337,6 +356,8 @@ class FusedLinearTrainer:
         form = self._form(bf, st)
         if form == "record_planes":
             return self._record_planes_step(bf, tr, st, xi)
+        if form == "record_planes_rows":
+            return self._record_planes_rows_step(bf, tr, st, xi)
         if form not in ("planes", "tiles"):
             self.flush_tail()                   # (a step of another form: whatever is pending goes first)
         if form == "planes":
@@ -604,6 +625,29 @@ class FusedLinearTrainer:
         self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, None, _p(self.W1),
                 _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *self._tail(bf), 0, *self._wg(bf, r1, 1, m // 2))
 
+    def _record_planes_rows_step(self, bf, tr, st, xi):
+        """The two-plane step of 48 < n_clusters <= 200 (_step_planes_rows: layer-1 tiles with the roles swapped, the sum of their partials, mid_fwd,
+        InfoNCE with the joint's tiles, the IIC core with z dP0, mid_bwd, dW3, the dW1 tiles with the tail on their loader waves) as eight RECORDED
+        launches, ten kernels: BatchedLinearTrainer runs each once for all the voters of a rank.  Nothing is launched here but what allocates this
+        voter's plane buffers."""
+        m, C, H1, F = bf.m, self.C, self.H1, self.F
+        pb = _planes_of(bf, F)
+        wh, wl, flag = self._w1_planes_of()
+        part = pb["part"][xi]
+        r1 = part.view(-1, m, H1)[0]            # [m, H1]: slab 0 of part[8][m][512]
+        nxt = (None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
+        self._k(_L.idl_l1_planes, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, _p(wh), _p(wl), F, H1, m, F, _p(part), _stream())
+        self._k(_L.idl_reduce_parts_rms, _p(part), H1 * m, _p(self.ctl), _p(self._ctl_snap), 0, None, None, None, None, None, None, None, None, 0, 0.0, 0.0,
+                None, 0, -1, None, None, 0, 0, 0, 0, None, 0, _stream())
+        self._k(_L.idl_mid_fwd_gather_planes, _p(r1), _p(self.b1), 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
+                0, GATHER_SPLIT, 8, _stream())
+        launch_losses(self._k, bf, self.lamb, self.weight, self.out, dz=True)
+        self._k(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, None), *self._next_batch(st, m), *nxt, GATHER_SPLIT, 8, 8, 0,
+                *self._dr1_planes_args(pb, True, bf.dzs), _stream())
+        self._k(_L.idl_at_b, _p(bf.dlogits), C, _p(bf.r2), self.H2, m, C, self.H2, _p(self.grads[4]), self.H2, _stream())      # dW3 = dlogits^T r2
+        self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, None, _p(self.W1),
+                _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *self._tail(bf), 0, *self._wg(bf, r1, 0, m // 2))
+
     def _dr1_planes_args(self, pb, on, dzs=None):
         """idl_mid_bwd_gather_planes' last arguments: dr1's planes and the words of their scale (or none of them: dr1 in fp32), and z dP0 as an
         input (the step of n_clusters > 48)."""
@@ -780,12 +824,14 @@ class BatchedLinearTrainer:
     The step of voter l is the launch sequence of FusedLinearTrainer.step_on_batch; here each of its launches is issued ONCE for
     all voters: the two big products as batched GEMMs over stacked operands ([L, 512, F] weights, [L, m, F] batches), the five
     kernels as recorded launches (idl_plan_*: every voter's launch is recorded through the ordinary launcher, the records
-    live on the device, the kernels take the voter index from blockIdx.y / .z).  Needs n_clusters <= 48 (the middle launches
-    assemble the next batch)."""
+    live on the device, the kernels take the voter index from blockIdx.x / .y / .z); in the two-plane forms every launch of the
+    step is a recorded one (six at n_clusters <= 48, eight at 48 < n_clusters <= 200) and the voters' steps are the lone voters'
+    bit for bit.  n_clusters <= 48 takes either form; 48 < n_clusters <= 200 has the two-plane form only (rows_lockstep_applies:
+    training.can_batch asks before it builds one), and beyond 200 output units voters train one after the other."""
 
     def __init__(self, nets, lr, weight, lamb, seed=0):
-        if nets[0].classifier[2].out_features > 48:
-            raise ValueError("BatchedLinearTrainer needs n_clusters <= 48")
+        if nets[0].classifier[2].out_features > 200:
+            raise ValueError("BatchedLinearTrainer needs n_clusters <= 200 (beyond 48: on the two-plane step form, fused.rows_lockstep_applies)")
         self.L = L = len(nets)
         lin1 = [n.layers[0] for n in nets]
         self.dev = dev = lin1[0].weight.device
@@ -806,6 +852,11 @@ class BatchedLinearTrainer:
         self._graphs = {}
         self._w1_in_launch = False
         self._planes_step = False
+
+    def planes_overflowed(self):
+        """Whether any voter's operands left the planes' range (FusedLinearTrainer.planes_overflowed): every lane's flag in ONE read (waits for the device)."""
+        flags = [t._w1_planes[2] for t in self.trainers if t._w1_planes is not None]
+        return bool(flags) and bool(torch.cat(flags).any().item())
 
     def drop_planes(self):
         """After the voters' trainers left the two-plane form (FusedLinearTrainer.drop_planes): the recorded programs and captured graphs hold its launches."""
@@ -838,11 +889,11 @@ class BatchedLinearTrainer:
                         t.step_on_batch(t.buffers(m), train=True, batch_advance=m // 2, next_from=store, xi=xi)
                     finally:
                         rec, t._rec = t._rec, None
-                    # the two-plane step: six recorded launches, no library GEMM; the fp32 form: 4 kernel launches + the two big products as batched
-                    # GEMMs (dW1 on own tiles at the head of the optimizer launch is a recorded launch instead: one GEMM)
-                    if (len(rec.plans), rec.mms) not in ((4, 2), (4, 1), (6, 0)):
+                    # the two-plane step: six recorded launches (eight at 48 < n_clusters <= 200), no library GEMM; the fp32 form: 4 kernel launches +
+                    # the two big products as batched GEMMs (dW1 on own tiles at the head of the optimizer launch is a recorded launch instead: one GEMM)
+                    if (len(rec.plans), rec.mms) not in ((4, 2), (4, 1), (6, 0), (8, 0)):
                         raise RuntimeError("the recorded step is not the default launch sequence")
-                    self._planes_step = len(rec.plans) == 6
+                    self._planes_step = rec.mms == 0
                     self._w1_in_launch = rec.mms == 1
                     recs.append(rec.plans)
                 ops = []
@@ -859,7 +910,8 @@ class BatchedLinearTrainer:
         L = self.L
         ops = prog[xi]
         if self._planes_step:
-            for k in range(6):                                # l1, reduce, mid_fwd, InfoNCE passes, mid_bwd, dW1 + RMSprop + tail: every voter's, one launch each
+            # l1, reduce, mid_fwd, InfoNCE passes, (IIC core + z dP0,) mid_bwd, (dW3,) dW1 + RMSprop + tail: every voter's, one launch each
+            for k in range(len(ops)):
                 if self.trainers[0]._cold:
                     self.trainers[0]._evict()
                 _lib.check(_L.idl_plan_launch(ctypes.c_void_p(ops[k][0].data_ptr()), _p(ops[k][1]), L, _stream()))

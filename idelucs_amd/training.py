@@ -62,13 +62,34 @@ def plane_step_applies(model):
     return H1 == 512 and F >= 1024 and F % 512 == 0 and m >= 256 and m % 128 == 0
 
 
+def lockstep_rows_applies(model):
+    """Whether a rank's voters of this model train in lockstep at 48 < n_clusters <= 200 (fused.rows_lockstep_applies on the model's full-batch
+    shape: the step's two-plane form recorded, eight launches for all voters).  Decided up front from the shape and the process's settings, like
+    plane_step_applies: IDELUCS_PLANES=0, lockstep_planes=0, the k = 4 / 5 shapes and n_clusters beyond 200 train one voter after the other."""
+    from . import fused
+    if not (48 < model.n_clusters <= 200 and getattr(model, "_use_fused", False)):
+        return False
+    try:
+        lin1 = model.net.layers[0]
+        F, H1 = int(lin1.in_features), int(lin1.out_features)
+        import torch
+        cus = torch.cuda.get_device_properties(lin1.weight.device).multi_processor_count
+    except (AttributeError, IndexError, TypeError, ValueError, AssertionError, RuntimeError):
+        return False
+    store = getattr(model, "store", None)
+    return fused.rows_lockstep_applies(2 * int(model.batch_sz), H1, F, int(model.n_clusters), int(store.n) if store is not None else 0, cus)
+
+
 def voter_lanes(n_voters_here, model=None):
     """How many voters of one rank train in lockstep as one batch (IDELUCS_VOTER_LANES; 1 = one after the other).
     One training step is a handful of launches, most of them latency-bound; batched, each launch serves every voter of the batch
     (fused.BatchedLinearTrainer: blockIdx.y = voter), the two big products included when the step takes them from fp16 planes
     (plane_step_applies).  Default: all of a rank's voters, up to 8: at cfg2 a voter-epoch costs 54.2 ms alone and 47.5 / 45.4 / 43.6 ms in
     lockstep batches of 2 / 4 / 8 (bench.py: predicted_fixed_job).  With IDELUCS_DEV=lockstep_planes=0 a batch runs the products as batched
-    fp32 library GEMMs (58.9 / 54.8 / 52.6 ms): a lone voter on planes then beats a batch of 2, and two voters train one after the other."""
+    fp32 library GEMMs (58.9 / 54.8 / 52.6 ms): a lone voter on planes then beats a batch of 2, and two voters train one after the other.
+    The same default holds at 48 < n_clusters <= 200 (lockstep_rows_applies): at 200 output units a voter-epoch of 100 000 x 3 pairs costs 74.6 ms
+    alone and 58.1 / 55.1 / 53.9 / 54.0 / 51.4 ms in lockstep batches of 2 / 3 / 4 / 5 / 8 (tools/bench_lockstep_rows.py, profiles/r08_lockstep_rows.jsonl:
+    every lane count clears the sequential rounds' own spread by far, so none falls back to 1)."""
     env = os.environ.get("IDELUCS_VOTER_LANES")
     lanes = max(1, min(int(env) if env is not None else 8, n_voters_here))
     from . import fused
@@ -78,11 +99,13 @@ def voter_lanes(n_voters_here, model=None):
 
 
 def can_batch(model):
-    """Voters can be batched when the model runs the default fused launch sequence (NetLinear + RMSprop, n_clusters <= 48, full
-    batches a multiple of 16 rows) and no scheduler reads the epoch loss on the host between epochs."""
+    """Voters can be batched when the model runs the default fused launch sequence (NetLinear + RMSprop, full batches a multiple of
+    16 rows; n_clusters <= 48 on either step form, 48 < n_clusters <= 200 where the two-plane form applies: lockstep_rows_applies) and
+    no scheduler reads the epoch loss on the host between epochs."""
     # (the CLI hands the scheduler over as the reference does, as a string: "None" unless Plateau / Triangle was asked for)
-    return bool(model._use_fused and model.n_clusters <= 48 and model.batch_sz % 16 == 0
-                and model.schedule not in ('Plateau', 'Triangle'))
+    if not (model._use_fused and model.batch_sz % 16 == 0 and model.schedule not in ('Plateau', 'Triangle')):
+        return False
+    return bool(model.n_clusters <= 48 or lockstep_rows_applies(model))
 
 
 def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=True):
@@ -112,12 +135,7 @@ def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=Tr
             continue
         if batched is None or batched.L != len(wave):
             lane_models = [model.lane() for _ in wave]
-            try:
-                batched = BatchedLinearTrainer([m.net for m in lane_models], model.lr, model.weight, model.l, seed=model.seed)
-            except ValueError:       # a network the batched step does not take (n_clusters > 48)
-                for v in voters[w:]:
-                    out[v] = train_voter(model, n_epochs, v, n_voters, progress)
-                return out
+            batched = BatchedLinearTrainer([m.net for m in lane_models], model.lr, model.weight, model.l, seed=model.seed)
             for m, t in zip(lane_models, batched.trainers):
                 m._fused = t
         if progress:
@@ -129,20 +147,31 @@ def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=Tr
             curves = {v: [] for v in wave}
             n_batches = (model.store.n_pairs + model.batch_sz - 1) // model.batch_sz
             gemm_tuning.maybe_enable(n_batches * n_epochs * len(voters))
-            for _ in range(n_epochs):
-                for m in lane_models:
-                    m.net.train()
-                res = batched.run_epoch(model.store, model.batch_sz, [m._gen for m in lane_models])
-                for m, v, (total, nb) in zip(lane_models, wave, res):
-                    curves[v].append(m._finish_epoch(total / (nb - 1), sync=False))     # models.py:135 quirk (divide by last index)
             try:
+                for epoch in range(n_epochs):
+                    for m in lane_models:
+                        m.net.train()
+                    res = batched.run_epoch(model.store, model.batch_sz, [m._gen for m in lane_models])
+                    for m, v, (total, nb) in zip(lane_models, wave, res):
+                        curves[v].append(m._finish_epoch(total / (nb - 1), sync=False))     # models.py:135 quirk (divide by last index)
+                    # data outside the planes' range shows in the first epoch: one read of every lane's flag then, so that it costs an epoch and
+                    # not a whole training pass of the batch (a run that diverges later: the predicts' check)
+                    if epoch == 0 and not attempt and batched.planes_overflowed():
+                        for m in lane_models:
+                            m._check_planes()
                 for m, v in zip(lane_models, wave):
                     out[v] = ([float(x) for x in curves[v]],) + tuple(m.predict())
                 break
             except models.PlanesOverflow as err:     # (as train_voter: the fp32 form, and the whole batch of voters again)
-                if attempt or not _leave_planes(lane_models, err):
+                if attempt or not _leave_planes(lane_models + [model], err):
                     raise
                 batched.drop_planes()
+                if not can_batch(model):
+                    # beyond 48 classes there is no fp32 form to record: this batch's voters and the remaining ones one after the other on the
+                    # fp32 tiles, which is the IDELUCS_PLANES=0 run
+                    for v in voters[w:]:
+                        out[v] = train_voter(model, n_epochs, v, n_voters, progress)
+                    return out
     # the caller goes on with `model`: leave it holding the LAST voter's weights, as after a sequential run
     if lane_models is not None and len(voters) % lanes != 1:
         last = lane_models[(len(voters) - 1) % lanes if len(voters) % lanes else lanes - 1]
