@@ -236,6 +236,9 @@ def build_parser():
     p.add_argument("--seed", action="store", type=int, default=0)
     p.add_argument("--small_step", action="store", type=str, default=None, choices=["autograd", "native"],
                    help="model_size='small': train on torch autograd (the default) or on the native HIP step (RMSprop only)")
+    # (no default: without the flag the namespace, the printed parameters and the results table have no such key)
+    p.add_argument("--linear_step", action="store", type=str, default=argparse.SUPPRESS, choices=["autograd", "native"],
+                   help="model_size='linear' with --optimizer SGD or Adam: train on torch autograd (the default) or on the native HIP step")
     return p
 
 

@@ -1,0 +1,339 @@
+// opt_step.hip -- the last launch of a NetLinear training step whose optimizer is SGD with momentum or Adam (reference
+// idelucs/models.py:89-92, stepped at models.py:131-132): idl_opt_step_gather_wgrad, the counterpart of idl_rmsprop_step_gather_wgrad
+// (train_step.hip) with the optimizer generalised.  The forward, the backward and the loss launches in front of it do not know
+// which optimizer follows them; this file is where the two enter the step.
+//
+// Grid, as the RMSprop launch's: [dW2 tiles][next-batch gather blocks][streaming optimizer blocks], 256 threads each.
+//   dW2 tiles       one 16 x 16 tile of wg_dy^T wg_x each on the fp32 matrix cores (v_mfma_f32_16x16x4_f32), the four waves splitting
+//                   the contraction index, partial tiles added through LDS in a fixed order, the update applied from registers
+//   gather blocks   idl_dev::gather_block: the optional rider that assembles the next batch
+//   optimizer       every other tensor: 16-byte accesses, four elements' loads of every stream in flight before the first use;
+//                   tensors whose gradient arrives as stacked partials (bias gradients, dW3 at n_clusters <= 48) per element, the
+//                   partials summed in ascending order
+// Nothing is accumulated with atomics: every sum runs in a fixed order, a replayed step equals the eager one bit for bit.
+//
+// Hyperparameters are a DEVICE double[5] = {lr, momentum | beta1, beta2, eps, weight_decay}: a captured graph follows what a
+// scheduler changed between epochs, and Adam's bias corrections 1 - beta^t are formed in double as torch forms them on the host
+// (an fp32 1 - 0.999^t is 3e-5 off at t = 1, which a bias tensor that starts at zero shows in full).
+// Adam's step count is the optimizer's own (not ctl[0], the dropout counter, which restarts with every voter): every workgroup
+// reads *step_in and ONE thread writes *step_in + 1 to *step_out, a different word -- no word that a workgroup of this launch reads
+// is written in this launch (not all workgroups are resident before the first one ends).  The caller swaps the two words from step
+// to step.
+#include <string.h>
+
+#include "common.h"
+#include "scaler_device.h"
+#include "wave_ops.h"
+
+namespace {
+
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+constexpr int OPT_THREADS = 256;
+constexpr int OPT_UNROLL = 4;          // 16-byte elements per thread of the streaming update
+constexpr int OPT_MAX_BLOCKS = 1024;   // optimizer blocks of one tensor (beyond: a block walks on)
+constexpr int PART_CHUNK = 16;         // stacked partial gradients requested together
+constexpr int KIND_SGD = 1, KIND_ADAM = 2;
+
+struct OptArgs {
+    const float *loss_rows;   // optional step-loss assembly (models.py:128), as idl_rmsprop_step
+    float *out;
+    int loss_m;
+    float w_nce, w_iic;
+    float *p[8];
+    const float *g[8];
+    float *s1[8];             // SGD: momentum_buffer; Adam: exp_avg
+    float *s2[8];             // Adam: exp_avg_sq
+    int64_t n[8];
+    int parts[8];             // g[t] holds parts[t] stacked partial gradients [parts, n]
+    int count;
+    const float *wg_dy, *wg_x; float *wg_grad;
+    int wg_t, wg_m, wg_n_out, wg_n_in, wg_tiles, wg_xt;      // wg_xt: wg_x is stored transposed, [n_in, wg_m]
+    int first[9];             // optimizer blocks [first[t], first[t + 1]) belong to tensor t
+    const double *hyper;
+    const int64_t *step_in;
+    int64_t *step_out;
+    int64_t *ctl;
+    int64_t batch_advance;
+};
+
+// What one step's update needs, in the precision torch's kernels see it: the host-side Python floats rounded to fp32.
+template <int KIND>
+struct Coef {
+    float lr, mu, wd;                             // SGD
+    float step, bc2s, eps, b1w, b2, b2w;          // Adam: lr / bc1, sqrt(bc2), eps, 1 - beta1, beta2, 1 - beta2
+};
+
+__device__ __forceinline__ double pow_int(double b, int64_t e)      // b^e, e >= 0 (wave-uniform: no divergence)
+{
+    double r = 1.0;
+    while (e > 0) {
+        if (e & 1) r *= b;
+        b *= b;
+        e >>= 1;
+    }
+    return r;
+}
+
+template <int KIND>
+__device__ __forceinline__ Coef<KIND> make_coef(const OptArgs &a)
+{
+    Coef<KIND> c{};
+    const double lr = a.hyper[0], h1 = a.hyper[1], h2 = a.hyper[2], eps = a.hyper[3], wd = a.hyper[4];
+    c.wd = (float)wd;
+    if constexpr (KIND == KIND_SGD) {
+        c.lr = (float)lr; c.mu = (float)h1;
+    } else {
+        const int64_t t = *a.step_in + 1;
+        const double bc1 = 1.0 - pow_int(h1, t), bc2 = 1.0 - pow_int(h2, t);
+        c.step = (float)(lr / bc1); c.bc2s = (float)sqrt(bc2); c.eps = (float)eps;
+        c.b1w = (float)(1.0 - h1); c.b2 = (float)h2; c.b2w = (float)(1.0 - h2);
+    }
+    return c;
+}
+
+// torch.optim.SGD (momentum, weight decay; dampening 0, no nesterov): g' = g + wd p; buf = mu buf + g'; p -= lr buf -- a zero buf
+// makes the first step buf = g', torch's clone.  torch.optim.Adam (no amsgrad): m.lerp_(g, 1 - b1); v = b2 v + (1 - b2) g g;
+// p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).
+template <int KIND>
+__device__ __forceinline__ void opt_update(float g, float &p, float &s1, float &s2, const Coef<KIND> &c)
+{
+    g = fmaf(c.wd, p, g);
+    if constexpr (KIND == KIND_SGD) {
+        s1 = fmaf(c.mu, s1, g);
+        p = fmaf(-c.lr, s1, p);
+    } else {
+        const float d = g - s1;
+        s1 = c.b1w < 0.5f ? fmaf(c.b1w, d, s1) : g - d * (1.0f - c.b1w);      // (Tensor.lerp_'s two forms)
+        s2 = fmaf(c.b2w * g, g, c.b2 * s2);
+        const float denom = sqrtf(s2) / c.bc2s + c.eps;
+        p = fmaf(-c.step, s1 / denom, p);
+    }
+}
+
+// One 16 x 16 tile of dy^T x: the four waves take a quarter of the contraction index each.  red: 1024 floats of LDS.
+// (The three operand loops and the LDS reduction are train_step.hip's wgrad_tile_rms without its look-ahead and spin forms, and the
+//  streaming body below follows rmsprop_body: that file's kernels stay as they are -- their register, ISA and bit-for-bit tests pin them --
+//  so a fix to the tile loop is made in BOTH files until the loops move into a shared .inc, as at_b_tile.inc did.)
+template <int KIND>
+__device__ __forceinline__ void wgrad_tile(const OptArgs &a, int tile, const Coef<KIND> &c, float *red, const int tid)
+{
+    const int lane = tid & 63, wv = tid >> 6, l = lane & 15, q = lane >> 4;
+    const int tn = a.wg_n_in / 16;
+    const int i0 = (tile / tn) * 16, j0 = (tile % tn) * 16;
+    const int lda = a.wg_n_out, ldb = a.wg_n_in, m = a.wg_m;
+    const int per = ((m + 15) / 16) * 4;                     // rows per wave, a multiple of 4
+    const int kb = wv * per, ke = (kb + per < m) ? kb + per : m;
+    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+    const float *pa = a.wg_dy + i0 + l, *pb = a.wg_x + j0 + l;    // A[i = l][k = q] = dy[k][i0 + l], B[k = q][j = l] = x[k][j0 + l]
+    if (a.wg_xt && (per & 127) == 0 && kb + per <= m) {
+        // x stored transposed ([n_in, m]): lane (l, q) walks 32 consecutive k of ITS column per batch (16-byte reads), and MFMA step
+        // u takes k = k0 + 32 q + u on both operands -- any assignment of k to (step, q) is a valid order of the same sum
+        const float *pbt = a.wg_x + (int64_t)(j0 + l) * m;
+        for (int k0 = kb; k0 < ke; k0 += 128) {
+            float av[32], bv[32];
+#pragma unroll
+            for (int u4 = 0; u4 < 8; ++u4) {
+                const float4 t4 = *(const float4 *)(pbt + k0 + 32 * q + 4 * u4);
+                bv[4 * u4] = t4.x; bv[4 * u4 + 1] = t4.y; bv[4 * u4 + 2] = t4.z; bv[4 * u4 + 3] = t4.w;
+            }
+#pragma unroll
+            for (int u = 0; u < 32; ++u) av[u] = pa[(k0 + 32 * q + u) * lda];
+#pragma unroll
+            for (int u = 0; u < 32; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
+        }
+    } else if (a.wg_xt) {
+        for (int k0 = kb; k0 < ke; k0 += 4) {
+            const int k = k0 + q;
+            const bool ok = k < ke;
+            const float ta = ok ? pa[k * lda] : 0.f, tb = ok ? a.wg_x[(int64_t)(j0 + l) * m + k] : 0.f;
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ta, tb, acc, 0, 0, 0);
+        }
+    } else {
+        for (int k0 = kb; k0 < ke; k0 += 128) {              // 64 independent loads in flight per lane, then 32 MFMAs
+            float av[32], bv[32];
+#pragma unroll
+            for (int u = 0; u < 32; ++u) {
+                const int k = k0 + 4 * u + q;
+                const bool ok = k < ke;
+                const int kc = ok ? k : ke - 1;              // clamped, not predicated: inside the operands, the loads stay unconditional
+                const float ta = pa[kc * lda], tb = pb[kc * ldb];
+                av[u] = ok ? ta : 0.f;
+                bv[u] = ok ? tb : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 32; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
+        }
+    }
+    const int o = (i0 + (tid >> 4)) * ldb + j0 + (tid & 15);      // this thread's element of the tile in the epilogue
+    float *p = a.p[a.wg_t], *s1 = a.s1[a.wg_t], *s2 = a.s2[a.wg_t];
+    float pi = p[o], ai = s1[o], bi = KIND == KIND_ADAM ? s2[o] : 0.f;      // (requested before the barrier: beside the LDS round trip)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wv * 256 + (4 * q + r) * 16 + l] = acc[r];          // C/D: row = 4 q + reg, col = l
+    __syncthreads();
+    const float g = (red[tid] + red[256 + tid]) + (red[512 + tid] + red[768 + tid]);
+    if (a.wg_grad != nullptr) a.wg_grad[o] = g;
+    opt_update<KIND>(g, pi, ai, bi, c);
+    s1[o] = ai;
+    if constexpr (KIND == KIND_ADAM) s2[o] = bi;
+    p[o] = pi;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(OptArgs a, int n_gather, idl_dev::GatherArgs g)
+{
+    const int blk = (int)blockIdx.x, tix = (int)threadIdx.x;
+    // grid order: the weight-gradient tiles (dependent chains of strided loads: first, so that the streaming blocks behind them hide
+    // their latency), then the gather blocks, then the optimizer blocks
+    const int b0 = blk - a.wg_tiles;
+    if (b0 >= 0 && b0 < n_gather) {
+        idl_dev::gather_block(g, (int64_t)b0, tix);
+        return;
+    }
+    const Coef<KIND> c = make_coef<KIND>(a);
+    if (blk < a.wg_tiles) {
+        __shared__ float red[1024];
+        wgrad_tile<KIND>(a, blk, c, red, tix);
+        return;
+    }
+    const int bid = b0 - n_gather;
+    int t = 0;
+    while (t + 1 < a.count && bid >= a.first[t + 1]) ++t;
+    const int bx = bid - a.first[t], gx = a.first[t + 1] - a.first[t];
+    if (gx > 0) {
+        float *p = a.p[t]; const float *gr = a.g[t]; float *s1 = a.s1[t]; float *s2 = a.s2[t];
+        const int64_t n = a.n[t];
+        const uintptr_t al = ((uintptr_t)p) | ((uintptr_t)gr) | ((uintptr_t)s1) | (KIND == KIND_ADAM ? (uintptr_t)s2 : 0);
+        if (a.parts[t] == 1 && (n & 3) == 0 && (al & 15u) == 0) {
+            float4 *p4 = (float4 *)p; const float4 *g4 = (const float4 *)gr; float4 *a4 = (float4 *)s1; float4 *b4 = (float4 *)s2;
+            const int64_t n4 = n / 4, stride = (int64_t)gx * OPT_THREADS;
+            for (int64_t i = (int64_t)bx * OPT_THREADS + tix; i < n4; i += OPT_UNROLL * stride) {
+                float4 pv[OPT_UNROLL], gv[OPT_UNROLL], av[OPT_UNROLL], bv[OPT_UNROLL];
+#pragma unroll
+                for (int u = 0; u < OPT_UNROLL; ++u) {
+                    const int64_t iu = i + u * stride < n4 ? i + u * stride : i;        // clamped, not predicated: the loads stay unconditional
+                    pv[u] = p4[iu]; gv[u] = g4[iu]; av[u] = a4[iu];
+                    if constexpr (KIND == KIND_ADAM) bv[u] = b4[iu]; else bv[u] = float4{0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int u = 0; u < OPT_UNROLL; ++u) {
+                    if (i + u * stride < n4) {
+                        opt_update<KIND>(gv[u].x, pv[u].x, av[u].x, bv[u].x, c); opt_update<KIND>(gv[u].y, pv[u].y, av[u].y, bv[u].y, c);
+                        opt_update<KIND>(gv[u].z, pv[u].z, av[u].z, bv[u].z, c); opt_update<KIND>(gv[u].w, pv[u].w, av[u].w, bv[u].w, c);
+                        a4[i + u * stride] = av[u];
+                        if constexpr (KIND == KIND_ADAM) b4[i + u * stride] = bv[u];
+                        p4[i + u * stride] = pv[u];
+                    }
+                }
+            }
+        } else {
+            const int parts = a.parts[t];
+            for (int64_t i = (int64_t)bx * OPT_THREADS + tix; i < n; i += (int64_t)gx * OPT_THREADS) {
+                float pi = p[i], ai = s1[i], bi = KIND == KIND_ADAM ? s2[i] : 0.f;
+                float sum = gr[i];
+                for (int q0 = 1; q0 < parts; q0 += PART_CHUNK) {      // PART_CHUNK independent loads in flight, added in ascending order
+                    float part[PART_CHUNK];
+#pragma unroll
+                    for (int q = 0; q < PART_CHUNK; ++q) part[q] = gr[(int64_t)(q0 + q < parts ? q0 + q : q0) * n + i];
+#pragma unroll
+                    for (int q = 0; q < PART_CHUNK; ++q) if (q0 + q < parts) sum += part[q];
+                }
+                opt_update<KIND>(sum, pi, ai, bi, c);
+                s1[i] = ai;
+                if constexpr (KIND == KIND_ADAM) s2[i] = bi;
+                p[i] = pi;
+            }
+        }
+    }
+    if (bid == 0 && tix == 0) {
+        // (ctl[1] is what the gather blocks of this launch read: it moves here only in a launch without them -- the launcher sees to it)
+        a.ctl[0] += 1;
+        if (a.batch_advance != 0) a.ctl[1] += a.batch_advance;
+        *a.step_out = *a.step_in + 1;
+    }
+    if (a.out != nullptr && bid == a.first[a.count] - 1 && tix < 64) {
+        // step loss = w_nce * mean(loss_rows) + w_iic * IIC (left in out[3] by the IIC core); out[1] = running sum
+        const float iic = a.out[3], run = a.out[1];
+        float acc = 0.f;
+        for (int i0 = 0; i0 < a.loss_m; i0 += 64 * 16) {      // 16 loads in flight, added in ascending order
+            float part[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) { const int i = i0 + tix + 64 * j; part[j] = i < a.loss_m ? a.loss_rows[i] : 0.f; }
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc += part[j];
+        }
+        acc = idl_dev::wave_sum_f(acc) / (float)a.loss_m;
+        if (tix == 0) { const float l = a.w_nce * acc + a.w_iic * iic; a.out[0] = l; a.out[1] = run + l; a.out[2] = acc; }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int idl_opt_step_gather_wgrad(int kind, int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
+                              float *const *state1, float *const *state2, const int64_t *sizes, const double *hyper,
+                              const int64_t *step_in, int64_t *step_out, int64_t *ctl,
+                              const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out,
+                              const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx, int64_t n_pairs,
+                              int64_t batch, const double *mean, const double *scale, const double *inv_scale, float *y,
+                              int wg_index, const float *wg_dy, const float *wg_x, int wg_x_transposed, int wg_m, int wg_n_out, int wg_n_in,
+                              float *wg_grad, int64_t batch_advance, void *stream)
+{
+    IDL_REQUIRE(kind == KIND_SGD || kind == KIND_ADAM, "opt_step: kind 1 (SGD with momentum) or 2 (Adam)");
+    IDL_REQUIRE(count >= 1 && count <= 8 && params && grads && state1 && sizes && hyper && ctl, "opt_step: 1..8 tensors");
+    IDL_REQUIRE(kind != KIND_ADAM || state2 != nullptr, "opt_step: Adam needs exp_avg_sq (state2)");
+    IDL_REQUIRE(step_in && step_out && step_in != step_out, "opt_step: the step count is read from one word and written to another");
+    IDL_REQUIRE((const void *)step_in != (const void *)ctl && (const void *)step_in != (const void *)(ctl + 1),
+                "opt_step: step_in must not be a word this launch writes");
+    IDL_REQUIRE((((uintptr_t)hyper) & 7u) == 0, "opt_step: hyper is a device double[5]");
+    OptArgs a{};
+    a.count = count;
+    IDL_REQUIRE(loss_rows == nullptr || (out != nullptr && loss_m > 0), "opt_step: loss_rows given without out or with loss_m < 1");
+    a.loss_rows = loss_rows; a.out = loss_rows != nullptr ? out : nullptr; a.loss_m = loss_m; a.w_nce = w_nce; a.w_iic = w_iic;
+    a.hyper = hyper; a.step_in = step_in; a.step_out = step_out; a.ctl = ctl; a.batch_advance = batch_advance;
+    for (int i = 0; i < count; ++i) {
+        a.p[i] = params[i]; a.g[i] = grads[i]; a.s1[i] = state1[i]; a.s2[i] = kind == KIND_ADAM ? state2[i] : nullptr; a.n[i] = sizes[i];
+        a.parts[i] = grad_parts ? grad_parts[i] : 1;
+        IDL_REQUIRE(a.parts[i] >= 1 && sizes[i] >= 0, "opt_step: grad_parts must be >= 1, sizes >= 0");
+        IDL_REQUIRE(sizes[i] == 0 || (a.p[i] && a.s1[i] && (kind != KIND_ADAM || a.s2[i])), "opt_step: a tensor without its parameter or state pointer");
+        IDL_REQUIRE(sizes[i] == 0 || i == wg_index || a.g[i], "opt_step: a tensor without its gradient");
+    }
+    if (wg_index >= 0) {
+        IDL_REQUIRE(wg_index < count && wg_dy && wg_x && wg_m >= 1 && wg_n_out >= 16 && (wg_n_out % 16) == 0 && wg_n_in >= 16 &&
+                    (wg_n_in % 16) == 0 && sizes[wg_index] == (int64_t)wg_n_out * wg_n_in && (int64_t)wg_m * wg_n_in < (1ll << 31) &&
+                    (int64_t)wg_m * wg_n_out < (1ll << 31),
+                    "opt_step: in-launch weight gradient needs n_out, n_in multiples of 16 and sizes[wg_index] == n_out * n_in");
+        IDL_REQUIRE(!wg_x_transposed || ((wg_m & 3) == 0 && (((uintptr_t)wg_x) & 15u) == 0), "opt_step: transposed wg_x needs 4 | m and 16-byte alignment");
+        a.wg_t = wg_index; a.wg_dy = wg_dy; a.wg_x = wg_x; a.wg_grad = wg_grad; a.wg_m = wg_m; a.wg_n_out = wg_n_out; a.wg_n_in = wg_n_in;
+        a.wg_tiles = (wg_n_out / 16) * (wg_n_in / 16);
+        a.wg_xt = wg_x_transposed ? 1 : 0;
+        a.n[wg_index] = 0;                  // its optimizer blocks have nothing to do: the tile workgroups update it
+    }
+    idl_dev::GatherArgs g{};
+    if (feats != nullptr) {
+        IDL_REQUIRE(pair_idx && mean && scale && y && n >= 1 && f >= 1 && batch >= 1 && n_pairs >= 0, "opt_step: bad gather arguments");
+        IDL_REQUIRE(batch_advance == 0, "opt_step: the launch that assembles the next batch reads ctl[1] and cannot advance it");
+        g = idl_dev::GatherArgs{feats, n, f, view_stride, pair_idx, ctl + 1, batch, n_pairs, mean, scale, inv_scale, y};
+    }
+    int nb_total = 0;
+    for (int i = 0; i < count; ++i) {
+        const uintptr_t al = ((uintptr_t)a.p[i]) | ((uintptr_t)a.g[i]) | ((uintptr_t)a.s1[i]) | ((uintptr_t)a.s2[i]);
+        const bool vec = a.parts[i] == 1 && (a.n[i] & 3) == 0 && (al & 15u) == 0;
+        int64_t nb = vec ? (a.n[i] / 4 + OPT_THREADS * OPT_UNROLL - 1) / (OPT_THREADS * OPT_UNROLL) : (a.n[i] + OPT_THREADS - 1) / OPT_THREADS;
+        if (nb > OPT_MAX_BLOCKS) nb = OPT_MAX_BLOCKS;
+        a.first[i] = nb_total;
+        nb_total += (int)nb;
+    }
+    if (nb_total == 0) nb_total = 1;        // (step counter / loss assembly still need a block)
+    for (int i = count; i <= 8; ++i) a.first[i] = nb_total;
+    const int64_t extra = g.y != nullptr ? idl_dev::gather_blocks(g.f, g.batch) : 0;
+    IDL_REQUIRE(extra + nb_total + a.wg_tiles < (1ll << 30), "opt_step: grid too large");
+    const dim3 grid((unsigned)(a.wg_tiles + extra + nb_total)), block(OPT_THREADS);
+    if (kind == KIND_SGD) hipLaunchKernelGGL(opt_step_kernel<KIND_SGD>, grid, block, 0, (hipStream_t)stream, a, (int)extra, g);
+    else hipLaunchKernelGGL(opt_step_kernel<KIND_ADAM>, grid, block, 0, (hipStream_t)stream, a, (int)extra, g);
+    IDL_HIP_TRY(hipGetLastError());
+    return IDL_OK;
+}
+
+}  // extern "C"

@@ -991,6 +991,7 @@ __device__ __forceinline__ void tail_sync(const int tix, unsigned int *spin)
     }
 }
 
+// (opt_step.hip's wgrad_tile carries a copy of the operand loops and the reduction below: a fix here is made there too.)
 template <bool AHEAD, bool SPIN = false>
 __device__ __forceinline__ void wgrad_tile_rms(const RmsArgs &a, int tile, float lr, float alpha, float eps, float wd, float oma, float *red, const int tix,
                                                unsigned int *spin)

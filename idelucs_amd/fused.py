@@ -205,7 +205,55 @@ class _Recorder:
         self.plans.append(blob)
 
 
-class FusedLinearTrainer:
+class _LinearStepParts:
+    """What every explicit NetLinear step shares whichever optimizer ends it (FusedLinearTrainer; fused_opt.FusedLinearOptTrainer): the
+    buffers of a batch shape, the argument lists of the optimizer-free launches, the prologue gather and the two ways a step is issued.
+    A user provides params / grads / parts, the network's shapes, weight, ctl, _perm, _bufs, _shared_buffers and step_on_batch."""
+
+    def gradient(self, i):
+        """Gradient of parameter i as a tensor of the parameter's shape (sums the stacked partials)."""
+        return self.grads[i].sum(0) if self.parts[i] > 1 else self.grads[i]
+
+    def buffers(self, m):
+        if m not in self._bufs:
+            self._bufs[m] = _Buffers(m, self.F, self.H1, self.H2, self.C, self.dev, shared=(self._shared_buffers or {}).get(m))
+        return self._bufs[m]
+
+    def _next_batch(self, st, m):
+        """The arguments with which a middle launch assembles its share of the next batch: the store, the pair list and the offset."""
+        return (_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
+                _p(st.mean), _p(st.scale), _p(st.inv_scale))
+
+    def _mid_fwd_args(self, bf, tr):
+        return (_p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3), bf.m, self.C, tr, self.seed, _p(self.ctl),
+                _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z))
+
+    def _mid_bwd_args(self, bf, tr, r1, gW3):
+        _, gb1, _, gb2, _, gb3 = self.grads
+        m = bf.m
+        return (_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), _p(self.W2), _p(r1), m, self.C, tr,
+                (1.0 - self.weight) / (m * TEMPERATURE), _p(bf.dlogits), _p(bf.dlat), _p(bf.dr1), _p(gb1), _p(gb2), _p(gb3), _p(gW3))
+
+    def _gather(self, store, bf):
+        b = bf.m // 2
+        _lib.check(_L.idl_gather_pairs_at(_p(store.feats), store.n, store.f, store.n * store.f, _p(self._perm), _p(self.ctl[1:]),
+                                          b, _p(store.mean), _p(store.scale), _p(store.inv_scale), _p(bf.x), _stream()))
+        if getattr(bf, "_planes", None) is not None:
+            bf._planes["valid"][0] = False
+            bf._planes["x32"][0] = True
+
+    def _full_step(self, store, bf, train=True, pipelined=False, xi=0, defer_tail=False):
+        """pipelined: bf.xs[xi] already holds this batch (assembled by the previous step, or by the prologue gather);
+        this step assembles the next one (into bf.xs[1 - xi] when the middle launches do it, else into bf.x).
+        defer_tail (run_epoch's steps): the step's optimizer tail may wait for the next step's first launch (flush_tail)."""
+        if pipelined:
+            self.step_on_batch(bf, train=train, batch_advance=bf.m // 2, next_from=store, xi=xi if self.F % 4 == 0 else 0, defer_tail=defer_tail)
+        else:
+            self._gather(store, bf)
+            self.step_on_batch(bf, train=train, batch_advance=bf.m // 2)
+
+
+class FusedLinearTrainer(_LinearStepParts):
     def __init__(self, net, lr, weight, lamb, weight_decay=0.01, alpha=0.99, eps=1e-8, seed=0, grad_w1=None, shared_buffers=None):
         lin1, lin2, lin3 = net.layers[0], net.layers[3], net.classifier[2]
         self.net = net
@@ -293,17 +341,8 @@ class FusedLinearTrainer:
         for v in self.square_avg:               # a voter starts with fresh optimizer state (models.IID_model.begin_voter)
             v.zero_()
 
-    def gradient(self, i):
-        """Gradient of parameter i as a tensor of the parameter's shape (sums the stacked partials)."""
-        return self.grads[i].sum(0) if self.parts[i] > 1 else self.grads[i]
-
     def set_lr(self, lr):
         self.hyper[0:1].fill_(float(lr))
-
-    def buffers(self, m):
-        if m not in self._bufs:
-            self._bufs[m] = _Buffers(m, self.F, self.H1, self.H2, self.C, self.dev, shared=(self._shared_buffers or {}).get(m))
-        return self._bufs[m]
 
     def _k(self, fn, *args):
         """One kernel launch of the step: performed, or recorded while a BatchedLinearTrainer is recording."""
@@ -369,11 +408,6 @@ class FusedLinearTrainer:
         else:
             self._step_general(bf, tr, batch_advance, st, xi)
 
-    def _next_batch(self, st, m):
-        """The arguments with which a middle launch assembles its share of the next batch: the store, the pair list and the offset."""
-        return (_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                _p(st.mean), _p(st.scale), _p(st.inv_scale))
-
     def _tail(self, bf, sizes=None):
         """The leading arguments of an optimizer launch: every tensor's RMSprop (sizes: self._sz, or without W1), the step loss."""
         return (len(self.params), self._pp, self._gp, self._parts, self._vp, self._sz if sizes is None else sizes, _p(self.hyper),
@@ -383,16 +417,6 @@ class FusedLinearTrainer:
         """The trailing arguments of an optimizer launch: the dW2 = dlat^T r1 tiles, the batch offset's advance, the stream."""
         m = bf.m
         return (2, _p(bf.dlat), _p(r1), transposed, m, self.H2, self.H1, _p(self.grads[2]), advance, _stream())
-
-    def _mid_fwd_args(self, bf, tr):
-        return (_p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3), bf.m, self.C, tr, self.seed, _p(self.ctl),
-                _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z))
-
-    def _mid_bwd_args(self, bf, tr, r1, gW3):
-        _, gb1, _, gb2, _, gb3 = self.grads
-        m = bf.m
-        return (_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), _p(self.W2), _p(r1), m, self.C, tr,
-                (1.0 - self.weight) / (m * TEMPERATURE), _p(bf.dlogits), _p(bf.dlat), _p(bf.dr1), _p(gb1), _p(gb2), _p(gb3), _p(gW3))
 
     def _gw1(self):
         return _p(self.grads[0]) if self._keep_w1_grad else None
@@ -725,24 +749,6 @@ class FusedLinearTrainer:
                 bf._planes["valid"] = [False, False]
                 bf._planes["x32"] = [True, True]
                 bf._planes["dr1_as_planes"] = False
-
-    def _gather(self, store, bf):
-        b = bf.m // 2
-        _lib.check(_L.idl_gather_pairs_at(_p(store.feats), store.n, store.f, store.n * store.f, _p(self._perm), _p(self.ctl[1:]),
-                                          b, _p(store.mean), _p(store.scale), _p(store.inv_scale), _p(bf.x), _stream()))
-        if getattr(bf, "_planes", None) is not None:
-            bf._planes["valid"][0] = False
-            bf._planes["x32"][0] = True
-
-    def _full_step(self, store, bf, train=True, pipelined=False, xi=0, defer_tail=False):
-        """pipelined: bf.xs[xi] already holds this batch (assembled by the previous step, or by the prologue gather);
-        this step assembles the next one (into bf.xs[1 - xi] when the middle launches do it, else into bf.x).
-        defer_tail (run_epoch's steps): the step's optimizer tail may wait for the next step's first launch (flush_tail)."""
-        if pipelined:
-            self.step_on_batch(bf, train=train, batch_advance=bf.m // 2, next_from=store, xi=xi if self.F % 4 == 0 else 0, defer_tail=defer_tail)
-        else:
-            self._gather(store, bf)
-            self.step_on_batch(bf, train=train, batch_advance=bf.m // 2)
 
     # ------------------------------------------------------------------ one epoch over the store
     @torch.no_grad()

@@ -1,0 +1,253 @@
+"""idelucs_amd.fused_opt -- the explicit training step of NetLinear with torch.optim.SGD or torch.optim.Adam (reference
+idelucs/models.py:89-92) on this library's own kernels, replayed as a HIP graph.  Opt-in: IID_model(args) with
+args['linear_step'] = 'native' (CLI: --linear_step native).
+
+Nothing in the forward or backward of the fp32 step forms of fused.FusedLinearTrainer knows which optimizer follows, so a step here is
+those launches with the gradient-only dW1 tiles and ONE new last launch (csrc/opt_step.hip):
+    n_clusters <= 48     idl_l1_fwd -> idl_mid_fwd_gather -> InfoNCE + IIC -> idl_mid_bwd_gather -> idl_wgrad_rmsprop (gradient only)
+                         -> idl_opt_step_gather_wgrad (dW2 tiles, SGD / Adam on every tensor, step loss, counters)
+    anything else        the choices of FusedLinearTrainer._step_general (library products for odd shapes and n_clusters > 48; at
+                         48 < n_clusters <= 200 the IIC core writes z dP0 itself), dW1 on the tiles where they apply, the same last launch
+The next batch rides in the two middle launches where it does for RMSprop.  SGD keeps momentum_buffer per tensor, Adam exp_avg and
+exp_avg_sq plus its step count in two words that swap roles from step to step (the launch reads one and writes the other).  The
+hyperparameters are copied from the torch optimizer's group before every epoch (sync_hyper): the schedulers keep acting on that
+object, CyclicLR on momentum / beta1 as well as the rate.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from ._lib import lib as _L
+from .fused import GATHER_SPLIT, STEPS_PER_GRAPH, TEMPERATURE, _LinearStepParts, _launch, _p, _stream, launch_losses
+
+KIND_SGD, KIND_ADAM = 1, 2
+_NO_GATHER = (None, 0, 0, 0, None, 0, 0, None, None, None, None)
+
+
+class FusedLinearOptTrainer(_LinearStepParts):
+    def __init__(self, net, optimizer, weight, lamb, seed=0):
+        """optimizer: the torch.optim.SGD / torch.optim.Adam object whose first group holds the hyperparameters (its state is not used)."""
+        if isinstance(optimizer, torch.optim.SGD):
+            self.kind = KIND_SGD
+        elif isinstance(optimizer, torch.optim.Adam):
+            self.kind = KIND_ADAM
+        else:
+            raise ValueError("FusedLinearOptTrainer needs a torch.optim.SGD or torch.optim.Adam object")
+        grp = optimizer.param_groups[0]
+        if grp.get('nesterov') or grp.get('dampening') or grp.get('amsgrad') or grp.get('maximize'):
+            raise ValueError("FusedLinearOptTrainer: nesterov, dampening, amsgrad and maximize are not supported")
+        lin1, lin2, lin3 = net.layers[0], net.layers[3], net.classifier[2]
+        self.net, self.optimizer = net, optimizer
+        self.W1, self.b1, self.W2, self.b2, self.W3, self.b3 = lin1.weight, lin1.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias
+        self.params = [self.W1, self.b1, self.W2, self.b2, self.W3, self.b3]
+        self.dev = self.W1.device
+        self.F, self.H1, self.H2, self.C = lin1.in_features, lin1.out_features, lin2.out_features, lin3.out_features
+        if self.H1 != 512 or self.H2 != 64 or self.C > 256 or lin2.in_features != self.H1 or lin3.in_features != 64:
+            raise ValueError("FusedLinearOptTrainer needs NetLinear (hidden 512, latent 64) and n_clusters <= 256")
+        # gradients as FusedLinearTrainer keeps them: the biases (and dW3 at n_clusters <= 48, from the middle backward) as stacked partial sums
+        self.parts = [1 if p.dim() == 2 else _L.idl_col_sum_parts() for p in self.params]
+        if self.C <= 48:
+            self.parts[4] = _L.idl_col_sum_parts()
+        self.grads = [torch.zeros((q,) + tuple(p.shape), dtype=p.dtype, device=p.device) if q > 1 else torch.zeros_like(p)
+                      for p, q in zip(self.params, self.parts)]
+        self.weight, self.lamb, self.seed = float(weight), float(lamb), int(seed) & (2 ** 64 - 1)
+        self.ctl = torch.zeros(2, dtype=torch.int64, device=self.dev)        # [dropout step counter, batch offset]
+        self.out = torch.zeros(4, dtype=torch.float32, device=self.dev)      # [step loss, running sum, nce, iic]
+        self._bufs, self._graphs, self._perm, self._shared_buffers = {}, {}, None, None
+        self.state1 = [torch.zeros_like(p) for p in self.params]             # SGD: momentum_buffer; Adam: exp_avg
+        self.state2 = [torch.zeros_like(p) for p in self.params] if self.kind == KIND_ADAM else []
+        self.hyper64 = torch.zeros(5, dtype=torch.float64, device=self.dev)      # [lr, momentum | beta1, beta2, eps, weight_decay]
+        self._hyper_host = [None] * 5
+        self.steps = torch.zeros(2, dtype=torch.int64, device=self.dev)          # the optimizer's step count: steps[_tpar] is current
+        self._tpar = 0
+        n = len(self.params)
+        self._pp = (ctypes.c_void_p * n)(*[p.data_ptr() for p in self.params])
+        self._gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in self.grads])
+        self._sz = (ctypes.c_int64 * n)(*[p.numel() for p in self.params])
+        self._parts = (ctypes.c_int32 * n)(*self.parts)
+        self._s1p = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.state1])
+        self._s2p = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.state2]) if self.state2 else None
+        self.sync_hyper()
+
+    # ------------------------------------------------------------------ state and hyperparameters
+    def state_tensors(self):
+        return list(self.state1) + list(self.state2)
+
+    def step_count(self):
+        """The optimizer's step count (waits for the device)."""
+        return int(self.steps[self._tpar].item())
+
+    def begin_voter(self, voter, keep_state=False):
+        """Dropout stream of voter v as FusedLinearTrainer.begin_voter sets it (ctl[0] starts at v << 24: voter v draws what it draws under
+        RMSprop).  keep_state: the previous voter's optimizer state stays (IDELUCS_VOTER_STATE=carry); the step count is part of it."""
+        self.ctl[0:1].fill_((int(voter) & 0xFF) << 24)
+        if keep_state:
+            return
+        for v in self.state_tensors():
+            v.zero_()
+        self.steps.zero_()
+        self._tpar = 0
+
+    def sync_hyper(self):
+        """Copy the torch optimizer's current group to the device (before every epoch: the schedulers act on that object)."""
+        grp = self.optimizer.param_groups[0]
+        if self.kind == KIND_SGD:
+            vals = [grp['lr'], grp['momentum'], 0.0, 0.0, grp['weight_decay']]
+        else:
+            vals = [grp['lr'], grp['betas'][0], grp['betas'][1], grp['eps'], grp['weight_decay']]
+        for i, v in enumerate(vals):
+            v = float(v)
+            if v != self._hyper_host[i]:
+                self.hyper64[i:i + 1].fill_(v)    # (fill_ on a view: no host-to-device copy from pageable memory, FusedLinearTrainer.begin_voter)
+                self._hyper_host[i] = v
+
+    def layer1_output(self, bf):
+        """Layer 1's ReLU (+ Dropout) output of the last step on bf as an [m, 512] tensor (tests): the step forms whose layer-1 product is
+        W1 x^T keep it transposed."""
+        return bf.r1.view(self.H1, bf.m).t() if getattr(bf, "_r1_transposed", False) else bf.r1
+
+    # ------------------------------------------------------------------ one step on a filled bf.xs[xi]
+    def _opt(self, bf, r1, transposed, advance, gather=_NO_GATHER):
+        """The step's last launch: dW2 = dlat^T r1 tiles + the optimizer on every tensor + step loss + counters (+ the next batch)."""
+        m = bf.m
+        _launch(_L.idl_opt_step_gather_wgrad, self.kind, len(self.params), self._pp, self._gp, self._parts, self._s1p, self._s2p, self._sz,
+                _p(self.hyper64), _p(self.steps[self._tpar:]), _p(self.steps[1 - self._tpar:]), _p(self.ctl),
+                _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out), *gather,
+                2, _p(bf.dlat), _p(r1), transposed, m, self.H2, self.H1, _p(self.grads[2]), advance, _stream())
+        self._tpar ^= 1
+
+    def _dw1(self, bf, x):
+        m, H1, F = bf.m, self.H1, self.F
+        if _L.idl_wgrad_supported(m, H1, F):      # the dW1 tiles, gradient only
+            _launch(_L.idl_wgrad_rmsprop, _p(bf.dr1), _p(x), m, H1, F, _p(self.grads[0]), None, None, None, _stream())
+        else:
+            torch.mm(bf.dr1.t(), x, out=self.grads[0])
+
+    @torch.no_grad()
+    def step_on_batch(self, bf, train=True, batch_advance=0, next_from=None, xi=0, defer_tail=False):
+        """Forward, backward and the optimizer's update for the [m, F] batch in bf.xs[xi]; arguments as FusedLinearTrainer.step_on_batch
+        (defer_tail, which _full_step passes on, has no meaning here: the step ends with its own last launch)."""
+        tr, st = 1 if train else 0, next_from
+        m, C, H1, F = bf.m, self.C, self.H1, self.F
+        early = st is not None and m % 16 == 0 and F % 4 == 0      # the middle launches assemble the next batch into bf.xs[1 - xi]
+        if not early:
+            xi = 0                                                  # (otherwise the last launch does, into bf.x)
+        x, r1 = bf.xs[xi], bf.r1
+        bf._r1_transposed = early and C <= 48
+        if early and C <= 48 and _L.idl_l1_fwd_supported(m, H1, F) and _L.idl_wgrad_supported(m, H1, F):
+            _launch(_L.idl_l1_fwd, _p(self.W1), _p(x), m, F, _p(r1.view(H1, m)), _stream())
+            _launch(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
+                    0, GATHER_SPLIT, 8, _stream())
+            launch_losses(_launch, bf, self.lamb, self.weight, self.out)
+            _launch(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
+                    GATHER_SPLIT, 8, 8, 1, _stream())
+            self._dw1(bf, x)
+            self._opt(bf, r1, 1, m // 2)
+            return
+        self._step_general_opt(bf, tr, batch_advance, st, xi, early)
+
+    def _step_general_opt(self, bf, tr, batch_advance, st, xi, early):
+        """FusedLinearTrainer._step_general's forward and backward (library products and the unfused kernels where a shape needs them)."""
+        m, C, H1, F = bf.m, self.C, self.H1, self.F
+        both = early and C <= 48
+        x, r1 = bf.xs[xi], bf.r1
+        _, gb1, _, gb2, gW3, gb3 = self.grads
+        k = _launch
+        # ---- forward
+        if both:
+            torch.mm(self.W1, x.t(), out=r1.view(H1, m))
+            k(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
+              0, GATHER_SPLIT, 8, _stream())
+        else:
+            torch.addmm(self.b1, x, self.W1.t(), out=r1)
+            if early:       # (n_clusters > 48: ALL of the next batch's tiles ride in the mid-forward launch)
+                k(_L.idl_mid_fwd_gather, _p(r1), None, 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]), 0, 8, 8, _stream())
+            elif m % 16 == 0:
+                k(_L.idl_mid_fwd, _p(r1), *self._mid_fwd_args(bf, tr), _stream())
+            else:
+                k(_L.idl_relu_dropout_fwd, _p(r1), r1.numel(), tr, self.seed, _p(self.ctl), 1, _stream())
+                torch.addmm(self.b2, r1, self.W2.t(), out=bf.lat)
+                k(_L.idl_head_fwd, _p(bf.lat), _p(self.W3), _p(self.b3), m, C, tr, self.seed, _p(self.ctl), _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
+                  _stream())
+        # (48 < n_clusters <= 200 with the fused InfoNCE kernels: the joint rides in InfoNCE pass 1 and the IIC core writes z dP0 -- two launches
+        #  and one library product fewer than joint + core + z dP0 as a GEMM)
+        dz = bf.nce_fused and 48 < C <= 200
+        launch_losses(k, bf, self.lamb, self.weight, self.out, dz=dz)
+        # ---- backward
+        adv_ctl, adv = (_p(self.ctl), batch_advance) if (st is not None and not early) else (None, 0)
+        nce_coef = (1.0 - self.weight) / (m * TEMPERATURE)
+        if both:
+            k(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, gW3), *self._next_batch(st, m), _p(bf.xs[1 - xi]), GATHER_SPLIT, 8, 8, 1, _stream())
+        elif C <= 48:
+            k(_L.idl_mid_bwd, *self._mid_bwd_args(bf, tr, r1, gW3), adv_ctl, adv, _stream())
+        else:
+            if dz or C > 64:
+                if not dz:
+                    torch.mm(bf.z, bf.P0, out=bf.dzs)
+                k(_L.idl_head_bwd_dz, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.dzs), _p(self.W3), m, C, tr,
+                  nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream())
+            else:
+                k(_L.idl_head_bwd, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), m, C, tr,
+                  nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream())
+            torch.mm(bf.dlogits.t(), bf.r2, out=gW3)
+            torch.mm(bf.dlat, self.W2, out=bf.dr1)
+            k(_L.idl_bias_grads, _p(bf.dr1), _p(r1), H1, _p(gb1), _p(bf.dlat), self.H2, _p(gb2), _p(bf.dlogits), C, _p(gb3),
+              m, tr, adv_ctl, adv, None, None, _stream())
+        # ---- dW1, then the optimizer (dW2 inside its launch)
+        self._dw1(bf, x)
+        if early:
+            self._opt(bf, r1, int(both), m // 2)
+        elif st is not None:        # the offset moved mid-step: the last launch assembles the next batch into bf.x
+            self._opt(bf, r1, 0, 0, gather=(_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs, m // 2, _p(st.mean), _p(st.scale),
+                                            _p(st.inv_scale), _p(bf.x)))
+        else:
+            self._opt(bf, r1, 0, batch_advance)
+
+    # ------------------------------------------------------------------ one epoch over the store
+    @torch.no_grad()
+    def run_epoch(self, store, batch_sz, use_graph=True, generator=None):
+        """One pass over a fresh permutation of the N*n_mimics pairs (models.py:117-133) -> (device scalar sum of the step losses,
+        number of batches).  Full batches replay a captured graph of an even number of steps; what does not fill a replay and the partial
+        last batch run eagerly."""
+        if store.f != self.F:
+            raise ValueError(f"the feature store has {store.f} features a row, the network {self.F}")
+        n_pairs = store.n_pairs
+        if self._perm is None or self._perm.numel() != n_pairs:
+            self._perm = torch.empty(n_pairs, dtype=torch.int64, device=self.dev)
+            self._graphs.clear()
+        torch.randperm(n_pairs, device=self.dev, generator=generator, out=self._perm)
+        self.ctl[1:2].zero_()
+        self.out[1:2].zero_()
+        n_full, rem = divmod(n_pairs, batch_sz)
+        if n_full:
+            bf = self.buffers(2 * batch_sz)
+            self._gather(store, bf)             # batch 0; every later one is assembled by the step before it
+            done = 0
+            if use_graph and n_full >= 4:
+                per = min(STEPS_PER_GRAPH, (n_full - 2) // 2 * 2)
+                # every address the captured launches bake in is part of the key, and so is the role of the two step words
+                base = (2 * batch_sz, store.feats.data_ptr(), store.mean.data_ptr(), store.scale.data_ptr(), store.inv_scale.data_ptr(),
+                        self._perm.data_ptr(), store.n, store.f, store.n_pairs, per)
+                key = base + (self._tpar,)
+                g = self._graphs.get(key)
+                if g is None:
+                    for i in range(2):           # (two real steps first: whatever a library product sets up lazily happens outside the capture)
+                        self._full_step(store, bf, pipelined=True, xi=i)
+                    done = 2
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        for i in range(per):
+                            self._full_step(store, bf, pipelined=True, xi=i % 2)
+                    self._graphs = {k_: v for k_, v in self._graphs.items() if k_[:-1] == base}      # one store at a time
+                    self._graphs[key] = g
+                    self.n_captures = getattr(self, "n_captures", 0) + 1
+                reps = (n_full - done) // per
+                for _ in range(reps):
+                    g.replay()
+                done += reps * per
+            for i in range(done, n_full):
+                self._full_step(store, bf, pipelined=True, xi=i % 2)
+        if rem:
+            self._full_step(store, self.buffers(2 * rem))
+        return self.out[1], n_full + (1 if rem else 0)

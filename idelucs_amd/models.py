@@ -109,6 +109,10 @@ class IID_model():
         # model_size='small': autograd (the default) or, opt-in, the explicit step of fused_small.FusedSmallTrainer
         self._small = None
         self._use_small = args['model_size'] == 'small' and self._small_step(args) == 'native'
+        # NetLinear with SGD or Adam: autograd (the default) or, opt-in, the explicit step of fused_opt.FusedLinearOptTrainer
+        self._linopt = None
+        self._use_linopt = (args['model_size'] == 'linear' and args['optimizer'] in ('SGD', 'Adam')
+                            and self._linear_step(args) == 'native')
 
     @staticmethod
     def _small_step(args):
@@ -120,6 +124,17 @@ class IID_model():
         if mode == 'native' and (args['optimizer'] != 'RMSprop' or not 1 <= args['n_clusters'] <= 256 or not 1 <= args['batch_sz'] <= 1024):
             raise ValueError("small_step='native' supports optimizer='RMSprop', n_clusters in 1..256 and batch_sz in 1..1024 "
                              f"(got optimizer={args['optimizer']!r}, n_clusters={args['n_clusters']}, batch_sz={args['batch_sz']})")
+        return mode
+
+    @staticmethod
+    def _linear_step(args):
+        """args['linear_step'] of a model_size='linear' model trained with SGD or Adam: 'autograd' (absent or None) or 'native'
+        (n_clusters <= 256); anything else raises ValueError.  (RMSprop's step is native already: the key is not looked at.)"""
+        mode = args.get('linear_step') or 'autograd'
+        if mode not in ('autograd', 'native'):
+            raise ValueError(f"linear_step must be 'autograd' or 'native', not {mode!r}")
+        if mode == 'native' and not 1 <= args['n_clusters'] <= 256:
+            raise ValueError(f"linear_step='native' supports n_clusters in 1..256 (got n_clusters={args['n_clusters']})")
         return mode
 
     def _make_scheduler(self):
@@ -186,6 +201,8 @@ class IID_model():
             self._fused.begin_voter(self._voter, keep_state=carry)
         if self._small is not None:
             self._small.begin_voter(self._voter, keep_state=carry)
+        if self._linopt is not None:
+            self._linopt.begin_voter(self._voter, keep_state=carry)
 
     def _step(self, x):
         """One optimizer step on a [2b, F] batch (rows [0,b) "true", [b,2b) "modified")."""
@@ -225,6 +242,17 @@ class IID_model():
                 self._small.begin_voter(self._voter)
             self._small.set_lr(self.optimizer.param_groups[0]['lr'])       # schedulers act on the torch optimizer
             total, n_batches = self._small.run_epoch(st, self.batch_sz, generator=self._gen)
+            return total / (n_batches - 1)                                  # models.py:135 quirk (divide by last index)
+        if self._use_linopt:
+            if self._linopt is None:
+                from . import gemm_tuning
+                from .fused_opt import FusedLinearOptTrainer
+                n_batches = (st.n_pairs + self.batch_sz - 1) // self.batch_sz
+                gemm_tuning.maybe_enable(n_batches * self.n_epochs * self.n_voters)
+                self._linopt = FusedLinearOptTrainer(self.net, self.optimizer, self.weight, self.l, seed=self.seed)
+                self._linopt.begin_voter(self._voter)
+            self._linopt.sync_hyper()                                       # schedulers act on the torch optimizer: rate, momentum / beta1
+            total, n_batches = self._linopt.run_epoch(st, self.batch_sz, generator=self._gen)
             return total / (n_batches - 1)                                  # models.py:135 quirk (divide by last index)
         running_loss = torch.zeros((), device=self.device)
         perm = torch.randperm(st.n_pairs, device=self.device, generator=self._gen)
