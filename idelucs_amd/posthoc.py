@@ -107,10 +107,10 @@ def label_features_device(predictions, n_clusters, device=None, n_init=10, max_i
 SILHOUETTE_HOST_MAX = 20000      # above this many points the silhouette is computed on the GPU (sklearn's is O(N^2) on the host)
 
 
-def _silhouette_from_sums(sums, own, counts):
-    """mean over the points of (b - a) / max(a, b) from the per-cluster distance sums [n, K] (float64), the points' own clusters
-    and the cluster sizes: a = mean distance to the rest of the own cluster, b = smallest mean distance to another cluster;
-    singletons score 0 (sklearn)."""
+def _silhouette_points_from_sums(sums, own, counts):
+    """(b - a) / max(a, b) of every point from the per-cluster distance sums [n, K] (float64), the points' own clusters and the
+    cluster sizes: a = mean distance to the rest of the own cluster, b = smallest mean distance to another cluster; singletons
+    score 0 (sklearn).  (`sums` is overwritten.)"""
     import torch
     n_own = counts[own]
     a = sums.gather(1, own[:, None]).squeeze(1) / (n_own - 1.0).clamp_min(1.0)
@@ -119,14 +119,19 @@ def _silhouette_from_sums(sums, own, counts):
     b = means.min(1).values
     sil = (b - a) / torch.maximum(a, b)
     sil = torch.where(n_own > 1.0, sil, torch.zeros_like(sil))
-    return torch.nan_to_num(sil).sum()
+    return torch.nan_to_num(sil)
 
 
-def _silhouette_one_pass(x, lab, k, dev):
+def _silhouette_from_sums(sums, own, counts):
+    """Sum over the points of _silhouette_points_from_sums."""
+    return _silhouette_points_from_sums(sums, own, counts).sum()
+
+
+def _silhouette_one_pass_points(x, lab, k, dev):
     """The per-cluster distance sums by idl_silhouette_sums (csrc/knn.hip): the points cluster by cluster, every cluster padded to
     whole 64-row waves (weight 0; the padding repeats a point of the cluster: a wave centres its coordinates on its first row, and
     a wave that straddled two tight far-apart clusters would lose the second one's distances to rounding), one MFMA pass over
-    all pairs.  -> sum over the points of their silhouette (float64 device scalar)."""
+    all pairs.  -> (every point's silhouette, float64, the points sorted by cluster; the permutation that sorted them)."""
     import ctypes
     import torch
     from . import _lib
@@ -150,19 +155,19 @@ def _silhouette_one_pass(x, lab, k, dev):
     vp = ctypes.c_void_p
     _lib.check(_lib.lib.idl_silhouette_sums(vp(xp.data_ptr()), vp(w.data_ptr()), vp(tile_cluster.data_ptr()), npad, 64, k, vp(sums.data_ptr()),
                                             vp(torch.cuda.current_stream().cuda_stream)))
-    return _silhouette_from_sums(sums[pos].double(), lab_s, counts.double())
+    return _silhouette_points_from_sums(sums[pos].double(), lab_s, counts.double()), order
+
+
+def _silhouette_one_pass(x, lab, k, dev):
+    """Sum over the points of their silhouette (float64 device scalar), added up in _silhouette_one_pass_points' order."""
+    return _silhouette_one_pass_points(x, lab, k, dev)[0].sum()
 
 
 SILHOUETTE_ONE_PASS_MIN = 4096   # points from which 64-dimensional data take the one-pass kernel
 
 
-def silhouette_score_device(data, labels, device=None, block=4096):
-    """sklearn.metrics.silhouette_score(data, labels) (euclidean, mean over all samples) on the GPU.  64-dimensional data (the
-    latent) from SILHOUETTE_ONE_PASS_MIN points: one pass over all pairs on the fp32 matrix cores that adds every point's distances
-    up per cluster in registers (_silhouette_one_pass; 10^6 points: 2 s).  Otherwise ($IDELUCS_DEV=silhouette=gemm forces it): for a
-    block of rows the distances to every point come from one GEMM (||x||^2 + ||y||^2 - 2 x.y, clamped, square-rooted) and their
-    per-cluster sums from a second GEMM with the one-hot label matrix (10 s at 10^6 points: five elementwise passes over 4 TB).
-    float64 from the per-cluster sums on; agrees with sklearn to ~1e-6 (tests/test_cli_surface.py)."""
+def _silhouette_inputs(data, labels, device):
+    """(x float32 [n, d] on the device, lab int64 [n] in 0 .. k - 1, k, device, whether the one-pass kernel takes these points)."""
     import torch
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     x = torch.as_tensor(np.asarray(data)).to(dev, torch.float32)
@@ -171,14 +176,19 @@ def silhouette_score_device(data, labels, device=None, block=4096):
     if not 2 <= k <= n - 1:
         raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % k)      # sklearn's check
     lab = torch.from_numpy(inv.astype(np.int64)).to(dev)
-    if x.shape[1] == 64 and n >= SILHOUETTE_ONE_PASS_MIN and OPTIONS["silhouette"] != "gemm":
-        return float(_silhouette_one_pass(x, lab, k, dev).item() / n)
+    one_pass = x.shape[1] == 64 and n >= SILHOUETTE_ONE_PASS_MIN and OPTIONS["silhouette"] != "gemm"
+    return x, lab, k, dev, one_pass
+
+
+def _silhouette_gemm_blocks(x, lab, k, dev, block):
+    """The GEMM form: yields the silhouettes (float64) of the points of one row block after the other, in the caller's order."""
+    import torch
+    n = x.shape[0]
     onehot = torch.zeros((n, k), dtype=torch.float32, device=dev)
     onehot[torch.arange(n, device=dev), lab] = 1.0
     counts = onehot.sum(0).double()
     x = x - x.mean(0, keepdim=True)                 # distances are translation invariant; centring keeps the cancellation small
     x2 = (x * x).sum(1)
-    total = torch.zeros((), dtype=torch.float64, device=dev)
     block = max(64, min(block, (1 << 32) // max(n, 1)))        # one [block, n] float32 buffer (<= 16 GB), reused by every block
     buf = torch.empty((min(block, n), n), dtype=torch.float32, device=dev)
     xt = x.t()
@@ -189,8 +199,45 @@ def silhouette_score_device(data, labels, device=None, block=4096):
         d2.mul_(-2.0).add_(x2[lo:hi, None]).add_(x2[None, :]).clamp_min_(0.0)
         d2[torch.arange(hi - lo, device=dev), torch.arange(lo, hi, device=dev)] = 0.0       # exact zeros on the diagonal
         sums = (d2.sqrt_() @ onehot).double()                                                # [rows, K]: sum of distances to each cluster
-        total += _silhouette_from_sums(sums, lab[lo:hi], counts)
+        yield _silhouette_points_from_sums(sums, lab[lo:hi], counts)
+
+
+def silhouette_score_device(data, labels, device=None, block=4096):
+    """sklearn.metrics.silhouette_score(data, labels) (euclidean, mean over all samples) on the GPU.  64-dimensional data (the
+    latent) from SILHOUETTE_ONE_PASS_MIN points: one pass over all pairs on the fp32 matrix cores that adds every point's distances
+    up per cluster in registers (_silhouette_one_pass; 10^6 points: 2 s).  Otherwise ($IDELUCS_DEV=silhouette=gemm forces it): for a
+    block of rows the distances to every point come from one GEMM (||x||^2 + ||y||^2 - 2 x.y, clamped, square-rooted) and their
+    per-cluster sums from a second GEMM with the one-hot label matrix (10 s at 10^6 points: five elementwise passes over 4 TB).
+    float64 from the per-cluster sums on.  Against sklearn (tests/test_gpu_silhouette.py, every point inside an a-priori rounding
+    bound; DESIGN.md section 7 has the table), in a float32 CPU replay of the kernel's arithmetic, not yet measured on a GPU: on
+    blobs, tight far-apart blobs, blobs 300 from the origin, K = 2, singletons and blobs cut in two every point within 4e-7 and
+    the score within 1e-9; with half of the points exact copies of others within 7e-6 per point (score 1.3e-7); with a wide
+    cluster among tight ones (a third of the points just outside tight blobs under one label, HDBSCAN's -1) a point can be off
+    by 2e-4 -- a wave of 64 rows of the wide cluster centres far from most of them -- and the score by 7e-6, inside its 2e-5."""
+    import torch
+    x, lab, k, dev, one_pass = _silhouette_inputs(data, labels, device)
+    n = x.shape[0]
+    if one_pass:
+        return float(_silhouette_one_pass(x, lab, k, dev).item() / n)
+    total = torch.zeros((), dtype=torch.float64, device=dev)
+    for sil in _silhouette_gemm_blocks(x, lab, k, dev, block):
+        total += sil.sum()
     return float(total.item() / n)
+
+
+def silhouette_samples_device(data, labels, device=None, block=4096):
+    """sklearn.metrics.silhouette_samples(data, labels) (euclidean) on the GPU: every point's silhouette, float64 numpy in the
+    caller's point order, by the path silhouette_score_device takes for the same input (whose score is the mean of these, added
+    up in another order)."""
+    import torch
+    x, lab, k, dev, one_pass = _silhouette_inputs(data, labels, device)
+    if one_pass:
+        sil, order = _silhouette_one_pass_points(x, lab, k, dev)
+        out = torch.empty_like(sil)
+        out[order] = sil
+    else:
+        out = torch.cat(list(_silhouette_gemm_blocks(x, lab, k, dev, block)))
+    return out.cpu().numpy()
 
 
 def compute_results(y_pred, data, y_true=None):
