@@ -152,6 +152,8 @@ SIGNATURES = {
                                  _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "idl_small_wgrad_rms": (_int, [_vp] * 5 + [_vp] * 8 + [_int, _int, _int, _vp, _c.c_float, _c.c_float, _vp,
                                    _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "idl_small_wgrad_rms_momentum": (_int, [_vp] * 6 + [_vp] * 8 + [_int, _int, _int, _vp, _c.c_float, _c.c_float, _vp,
+                                            _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "idl_opt_step_gather_wgrad": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp,
                                          _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
                                          _int, _vp, _vp, _int, _int, _int, _int, _vp, _i64, _vp]),

@@ -1,5 +1,6 @@
-// opt_step.hip -- the last launch of a NetLinear training step whose optimizer is SGD with momentum or Adam (reference
-// idelucs/models.py:89-92, stepped at models.py:131-132): idl_opt_step_gather_wgrad, the counterpart of idl_rmsprop_step_gather_wgrad
+// opt_step.hip -- the last launch of a NetLinear training step whose optimizer is SGD with momentum, Adam (reference
+// idelucs/models.py:89-92, stepped at models.py:131-132) or RMSprop with the momentum buffer that CyclicLR's cycle_momentum gives it
+// (models.py:87-88 under models.py:99): idl_opt_step_gather_wgrad, the counterpart of idl_rmsprop_step_gather_wgrad
 // (train_step.hip) with the optimizer generalised.  The forward, the backward and the loss launches in front of it do not know
 // which optimizer follows them; this file is where the two enter the step.
 //
@@ -12,7 +13,7 @@
 //                   partials summed in ascending order
 // Nothing is accumulated with atomics: every sum runs in a fixed order, a replayed step equals the eager one bit for bit.
 //
-// Hyperparameters are a DEVICE double[5] = {lr, momentum | beta1, beta2, eps, weight_decay}: a captured graph follows what a
+// Hyperparameters are a DEVICE double[5] = {lr, momentum | beta1, beta2 | alpha, eps, weight_decay}: a captured graph follows what a
 // scheduler changed between epochs, and Adam's bias corrections 1 - beta^t are formed in double as torch forms them on the host
 // (an fp32 1 - 0.999^t is 3e-5 off at t = 1, which a bias tensor that starts at zero shows in full).
 // Adam's step count is the optimizer's own (not ctl[0], the dropout counter, which restarts with every voter): every workgroup
@@ -33,7 +34,7 @@ constexpr int OPT_THREADS = 256;
 constexpr int OPT_UNROLL = 4;          // 16-byte elements per thread of the streaming update
 constexpr int OPT_MAX_BLOCKS = 1024;   // optimizer blocks of one tensor (beyond: a block walks on)
 constexpr int PART_CHUNK = 16;         // stacked partial gradients requested together
-constexpr int KIND_SGD = 1, KIND_ADAM = 2;
+constexpr int KIND_SGD = 1, KIND_ADAM = 2, KIND_RMSPROP = 3;
 
 struct OptArgs {
     const float *loss_rows;   // optional step-loss assembly (models.py:128), as idl_rmsprop_step
@@ -42,8 +43,8 @@ struct OptArgs {
     float w_nce, w_iic;
     float *p[8];
     const float *g[8];
-    float *s1[8];             // SGD: momentum_buffer; Adam: exp_avg
-    float *s2[8];             // Adam: exp_avg_sq
+    float *s1[8];             // SGD: momentum_buffer; Adam: exp_avg; RMSprop: square_avg
+    float *s2[8];             // Adam: exp_avg_sq; RMSprop: momentum_buffer
     int64_t n[8];
     int parts[8];             // g[t] holds parts[t] stacked partial gradients [parts, n]
     int count;
@@ -60,7 +61,7 @@ struct OptArgs {
 // What one step's update needs, in the precision torch's kernels see it: the host-side Python floats rounded to fp32.
 template <int KIND>
 struct Coef {
-    float lr, mu, wd;                             // SGD
+    float lr, mu, wd;                             // SGD; RMSprop: these and eps, b2 = alpha, b2w = 1 - alpha
     float step, bc2s, eps, b1w, b2, b2w;          // Adam: lr / bc1, sqrt(bc2), eps, 1 - beta1, beta2, 1 - beta2
 };
 
@@ -83,6 +84,8 @@ __device__ __forceinline__ Coef<KIND> make_coef(const OptArgs &a)
     c.wd = (float)wd;
     if constexpr (KIND == KIND_SGD) {
         c.lr = (float)lr; c.mu = (float)h1;
+    } else if constexpr (KIND == KIND_RMSPROP) {
+        c.lr = (float)lr; c.mu = (float)h1; c.eps = (float)eps; c.b2 = (float)h2; c.b2w = (float)(1.0 - h2);
     } else {
         const int64_t t = *a.step_in + 1;
         const double bc1 = 1.0 - pow_int(h1, t), bc2 = 1.0 - pow_int(h2, t);
@@ -94,7 +97,8 @@ __device__ __forceinline__ Coef<KIND> make_coef(const OptArgs &a)
 
 // torch.optim.SGD (momentum, weight decay; dampening 0, no nesterov): g' = g + wd p; buf = mu buf + g'; p -= lr buf -- a zero buf
 // makes the first step buf = g', torch's clone.  torch.optim.Adam (no amsgrad): m.lerp_(g, 1 - b1); v = b2 v + (1 - b2) g g;
-// p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).
+// p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).  torch.optim.RMSprop (not centered) with a momentum buffer: v = alpha v + (1 - alpha) g' g';
+// avg = sqrt(v) + eps; buf = mu buf + g' / avg; p -= lr buf (s1 = v, s2 = buf) -- mu = 0 makes buf = g' / avg, torch's addcdiv_ form.
 template <int KIND>
 __device__ __forceinline__ void opt_update(float g, float &p, float &s1, float &s2, const Coef<KIND> &c)
 {
@@ -102,6 +106,11 @@ __device__ __forceinline__ void opt_update(float g, float &p, float &s1, float &
     if constexpr (KIND == KIND_SGD) {
         s1 = fmaf(c.mu, s1, g);
         p = fmaf(-c.lr, s1, p);
+    } else if constexpr (KIND == KIND_RMSPROP) {
+        s1 = fmaf(c.b2w * g, g, c.b2 * s1);
+        const float avg = sqrtf(s1) + c.eps;
+        s2 = fmaf(c.mu, s2, g / avg);
+        p = fmaf(-c.lr, s2, p);
     } else {
         const float d = g - s1;
         s1 = c.b1w < 0.5f ? fmaf(c.b1w, d, s1) : g - d * (1.0f - c.b1w);      // (Tensor.lerp_'s two forms)
@@ -167,7 +176,7 @@ __device__ __forceinline__ void wgrad_tile(const OptArgs &a, int tile, const Coe
     }
     const int o = (i0 + (tid >> 4)) * ldb + j0 + (tid & 15);      // this thread's element of the tile in the epilogue
     float *p = a.p[a.wg_t], *s1 = a.s1[a.wg_t], *s2 = a.s2[a.wg_t];
-    float pi = p[o], ai = s1[o], bi = KIND == KIND_ADAM ? s2[o] : 0.f;      // (requested before the barrier: beside the LDS round trip)
+    float pi = p[o], ai = s1[o], bi = KIND != KIND_SGD ? s2[o] : 0.f;      // (requested before the barrier: beside the LDS round trip)
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[wv * 256 + (4 * q + r) * 16 + l] = acc[r];          // C/D: row = 4 q + reg, col = l
     __syncthreads();
@@ -175,7 +184,7 @@ __device__ __forceinline__ void wgrad_tile(const OptArgs &a, int tile, const Coe
     if (a.wg_grad != nullptr) a.wg_grad[o] = g;
     opt_update<KIND>(g, pi, ai, bi, c);
     s1[o] = ai;
-    if constexpr (KIND == KIND_ADAM) s2[o] = bi;
+    if constexpr (KIND != KIND_SGD) s2[o] = bi;
     p[o] = pi;
 }
 
@@ -203,7 +212,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(OptArgs a, int n_
     if (gx > 0) {
         float *p = a.p[t]; const float *gr = a.g[t]; float *s1 = a.s1[t]; float *s2 = a.s2[t];
         const int64_t n = a.n[t];
-        const uintptr_t al = ((uintptr_t)p) | ((uintptr_t)gr) | ((uintptr_t)s1) | (KIND == KIND_ADAM ? (uintptr_t)s2 : 0);
+        const uintptr_t al = ((uintptr_t)p) | ((uintptr_t)gr) | ((uintptr_t)s1) | (KIND != KIND_SGD ? (uintptr_t)s2 : 0);
         if (a.parts[t] == 1 && (n & 3) == 0 && (al & 15u) == 0) {
             float4 *p4 = (float4 *)p; const float4 *g4 = (const float4 *)gr; float4 *a4 = (float4 *)s1; float4 *b4 = (float4 *)s2;
             const int64_t n4 = n / 4, stride = (int64_t)gx * OPT_THREADS;
@@ -213,7 +222,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(OptArgs a, int n_
                 for (int u = 0; u < OPT_UNROLL; ++u) {
                     const int64_t iu = i + u * stride < n4 ? i + u * stride : i;        // clamped, not predicated: the loads stay unconditional
                     pv[u] = p4[iu]; gv[u] = g4[iu]; av[u] = a4[iu];
-                    if constexpr (KIND == KIND_ADAM) bv[u] = b4[iu]; else bv[u] = float4{0.f, 0.f, 0.f, 0.f};
+                    if constexpr (KIND != KIND_SGD) bv[u] = b4[iu]; else bv[u] = float4{0.f, 0.f, 0.f, 0.f};
                 }
 #pragma unroll
                 for (int u = 0; u < OPT_UNROLL; ++u) {
@@ -221,7 +230,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(OptArgs a, int n_
                         opt_update<KIND>(gv[u].x, pv[u].x, av[u].x, bv[u].x, c); opt_update<KIND>(gv[u].y, pv[u].y, av[u].y, bv[u].y, c);
                         opt_update<KIND>(gv[u].z, pv[u].z, av[u].z, bv[u].z, c); opt_update<KIND>(gv[u].w, pv[u].w, av[u].w, bv[u].w, c);
                         a4[i + u * stride] = av[u];
-                        if constexpr (KIND == KIND_ADAM) b4[i + u * stride] = bv[u];
+                        if constexpr (KIND != KIND_SGD) b4[i + u * stride] = bv[u];
                         p4[i + u * stride] = pv[u];
                     }
                 }
@@ -229,7 +238,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(OptArgs a, int n_
         } else {
             const int parts = a.parts[t];
             for (int64_t i = (int64_t)bx * OPT_THREADS + tix; i < n; i += (int64_t)gx * OPT_THREADS) {
-                float pi = p[i], ai = s1[i], bi = KIND == KIND_ADAM ? s2[i] : 0.f;
+                float pi = p[i], ai = s1[i], bi = KIND != KIND_SGD ? s2[i] : 0.f;
                 float sum = gr[i];
                 for (int q0 = 1; q0 < parts; q0 += PART_CHUNK) {      // PART_CHUNK independent loads in flight, added in ascending order
                     float part[PART_CHUNK];
@@ -240,7 +249,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(OptArgs a, int n_
                 }
                 opt_update<KIND>(sum, pi, ai, bi, c);
                 s1[i] = ai;
-                if constexpr (KIND == KIND_ADAM) s2[i] = bi;
+                if constexpr (KIND != KIND_SGD) s2[i] = bi;
                 p[i] = pi;
             }
         }
@@ -280,9 +289,9 @@ int idl_opt_step_gather_wgrad(int kind, int count, float *const *params, const f
                               int wg_index, const float *wg_dy, const float *wg_x, int wg_x_transposed, int wg_m, int wg_n_out, int wg_n_in,
                               float *wg_grad, int64_t batch_advance, void *stream)
 {
-    IDL_REQUIRE(kind == KIND_SGD || kind == KIND_ADAM, "opt_step: kind 1 (SGD with momentum) or 2 (Adam)");
+    IDL_REQUIRE(kind == KIND_SGD || kind == KIND_ADAM || kind == KIND_RMSPROP, "opt_step: kind 1 (SGD with momentum), 2 (Adam) or 3 (RMSprop with momentum)");
     IDL_REQUIRE(count >= 1 && count <= 8 && params && grads && state1 && sizes && hyper && ctl, "opt_step: 1..8 tensors");
-    IDL_REQUIRE(kind != KIND_ADAM || state2 != nullptr, "opt_step: Adam needs exp_avg_sq (state2)");
+    IDL_REQUIRE(kind == KIND_SGD || state2 != nullptr, "opt_step: Adam needs exp_avg_sq, RMSprop momentum_buffer (state2)");
     IDL_REQUIRE(step_in && step_out && step_in != step_out, "opt_step: the step count is read from one word and written to another");
     IDL_REQUIRE((const void *)step_in != (const void *)ctl && (const void *)step_in != (const void *)(ctl + 1),
                 "opt_step: step_in must not be a word this launch writes");
@@ -293,10 +302,10 @@ int idl_opt_step_gather_wgrad(int kind, int count, float *const *params, const f
     a.loss_rows = loss_rows; a.out = loss_rows != nullptr ? out : nullptr; a.loss_m = loss_m; a.w_nce = w_nce; a.w_iic = w_iic;
     a.hyper = hyper; a.step_in = step_in; a.step_out = step_out; a.ctl = ctl; a.batch_advance = batch_advance;
     for (int i = 0; i < count; ++i) {
-        a.p[i] = params[i]; a.g[i] = grads[i]; a.s1[i] = state1[i]; a.s2[i] = kind == KIND_ADAM ? state2[i] : nullptr; a.n[i] = sizes[i];
+        a.p[i] = params[i]; a.g[i] = grads[i]; a.s1[i] = state1[i]; a.s2[i] = kind != KIND_SGD ? state2[i] : nullptr; a.n[i] = sizes[i];
         a.parts[i] = grad_parts ? grad_parts[i] : 1;
         IDL_REQUIRE(a.parts[i] >= 1 && sizes[i] >= 0, "opt_step: grad_parts must be >= 1, sizes >= 0");
-        IDL_REQUIRE(sizes[i] == 0 || (a.p[i] && a.s1[i] && (kind != KIND_ADAM || a.s2[i])), "opt_step: a tensor without its parameter or state pointer");
+        IDL_REQUIRE(sizes[i] == 0 || (a.p[i] && a.s1[i] && (kind == KIND_SGD || a.s2[i])), "opt_step: a tensor without its parameter or state pointer");
         IDL_REQUIRE(sizes[i] == 0 || i == wg_index || a.g[i], "opt_step: a tensor without its gradient");
     }
     if (wg_index >= 0) {
@@ -331,7 +340,8 @@ int idl_opt_step_gather_wgrad(int kind, int count, float *const *params, const f
     IDL_REQUIRE(extra + nb_total + a.wg_tiles < (1ll << 30), "opt_step: grid too large");
     const dim3 grid((unsigned)(a.wg_tiles + extra + nb_total)), block(OPT_THREADS);
     if (kind == KIND_SGD) hipLaunchKernelGGL(opt_step_kernel<KIND_SGD>, grid, block, 0, (hipStream_t)stream, a, (int)extra, g);
-    else hipLaunchKernelGGL(opt_step_kernel<KIND_ADAM>, grid, block, 0, (hipStream_t)stream, a, (int)extra, g);
+    else if (kind == KIND_ADAM) hipLaunchKernelGGL(opt_step_kernel<KIND_ADAM>, grid, block, 0, (hipStream_t)stream, a, (int)extra, g);
+    else hipLaunchKernelGGL(opt_step_kernel<KIND_RMSPROP>, grid, block, 0, (hipStream_t)stream, a, (int)extra, g);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }

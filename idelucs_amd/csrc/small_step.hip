@@ -14,6 +14,8 @@
 //   small_wgrad_rms   every weight gradient as A^T B tiles with the RMSprop update in their epilogue (the gradient stays in registers),
 //                     the four bias gradients as column sums with the update behind them, the step loss and step counter, and the
 //                     assembly of the NEXT batch into the other x buffer
+//                     (small_wgrad_rms_momentum: the same launch with torch's momentum buffer in the update, for RMSprop under
+//                     CyclicLR's cycle_momentum)
 //
 // Dropout: Philox4x32-10 keyed by the seed, counter (element group, layer, ctl[0]).  Layer ids 11 (after layer 1) and 12 (classifier)
 // are distinct from NetLinear's 1 and 2.  The layer-1 mask is recovered in the backward from the sign of a1 (kept and active <=> a1 > 0,
@@ -420,7 +422,19 @@ __device__ __forceinline__ void rms(float g, float &p, float &v, const float *h)
     p = p - h[0] * (gi / (sqrtf(v) + h[2]));          // param.addcdiv_(grad, sqrt(v)+eps, value=-lr)
 }
 
-__device__ __forceinline__ void grad_tile(const GradJob &j, int t, int m, const float *hyper, float *lds)
+// RMSprop with the momentum buffer that CyclicLR's cycle_momentum gives the optimizer (models.py:87-88 under models.py:99): torch's order,
+// buf = mu buf + g / (sqrt(v) + eps); p -= lr buf, mu = h[5] (mu = 0: buf = g / avg, the momentum-free step)
+__device__ __forceinline__ void rms_momentum(float g, float &p, float &v, float &buf, const float *h)
+{
+    const float gi = g + h[3] * p;
+    v = v * h[1] + h[4] * gi * gi;
+    buf = buf * h[5] + gi / (sqrtf(v) + h[2]);        // buf.mul_(momentum).addcdiv_(grad, avg)
+    p = p - h[0] * buf;                               // param.add_(buf, alpha=-lr)
+}
+
+// (MOM: the momentum form, buf = the tensor's momentum_buffer; the momentum-free instantiation is the code it was before the template)
+template <bool MOM>
+__device__ __forceinline__ void grad_tile(const GradJob &j, int t, int m, const float *hyper, float *lds, float *buf)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l = lane & 15, q = lane >> 4;
     const int i0 = (t / j.tiles_n) * WG_TM, j0 = (t % j.tiles_n) * WG_TN;
@@ -484,13 +498,20 @@ __device__ __forceinline__ void grad_tile(const GradJob &j, int t, int m, const 
                     const int64_t e = (int64_t)i * j.N + jj;
                     if (j.grad != nullptr) j.grad[e] = g;
                     float p = j.W[e], v = j.v[e];
-                    rms(g, p, v, hyper);
+                    if constexpr (MOM) {
+                        float bu = buf[e];
+                        rms_momentum(g, p, v, bu, hyper);
+                        buf[e] = bu;
+                    } else {
+                        rms(g, p, v, hyper);
+                    }
                     j.W[e] = p; j.v[e] = v;
                 }
             }
 }
 
-__device__ __forceinline__ void bias_cols(const BiasJob &j, int t, int m, const float *hyper, float *lds)
+template <bool MOM>
+__device__ __forceinline__ void bias_cols(const BiasJob &j, int t, int m, const float *hyper, float *lds, float *buf)
 {
     const int tid = threadIdx.x, c = tid & (BIAS_COLS - 1), rg = tid / BIAS_COLS;       // 8 row groups
     const int col = t * BIAS_COLS + c;
@@ -505,9 +526,17 @@ __device__ __forceinline__ void bias_cols(const BiasJob &j, int t, int m, const 
     for (int w = 1; w < WG_THREADS / BIAS_COLS; ++w) g += red[w][c];
     if (j.grad != nullptr) j.grad[col] = g;
     float p = j.b[col], v = j.v[col];
-    rms(g, p, v, hyper);
+    if constexpr (MOM) {
+        float bu = buf[col];
+        rms_momentum(g, p, v, bu, hyper);
+        buf[col] = bu;
+    } else {
+        rms(g, p, v, hyper);
+    }
     j.b[col] = p; j.v[col] = v;
 }
+
+struct MomBufs { float *g[4], *b[4]; };               // momentum_buffer of the four weights / the four biases
 
 __global__ __launch_bounds__(WG_THREADS) void small_wgrad_rms_kernel(SmallWgArgs a)
 {
@@ -516,12 +545,50 @@ __global__ __launch_bounds__(WG_THREADS) void small_wgrad_rms_kernel(SmallWgArgs
     int lo = 0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        if (bid < a.g_end[t]) { grad_tile(a.g[t], bid - lo, a.m, a.hyper, lds); return; }
+        if (bid < a.g_end[t]) { grad_tile<false>(a.g[t], bid - lo, a.m, a.hyper, lds, nullptr); return; }
         lo = a.g_end[t];
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        if (bid < a.b_end[t]) { bias_cols(a.b[t], bid - lo, a.m, a.hyper, lds); return; }
+        if (bid < a.b_end[t]) { bias_cols<false>(a.b[t], bid - lo, a.m, a.hyper, lds, nullptr); return; }
+        lo = a.b_end[t];
+    }
+    if (bid == a.loss_blk) {
+        if (threadIdx.x >= 64) return;
+        const int lane = threadIdx.x;
+        float s = 0.f;
+        if (a.loss_rows != nullptr)
+            for (int r = lane; r < a.m; r += 64) s += a.loss_rows[r];
+        s = idl_dev::wave_sum_f(s);
+        if (lane == 0) {
+            if (a.loss_rows != nullptr) {
+                const float nce = s / (float)a.m;
+                const float tot = a.w_nce * nce + a.w_iic * a.out[3];
+                a.out[2] = nce; a.out[0] = tot; a.out[1] += tot;
+            }
+            a.ctl[0] += 1;
+        }
+        return;
+    }
+    const int blk = 2 * (bid - a.loss_blk - 1) + (int)(threadIdx.x >> 8);
+    if (blk < a.gather_end) idl_dev::gather_block(a.gth, (int64_t)blk, (int)(threadIdx.x & 255));
+}
+
+// The momentum form of the launch above: the same grid and roles, one more stream (momentum_buffer) per tensor.  (A kernel of its own,
+// not a shared body taking the arguments by reference: that copies the argument block to scratch.)
+__global__ __launch_bounds__(WG_THREADS) void small_wgrad_momentum_kernel(SmallWgArgs a, MomBufs mb)
+{
+    __shared__ float lds[(WG_WAVES - 1) * WG_RB * WG_CB * 256];
+    const int bid = (int)blockIdx.x;
+    int lo = 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        if (bid < a.g_end[t]) { grad_tile<true>(a.g[t], bid - lo, a.m, a.hyper, lds, mb.g[t]); return; }
+        lo = a.g_end[t];
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        if (bid < a.b_end[t]) { bias_cols<true>(a.b[t], bid - lo, a.m, a.hyper, lds, mb.b[t]); return; }
         lo = a.b_end[t];
     }
     if (bid == a.loss_blk) {
@@ -595,12 +662,14 @@ int idl_small_mid_bwd(const float *z, const float *f, const float *inv, const fl
     return IDL_OK;
 }
 
-int idl_small_wgrad_rms(float *const *params, float *const *grads, float *const *square_avg, const float *hyper, int64_t *ctl,
-                        const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
-                        const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
-                        float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
-                        int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
-                        float *y_next, void *stream)
+// The two forms of the step's last launch share everything but the optimizer's epilogue: momentum_buffer == NULL is idl_small_wgrad_rms.
+static int small_wgrad_launch(float *const *params, float *const *grads, float *const *square_avg, float *const *momentum_buffer,
+                              const float *hyper, int64_t *ctl,
+                              const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
+                              const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
+                              float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
+                              int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
+                              float *y_next, void *stream)
 {
     IDL_REQUIRE(params && square_avg && hyper && ctl && x && dr1 && a1 && da2 && a2 && dh && d2 && dlogits, "NULL buffer");
     IDL_REQUIRE(m >= 1 && F >= 1 && C >= 1 && C <= SMAX_C, "small_wgrad_rms: m, F >= 1, n_clusters in 1..256");
@@ -634,9 +703,42 @@ int idl_small_wgrad_rms(float *const *params, float *const *grads, float *const 
         a.gather_end = (int)idl_dev::gather_blocks(f, gather_batch);
         end += (a.gather_end + 1) / 2;
     }
-    hipLaunchKernelGGL(small_wgrad_rms_kernel, dim3((unsigned)end), dim3(WG_THREADS), 0, (hipStream_t)stream, a);
+    if (momentum_buffer != nullptr) {
+        MomBufs mb{};
+        for (int t = 0; t < 4; ++t) {
+            IDL_REQUIRE(momentum_buffer[2 * t] && momentum_buffer[2 * t + 1], "small_wgrad_rms_momentum: NULL momentum buffer");
+            mb.g[t] = momentum_buffer[2 * t]; mb.b[t] = momentum_buffer[2 * t + 1];
+        }
+        hipLaunchKernelGGL(small_wgrad_momentum_kernel, dim3((unsigned)end), dim3(WG_THREADS), 0, (hipStream_t)stream, a, mb);
+    } else {
+        hipLaunchKernelGGL(small_wgrad_rms_kernel, dim3((unsigned)end), dim3(WG_THREADS), 0, (hipStream_t)stream, a);
+    }
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
+}
+
+int idl_small_wgrad_rms(float *const *params, float *const *grads, float *const *square_avg, const float *hyper, int64_t *ctl,
+                        const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
+                        const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
+                        float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
+                        int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
+                        float *y_next, void *stream)
+{
+    return small_wgrad_launch(params, grads, square_avg, nullptr, hyper, ctl, x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows, w_nce,
+                              w_iic, out, feats, n, f, view_stride, pair_idx, gather_batch, n_pairs, mean, scale, inv_scale, y_next, stream);
+}
+
+int idl_small_wgrad_rms_momentum(float *const *params, float *const *grads, float *const *square_avg, float *const *momentum_buffer,
+                                 const float *hyper, int64_t *ctl,
+                                 const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
+                                 const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
+                                 float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
+                                 int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
+                                 float *y_next, void *stream)
+{
+    IDL_REQUIRE(momentum_buffer != nullptr, "small_wgrad_rms_momentum: NULL momentum buffers");
+    return small_wgrad_launch(params, grads, square_avg, momentum_buffer, hyper, ctl, x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows,
+                              w_nce, w_iic, out, feats, n, f, view_stride, pair_idx, gather_batch, n_pairs, mean, scale, inv_scale, y_next, stream);
 }
 
 int idl_small_dropout_masks(uint64_t seed, int64_t step, int m, float *mask1, float *mask2, void *stream)

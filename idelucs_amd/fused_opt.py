@@ -1,6 +1,7 @@
 """idelucs_amd.fused_opt -- the explicit training step of NetLinear with torch.optim.SGD or torch.optim.Adam (reference
 idelucs/models.py:89-92) on this library's own kernels, replayed as a HIP graph.  Opt-in: IID_model(args) with
-args['linear_step'] = 'native' (CLI: --linear_step native).
+args['linear_step'] = 'native' (CLI: --linear_step native).  Also torch.optim.RMSprop WITH the momentum buffer that the Triangle
+scheduler's CyclicLR gives it (models.py:87-88, 99): args['rmsprop_momentum'] = 'follow' (CLI: --rmsprop_momentum follow).
 
 Nothing in the forward or backward of the fp32 step forms of fused.FusedLinearTrainer knows which optimizer follows, so a step here is
 those launches with the gradient-only dW1 tiles and ONE new last launch (csrc/opt_step.hip):
@@ -8,8 +9,8 @@ those launches with the gradient-only dW1 tiles and ONE new last launch (csrc/op
                          -> idl_opt_step_gather_wgrad (dW2 tiles, SGD / Adam on every tensor, step loss, counters)
     anything else        the choices of FusedLinearTrainer._step_general (library products for odd shapes and n_clusters > 48; at
                          48 < n_clusters <= 200 the IIC core writes z dP0 itself), dW1 on the tiles where they apply, the same last launch
-The next batch rides in the two middle launches where it does for RMSprop.  SGD keeps momentum_buffer per tensor, Adam exp_avg and
-exp_avg_sq plus its step count in two words that swap roles from step to step (the launch reads one and writes the other).  The
+The next batch rides in the two middle launches where it does for RMSprop.  SGD keeps momentum_buffer per tensor, RMSprop square_avg and
+momentum_buffer, Adam exp_avg and exp_avg_sq plus its step count in two words that swap roles from step to step (the launch reads one and writes the other).  The
 hyperparameters are copied from the torch optimizer's group before every epoch (sync_hyper): the schedulers keep acting on that
 object, CyclicLR on momentum / beta1 as well as the rate.
 """
@@ -21,20 +22,24 @@ from . import _lib
 from ._lib import lib as _L
 from .fused import GATHER_SPLIT, STEPS_PER_GRAPH, TEMPERATURE, _LinearStepParts, _launch, _p, _stream, launch_losses
 
-KIND_SGD, KIND_ADAM = 1, 2
+KIND_SGD, KIND_ADAM, KIND_RMSPROP = 1, 2, 3
 _NO_GATHER = (None, 0, 0, 0, None, 0, 0, None, None, None, None)
 
 
 class FusedLinearOptTrainer(_LinearStepParts):
     def __init__(self, net, optimizer, weight, lamb, seed=0):
-        """optimizer: the torch.optim.SGD / torch.optim.Adam object whose first group holds the hyperparameters (its state is not used)."""
+        """optimizer: the torch.optim.SGD / torch.optim.Adam / torch.optim.RMSprop object whose first group holds the hyperparameters (its state is not used)."""
         if isinstance(optimizer, torch.optim.SGD):
             self.kind = KIND_SGD
         elif isinstance(optimizer, torch.optim.Adam):
             self.kind = KIND_ADAM
+        elif isinstance(optimizer, torch.optim.RMSprop):
+            self.kind = KIND_RMSPROP
         else:
-            raise ValueError("FusedLinearOptTrainer needs a torch.optim.SGD or torch.optim.Adam object")
+            raise ValueError("FusedLinearOptTrainer needs a torch.optim.SGD, torch.optim.Adam or torch.optim.RMSprop object")
         grp = optimizer.param_groups[0]
+        if self.kind == KIND_RMSPROP and (grp.get('centered') or grp.get('maximize')):
+            raise ValueError("FusedLinearOptTrainer: centered and maximize are not supported with RMSprop")
         if grp.get('nesterov') or grp.get('dampening') or grp.get('amsgrad') or grp.get('maximize'):
             raise ValueError("FusedLinearOptTrainer: nesterov, dampening, amsgrad and maximize are not supported")
         lin1, lin2, lin3 = net.layers[0], net.layers[3], net.classifier[2]
@@ -55,9 +60,9 @@ class FusedLinearOptTrainer(_LinearStepParts):
         self.ctl = torch.zeros(2, dtype=torch.int64, device=self.dev)        # [dropout step counter, batch offset]
         self.out = torch.zeros(4, dtype=torch.float32, device=self.dev)      # [step loss, running sum, nce, iic]
         self._bufs, self._graphs, self._perm, self._shared_buffers = {}, {}, None, None
-        self.state1 = [torch.zeros_like(p) for p in self.params]             # SGD: momentum_buffer; Adam: exp_avg
-        self.state2 = [torch.zeros_like(p) for p in self.params] if self.kind == KIND_ADAM else []
-        self.hyper64 = torch.zeros(5, dtype=torch.float64, device=self.dev)      # [lr, momentum | beta1, beta2, eps, weight_decay]
+        self.state1 = [torch.zeros_like(p) for p in self.params]             # SGD: momentum_buffer; Adam: exp_avg; RMSprop: square_avg
+        self.state2 = [torch.zeros_like(p) for p in self.params] if self.kind != KIND_SGD else []      # Adam: exp_avg_sq; RMSprop: momentum_buffer
+        self.hyper64 = torch.zeros(5, dtype=torch.float64, device=self.dev)      # [lr, momentum | beta1, beta2 | alpha, eps, weight_decay]
         self._hyper_host = [None] * 5
         self.steps = torch.zeros(2, dtype=torch.int64, device=self.dev)          # the optimizer's step count: steps[_tpar] is current
         self._tpar = 0
@@ -94,6 +99,8 @@ class FusedLinearOptTrainer(_LinearStepParts):
         grp = self.optimizer.param_groups[0]
         if self.kind == KIND_SGD:
             vals = [grp['lr'], grp['momentum'], 0.0, 0.0, grp['weight_decay']]
+        elif self.kind == KIND_RMSPROP:
+            vals = [grp['lr'], grp['momentum'], grp['alpha'], grp['eps'], grp['weight_decay']]
         else:
             vals = [grp['lr'], grp['betas'][0], grp['betas'][1], grp['eps'], grp['weight_decay']]
         for i, v in enumerate(vals):

@@ -10,6 +10,9 @@ even number of steps (one stream, no forked branches); the steps that do not fil
 (the partial batch: the same kernels, and for an m that is not a multiple of 32 one library product for S = f f^T).
 
 The parameters are the nn.Parameters of model.net (state_dict / predict / weights_init unchanged); RMSprop state lives here.
+FusedSmallTrainer(..., momentum=mu) is the momentum form: torch's RMSprop with a momentum_buffer, which is what the Triangle
+scheduler's CyclicLR makes of the reference's optimizer (models.py:87-88, 99); its last launch is idl_small_wgrad_rms_momentum and
+set_momentum() follows the scheduler beside set_lr().
 """
 import ctypes
 
@@ -56,7 +59,8 @@ class _SmallBuffers:
 
 
 class FusedSmallTrainer:
-    def __init__(self, net, lr, weight, lamb, weight_decay=0.01, alpha=0.99, eps=1e-8, seed=0):
+    def __init__(self, net, lr, weight, lamb, weight_decay=0.01, alpha=0.99, eps=1e-8, seed=0, momentum=None):
+        """momentum: None -> the momentum-free step; a number -> the momentum form (momentum_buffer per tensor, set_momentum())."""
         lin1, lin2, lini, linc = net.layers[0], net.layers[3], net.instance, net.classifier[1]
         self.net = net
         self.params = [lin1.weight, lin1.bias, lin2.weight, lin2.bias, lini.weight, lini.bias, linc.weight, linc.bias]
@@ -68,7 +72,10 @@ class FusedSmallTrainer:
         self.grads = [torch.zeros_like(p) for p in self.params]
         self.square_avg = [torch.zeros_like(p) for p in self.params]
         self.weight, self.lamb, self.seed = float(weight), float(lamb), int(seed) & (2 ** 64 - 1)
-        self.hyper = torch.tensor([lr, alpha, eps, weight_decay, 1.0 - alpha], dtype=torch.float32, device=self.dev)
+        self.with_momentum = momentum is not None
+        self.momentum_buffer = [torch.zeros_like(p) for p in self.params] if self.with_momentum else []
+        self.hyper = torch.tensor([lr, alpha, eps, weight_decay, 1.0 - alpha] + ([float(momentum)] if self.with_momentum else []),
+                                  dtype=torch.float32, device=self.dev)
         self.ctl = torch.zeros(2, dtype=torch.int64, device=self.dev)        # [step counter, batch offset]
         self.out = torch.zeros(4, dtype=torch.float32, device=self.dev)      # [step loss, running sum, nce, iic]
         self._bufs = {}
@@ -77,6 +84,7 @@ class FusedSmallTrainer:
         n = len(self.params)
         self._pp = (ctypes.c_void_p * n)(*[p.data_ptr() for p in self.params])
         self._vp = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.square_avg])
+        self._mp = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.momentum_buffer]) if self.with_momentum else None
         self.keep_grads = False         # True: the step also writes dW1 to grads[0] (tests; the small tensors' gradients are always kept)
 
     def _gp(self):
@@ -90,11 +98,16 @@ class FusedSmallTrainer:
         self.ctl[0:1].fill_((int(voter) & 0xFF) << 24)
         if keep_state:
             return
-        for v in self.square_avg:
+        for v in self.square_avg + self.momentum_buffer:
             v.zero_()
 
     def set_lr(self, lr):
         self.hyper[0:1].fill_(float(lr))
+
+    def set_momentum(self, momentum):
+        if not self.with_momentum:
+            raise ValueError("this FusedSmallTrainer was built without a momentum buffer (momentum=None)")
+        self.hyper[5:6].fill_(float(momentum))
 
     def gradient(self, i):
         """Gradient of parameter i of the last step (i = 0, dW1: only when keep_grads was set before that step)."""
@@ -139,9 +152,12 @@ class FusedSmallTrainer:
         st = next_from
         gth = ((_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), m // 2, st.n_pairs, _p(st.mean), _p(st.scale), _p(st.inv_scale),
                 _p(bf.xs[1 - xi])) if st is not None else (None, 0, 0, 0, None, 0, 0, None, None, None, None))
-        chk(_L.idl_small_wgrad_rms(self._pp, self._gp(), self._vp, _p(self.hyper), _p(self.ctl), _p(x), _p(bf.dr1), _p(bf.a1), _p(bf.da2),
-                                   _p(bf.a2), _p(bf.dh), _p(bf.d2), _p(bf.dlogits), m, F, C, _p(bf.loss_rows), 1.0 - self.weight, self.weight,
-                                   _p(self.out), *gth, _stream()))
+        tail = (_p(self.hyper), _p(self.ctl), _p(x), _p(bf.dr1), _p(bf.a1), _p(bf.da2), _p(bf.a2), _p(bf.dh), _p(bf.d2), _p(bf.dlogits), m, F, C,
+                _p(bf.loss_rows), 1.0 - self.weight, self.weight, _p(self.out), *gth, _stream())
+        if self.with_momentum:
+            chk(_L.idl_small_wgrad_rms_momentum(self._pp, self._gp(), self._vp, self._mp, *tail))
+        else:
+            chk(_L.idl_small_wgrad_rms(self._pp, self._gp(), self._vp, *tail))
 
     def _gather(self, store, bf, b):
         _lib.check(_L.idl_gather_pairs_at(_p(store.feats), store.n, store.f, store.n * store.f, _p(self._perm), _p(self.ctl[1:]),

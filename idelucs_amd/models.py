@@ -97,6 +97,10 @@ class IID_model():
             raise ValueError("Optimizer not supported")
 
         self._make_scheduler()
+        # RMSprop under the Triangle scheduler: CyclicLR's cycle_momentum writes a momentum into the optimizer's group (models.py:99), so
+        # torch -- the reference and the autograd paths here -- trains RMSprop WITH a momentum buffer.  The native steps ignore it (the
+        # default) or, opt-in, follow it.
+        follow = args['optimizer'] == 'RMSprop' and self._rmsprop_momentum(args) == 'follow' and self.schedule == 'Triangle'
         self.store = None
         self._args = dict(args)
         self._shared = {}           # what the lanes of one ensemble share besides the store (see lane()): the predict inputs
@@ -106,6 +110,7 @@ class IID_model():
         self._fused = None
         self._use_fused = (args['model_size'] == 'linear' and args['optimizer'] == 'RMSprop'
                            and args['n_clusters'] <= 256 and _fused_on())
+        self._small_momentum = follow       # the native small step in its momentum form
         # model_size='small': autograd (the default) or, opt-in, the explicit step of fused_small.FusedSmallTrainer
         self._small = None
         self._use_small = args['model_size'] == 'small' and self._small_step(args) == 'native'
@@ -113,6 +118,8 @@ class IID_model():
         self._linopt = None
         self._use_linopt = (args['model_size'] == 'linear' and args['optimizer'] in ('SGD', 'Adam')
                             and self._linear_step(args) == 'native')
+        if follow and self._use_fused:      # NetLinear: the step of fused_opt.FusedLinearOptTrainer with RMSprop as its optimizer
+            self._use_fused, self._use_linopt = False, True
 
     @staticmethod
     def _small_step(args):
@@ -124,6 +131,15 @@ class IID_model():
         if mode == 'native' and (args['optimizer'] != 'RMSprop' or not 1 <= args['n_clusters'] <= 256 or not 1 <= args['batch_sz'] <= 1024):
             raise ValueError("small_step='native' supports optimizer='RMSprop', n_clusters in 1..256 and batch_sz in 1..1024 "
                              f"(got optimizer={args['optimizer']!r}, n_clusters={args['n_clusters']}, batch_sz={args['batch_sz']})")
+        return mode
+
+    @staticmethod
+    def _rmsprop_momentum(args):
+        """args['rmsprop_momentum'] of a model trained with RMSprop: 'ignore' (absent or None) or 'follow'; anything else raises
+        ValueError.  (SGD and Adam: the key is not looked at.)"""
+        mode = args.get('rmsprop_momentum') or 'ignore'
+        if mode not in ('ignore', 'follow'):
+            raise ValueError(f"rmsprop_momentum must be 'ignore' or 'follow', not {mode!r}")
         return mode
 
     @staticmethod
@@ -238,9 +254,13 @@ class IID_model():
         if self._use_small:
             if self._small is None:
                 from .fused_small import FusedSmallTrainer
-                self._small = FusedSmallTrainer(self.net, self.lr, self.weight, self.l, seed=self.seed)
+                grp = self.optimizer.param_groups[0]
+                self._small = FusedSmallTrainer(self.net, self.lr, self.weight, self.l, seed=self.seed,
+                                                momentum=grp['momentum'] if self._small_momentum else None)
                 self._small.begin_voter(self._voter)
             self._small.set_lr(self.optimizer.param_groups[0]['lr'])       # schedulers act on the torch optimizer
+            if self._small_momentum:
+                self._small.set_momentum(self.optimizer.param_groups[0]['momentum'])
             total, n_batches = self._small.run_epoch(st, self.batch_sz, generator=self._gen)
             return total / (n_batches - 1)                                  # models.py:135 quirk (divide by last index)
         if self._use_linopt:

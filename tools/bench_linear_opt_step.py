@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Times one optimizer step of NetLinear trained with SGD or Adam in both step forms on the same GPU, in the same process,
+"""Times one optimizer step of NetLinear trained with SGD, Adam or RMSprop with momentum 0.9 (what the Triangle scheduler makes of the
+reference's RMSprop; rmsprop_momentum='follow') in both step forms on the same GPU, in the same process,
 alternating them: torch autograd (IID_model._step, what linear_step='autograd' runs) and the native HIP step
 (fused_opt.FusedLinearOptTrainer, linear_step='native', full-batch steps replayed from a captured graph).
 
 Input: a seeded synthetic feature store, 100 000 sequences x 3 mimic views, k = 6 (F = 4096 features), batch 512 (m = 1024 rows a
 step).  For every (optimizer, n_clusters) of --optimizers x --clusters one JSON line: us per step of each form (median of the rounds,
 and the rounds), whether the native median clears the autograd median by more than the autograd rounds' own spread (max - min),
-launches and library products per step (torch.profiler).
+launches and library products per step (torch.profiler).  The RMSprop case also times the default fused step at the same shape
+(fused.FusedLinearTrainer, the momentum ignored; whole epochs of its own graph replays): the price of following the reference, no bar.
 
 Usage:  python tools/bench_linear_opt_step.py [--rounds R] [--steps S] [--out FILE]      (--out: the lines are also appended to FILE)
 """
@@ -35,6 +37,8 @@ def make_optimizer(name, params):
     import torch
     if name == "SGD":                                        # reference models.py:89-92
         return torch.optim.SGD(params, lr=1e-3, weight_decay=0.01, momentum=0.9)
+    if name == "RMSprop":                                    # models.py:87-88 as CyclicLR (models.py:99) leaves it at construction
+        return torch.optim.RMSprop(params, lr=1e-3, weight_decay=0.01, momentum=0.9)
     return torch.optim.Adam(params, lr=1e-3)
 
 
@@ -96,6 +100,21 @@ def bench(opt_name, C, st, a, dev):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / n
 
+    default, t_def = None, []
+    if opt_name == "RMSprop":                            # the default step of this shape: RMSprop without the momentum
+        from idelucs_amd.fused import FusedLinearTrainer
+        torch.manual_seed(0)
+        net_d = NetLinear(F, C).to(dev)
+        net_d.apply(models.weights_init)
+        default = FusedLinearTrainer(net_d, 1e-3, 0.25, 2.8, seed=0)
+        default.begin_voter(0)
+        gen_d = torch.Generator(device=dev).manual_seed(1)
+        n_default = [1]
+
+        def default_epoch(n):
+            n_default[0] = default.run_epoch(st, B, generator=gen_d)[1]
+        default_epoch(0)                                 # (warm: the capture)
+
     autograd_steps(8)
     native_prologue()
     native_steps(per * 2)
@@ -105,6 +124,8 @@ def bench(opt_name, C, st, a, dev):
         t_auto.append(timed(autograd_steps, steps))
         native_prologue()
         t_nat.append(timed(native_steps, steps))
+        if default is not None:
+            t_def.append(timed(default_epoch, 1) / n_default[0])
 
     def launches(fn, n):
         torch.cuda.synchronize()
@@ -120,12 +141,16 @@ def bench(opt_name, C, st, a, dev):
     l_nat, lib_nat = launches(native_eager, 4)
     us_a, us_n = float(np.median(t_auto)), float(np.median(t_nat))
     spread = max(t_auto) - min(t_auto)
-    return {"tool": "bench_linear_opt_step", "optimizer": opt_name, "m": m, "F": F, "C": C, "n_pairs": st.n_pairs, "steps_per_round": steps,
-            "autograd_us_per_step": round(us_a, 2), "native_us_per_step": round(us_n, 2), "speedup": round(us_a / us_n, 2),
-            "autograd_rounds_us": [round(t, 2) for t in t_auto], "native_rounds_us": [round(t, 2) for t in t_nat],
-            "autograd_spread_us": round(spread, 2), "native_below_autograd_by_more_than_its_spread": bool(us_a - us_n > spread),
-            "launches_per_step": {"autograd": l_auto, "native": l_nat}, "library_gemms_per_step": {"autograd": lib_auto, "native": lib_nat},
-            "device": torch.cuda.get_device_name(0)}
+    res = {"tool": "bench_linear_opt_step", "optimizer": opt_name, "m": m, "F": F, "C": C, "n_pairs": st.n_pairs, "steps_per_round": steps,
+           "autograd_us_per_step": round(us_a, 2), "native_us_per_step": round(us_n, 2), "speedup": round(us_a / us_n, 2),
+           "autograd_rounds_us": [round(t, 2) for t in t_auto], "native_rounds_us": [round(t, 2) for t in t_nat],
+           "autograd_spread_us": round(spread, 2), "native_below_autograd_by_more_than_its_spread": bool(us_a - us_n > spread),
+           "launches_per_step": {"autograd": l_auto, "native": l_nat}, "library_gemms_per_step": {"autograd": lib_auto, "native": lib_nat},
+           "device": torch.cuda.get_device_name(0)}
+    if default is not None:
+        res.update({"default_fused_us_per_step": round(float(np.median(t_def)), 2), "default_fused_rounds_us": [round(t, 2) for t in t_def],
+                    "default_fused_steps_per_round": n_default[0]})
+    return res
 
 
 def main():
@@ -134,7 +159,7 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--n", type=int, default=100_000)
     ap.add_argument("--clusters", type=int, nargs="+", default=[20, 200])
-    ap.add_argument("--optimizers", nargs="+", default=["SGD", "Adam"], choices=["SGD", "Adam"])
+    ap.add_argument("--optimizers", nargs="+", default=["SGD", "Adam"], choices=["SGD", "Adam", "RMSprop"])
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()

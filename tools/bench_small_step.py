@@ -8,7 +8,11 @@ Input: a seeded synthetic feature store at the cfg2 size with reduce=True -- 100
 per step (torch.profiler), the algorithmic FLOP of a step (from the shapes) and the native step's share of the 157.3 TF/s fp32
 matrix peak.
 
-Usage:  python tools/bench_small_step.py [--rounds R] [--steps S]
+--momentum MU: RMSprop with a momentum buffer in both forms (torch's momentum=MU; the native step's momentum form, what
+rmsprop_momentum='follow' trains under the Triangle scheduler), whether the native median clears the autograd median by more than the
+autograd rounds' own spread, and beside them the default momentum-free native step in the same rounds.
+
+Usage:  python tools/bench_small_step.py [--rounds R] [--steps S] [--momentum MU] [--out FILE]
 """
 import argparse
 import json
@@ -51,6 +55,8 @@ def main():
     ap.add_argument("--n", type=int, default=100_000)
     ap.add_argument("--clusters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--momentum", type=float, default=None)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -68,18 +74,27 @@ def main():
     torch.manual_seed(0)
     net_a = myNet(F, C).to(dev)
     net_a.apply(models.weights_init)
-    opt = torch.optim.RMSprop(net_a.parameters(), lr=1e-3, weight_decay=0.01)
+    opt = torch.optim.RMSprop(net_a.parameters(), lr=1e-3, weight_decay=0.01, momentum=a.momentum or 0.0)
     auto = types.SimpleNamespace(net=net_a, optimizer=opt, weight=0.25, l=2.8)
     perm = torch.randperm(st.n_pairs, device=dev)
 
     torch.manual_seed(0)
     net_n = myNet(F, C).to(dev)
     net_n.apply(models.weights_init)
-    tr = FusedSmallTrainer(net_n, 1e-3, 0.25, 2.8, seed=0)
+    tr = FusedSmallTrainer(net_n, 1e-3, 0.25, 2.8, seed=0, momentum=a.momentum)
     tr.begin_voter(0)
     tr._perm = perm
     per = 16
     bf = tr.buffers(m)
+    plain = None
+    if a.momentum is not None:                           # the default step beside it: the momentum-free launch, its own buffers and graph
+        torch.manual_seed(0)
+        net_p = myNet(F, C).to(dev)
+        net_p.apply(models.weights_init)
+        plain = FusedSmallTrainer(net_p, 1e-3, 0.25, 2.8, seed=0)
+        plain.begin_voter(0)
+        plain._perm = perm
+        bf_p = plain.buffers(m)
 
     def native_prologue():
         tr.ctl[1:2].zero_()
@@ -101,6 +116,20 @@ def main():
         for _ in range(n // per):
             g.replay()
 
+    if plain is not None:
+        def plain_prologue():
+            plain.ctl[1:2].zero_()
+            plain._gather(st, bf_p, B)
+        plain_prologue()
+        g_p = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g_p):
+            for i in range(per):
+                plain.step_on_batch(bf_p, xi=i % 2, next_from=st)
+
+        def plain_steps(n):
+            for _ in range(n // per):
+                g_p.replay()
+
     def timed(fn, n):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -114,11 +143,17 @@ def main():
     native_prologue()
     native_steps(per * 2)
     steps = max(per, min(a.steps, st.n_pairs // B - 1) // per * per)
-    t_auto, t_nat = [], []
+    t_auto, t_nat, t_plain = [], [], []
+    if plain is not None:
+        plain_prologue()
+        plain_steps(per * 2)
     for _ in range(a.rounds):                            # alternating, same box, same process
         t_auto.append(timed(autograd_steps, steps))
         native_prologue()
         t_nat.append(timed(native_steps, steps))
+        if plain is not None:
+            plain_prologue()
+            t_plain.append(timed(plain_steps, steps))
 
     def launches(fn, n):
         torch.cuda.synchronize()
@@ -134,13 +169,23 @@ def main():
     l_nat = launches(lambda n: [tr.step_on_batch(bf, xi=i % 2, next_from=st) for i in range(n)], 4)[0]
     flop = step_flop(m, F, C)
     us_a, us_n = float(np.median(t_auto)), float(np.median(t_nat))
-    print(json.dumps({"tool": "bench_small_step", "m": m, "F": F, "C": C, "n_pairs": st.n_pairs,
+    extra = {}
+    if plain is not None:
+        spread = max(t_auto) - min(t_auto)
+        extra = {"momentum": a.momentum, "autograd_spread_us": round(spread, 2),
+                 "native_below_autograd_by_more_than_its_spread": bool(us_a - us_n > spread),
+                 "default_native_us_per_step": round(float(np.median(t_plain)), 2), "default_native_rounds_us": [round(t, 2) for t in t_plain]}
+    line = json.dumps({**extra, "tool": "bench_small_step", "m": m, "F": F, "C": C, "n_pairs": st.n_pairs, "steps_per_round": steps,
                       "autograd_us_per_step": round(us_a, 2), "native_us_per_step": round(us_n, 2), "speedup": round(us_a / us_n, 2),
                       "autograd_rounds_us": [round(t, 2) for t in t_auto], "native_rounds_us": [round(t, 2) for t in t_nat],
                       "launches_per_step": {"autograd": l_auto, "native": l_nat}, "library_gemms_per_step_autograd": lib_auto,
                       "flop_per_step": flop, "native_tflops": round(flop / (us_n * 1e-6) / 1e12, 2),
                       "native_share_of_fp32_matrix_peak": round(flop / (us_n * 1e-6) / PEAK_FP32_MATRIX, 4),
-                      "device": torch.cuda.get_device_name(0)}))
+                      "device": torch.cuda.get_device_name(0)})
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
