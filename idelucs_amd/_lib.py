@@ -17,7 +17,7 @@ IDL_OK, IDL_ERR_ARG, IDL_ERR_HIP, IDL_ERR_IO, IDL_ERR_HEADER, IDL_ERR_BASE, IDL_
 MODE_KMER, MODE_CGR, MODE_CANONICAL = 0, 1, 2
 INIT_ZERO, INIT_ONE, INIT_FROM_OUT = 0, 1, 2
 OUT_COUNTS_I32, OUT_FREQ_F32, OUT_FREQ_F64 = 0, 1, 2
-MAX_K = 7
+MAX_K = 9
 
 _c = ctypes
 _vp, _i64, _i32, _int = _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int
@@ -141,6 +141,8 @@ SIGNATURES = {
     "idl_mimic_slots_capacity": (_i64, [_i64, _int, _vp, _vp, _vp, _i64]),
     "idl_mimic_edits_slots": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _c.c_uint64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "idl_vectorise_ranges": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "idl_vectorise_slices_lds": (_int, []),
+    "idl_vectorise_slices_per_cu": (_int, []),
     "idl_plan_bytes": (_i64, []),
     "idl_plan_begin": (_int, [_vp]),
     "idl_plan_end": (_int, []),

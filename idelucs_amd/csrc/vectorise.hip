@@ -1769,6 +1769,8 @@ int launch_vectorise(const VecArgs &a_in, const idl::DeviceInfo &di, hipStream_t
     return IDL_OK;
 }
 
+#include "vectorise_slices.h"   // k = 8, 9: the histogram exceeds one CU's LDS
+
 int dispatch_vectorise(int k, const VecArgs &a, hipStream_t st)
 {
     idl::DeviceInfo di;
@@ -1782,6 +1784,8 @@ int dispatch_vectorise(int k, const VecArgs &a, hipStream_t st)
     case 5: return launch_vectorise<5>(a, di, st);
     case 6: return launch_vectorise<6>(a, di, st);
     case 7: return launch_vectorise<7>(a, di, st);
+    case 8: return launch_vectorise_slices<8>(a, di, st);
+    case 9: return launch_vectorise_slices<9>(a, di, st);
     }
     idl::set_error("k=%d outside 1..%d", k, IDL_MAX_K);
     return IDL_ERR_ARG;
@@ -1885,6 +1889,8 @@ int idl_kmer_rev_comp(int32_t *counts, int k, int32_t *out)
     case 5: hipLaunchKernelGGL(collapse_kernel<5>, dim3(1), dim3(64), 0, nullptr, dc, dout); break;
     case 6: hipLaunchKernelGGL(collapse_kernel<6>, dim3(1), dim3(64), 0, nullptr, dc, dout); break;
     case 7: hipLaunchKernelGGL(collapse_kernel<7>, dim3(1), dim3(64), 0, nullptr, dc, dout); break;
+    case 8: hipLaunchKernelGGL(collapse_kernel<8>, dim3(1), dim3(64), 0, nullptr, dc, dout); break;
+    case 9: hipLaunchKernelGGL(collapse_kernel<9>, dim3(1), dim3(64), 0, nullptr, dc, dout); break;
     }
     IDL_HIP_TRY(hipGetLastError());
     IDL_HIP_TRY(hipMemcpy(counts, d_counts.p, (size_t)F * 4, hipMemcpyDeviceToHost));
@@ -1959,5 +1965,9 @@ int idl_vectorise_ranges(const void *codes, const void *mask, const int64_t *slo
 {
     return vectorise_impl(codes, mask, slot_off, lengths, n, k, mode, init, out_kind, n_views, edits, edit_ranges, 1, out, view_stride, max_len, stream);
 }
+
+/* the k = 8, 9 kernel's dynamic LDS per workgroup and the workgroups per CU its launcher puts on the chip (build checks, reports) */
+int idl_vectorise_slices_lds(void) { return SL_LDS_WORDS * 4; }
+int idl_vectorise_slices_per_cu(void) { return SL_WG_PER_CU; }
 
 }  // extern "C"

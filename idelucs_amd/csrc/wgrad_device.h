@@ -70,7 +70,10 @@ __device__ __forceinline__ void rms_update(float g, float &p, float &v, const Hy
 
 __host__ __device__ inline bool supported(int m, int n_out, int n_in)
 {
-    return m >= 4 * RING && (m % (4 * RING)) == 0 && n_out >= TM && (n_out % TM) == 0 && n_in >= TN && (n_in % TN) == 0;
+    // (the last two: the tiles address their operands with 32-bit byte offsets, what every launcher of them requires -- at 4^9
+    //  columns that is m < 2048, and a larger batch takes the library GEMM of the general form instead of failing its launch)
+    return m >= 4 * RING && (m % (4 * RING)) == 0 && n_out >= TM && (n_out % TM) == 0 && n_in >= TN && (n_in % TN) == 0 &&
+           (int64_t)m * n_in < (1ll << 29) && (int64_t)n_out * n_in < (1ll << 29);
 }
 
 // One 64 x 128 tile by one 256-thread workgroup (bid = tile index).  VARIANT 1: no loads in the loop (a diagnostic: what the

@@ -50,7 +50,7 @@ def _run(fn, seq, k, counts):
     sv, cv = _seq_view(seq), _counts_view(counts)
     k = int(k)
     if not 1 <= k <= _lib.MAX_K:
-        raise ValueError(f"k={k} is outside 1..{_lib.MAX_K} (one wavefront's LDS histogram holds 4^k uint32 bins)")
+        raise ValueError(f"k={k} is outside 1..{_lib.MAX_K} (the vectoriser has kernels for those lengths only)")
     if cv.shape[0] < 4 ** k:
         # the reference has bounds checks off (kmers.pyx:1) and would corrupt memory here
         raise ValueError(f"counts has {cv.shape[0]} entries; k={k} needs {4 ** k}")
