@@ -7,6 +7,12 @@
 //         candidate = the j with the smallest min_reach[j] (strict <, so the FIRST such j), with its source
 //     edge (source, j, min_reach[j]); current = j
 // -- so that the edges, and with them sklearn's own condensed-tree code that runs on them afterwards, are the ones sklearn gets.
+// (In sklearn's text the candidate is tracked inside the same scan, `elif min_reach[j] < best` for the entries that did not fall; that
+// is the first j with the smallest min_reach AFTER the updates, as written above.  The evidence: tests/test_gpu_mst_edges.py compares
+// idl_mst_prim's and idl_mst_prim_local's edges -- nodes, order, weights, bit for bit -- with tests/mst_ref.py, a numpy restatement
+// that tests/test_mst_reference.py compares with mst_from_data_matrix itself, on lattices, integer grids, duplicates and equal
+// points (every weight ties), at n = 2 .. 3072 around one workgroup, at 1 .. 256 features in float32 and float64.  idl_mst_prim_lazy
+// and the strided tail beyond 2^20 points are compared with these kernels only: tests/test_gpu_knn.py.)
 // Distances are formed exactly as sklearn's EuclideanDistance64 does (float64: t = a - b; d += t * t, in feature order, then one
 // sqrt; no fused multiply-add), from the points stored feature-major ([D][N]: lanes read consecutive points) in float32 when
 // the data is float32-exact (the latent is) or float64 otherwise.

@@ -608,6 +608,11 @@ def hdbscan_device(points, min_cluster_size, device=None, stats=None, core=None,
     idl_mst_prim: sklearn's mst_from_data_matrix visit for visit, in float64); the edges then go through sklearn's own
     single-linkage / condensed-tree code (sklearn.cluster._hdbscan: make_single_linkage, tree_to_labels -- private names of
     sklearn 1.7, the stand-in for the absent `hdbscan` package: SURVEY 8c), so the labels are sklearn's.
+    "Visit for visit" is tested at that level: tests/test_gpu_mst_edges.py holds the edges of idl_mst_prim and idl_mst_prim_local --
+    nodes, order, float64 weights, bit for bit -- to tests/mst_ref.py, which tests/test_mst_reference.py holds to sklearn's own
+    mst_from_data_matrix, on inputs whose weights tie; idl_mst_prim_lazy, and inputs beyond 2^20 points, are compared with those
+    kernels only (tests/test_gpu_knn.py).  stats (a dict) receives timings, the edges ("mst_edges") and which Prim ran ("mst_path":
+    plain | local | lazy; "mst_groups" with the latter two).
     core: the core distances (float64 [n], device or host) when the caller has them already (the CLI computes them over all ranks of
     a multi-GPU job before the others leave: core_distances_sharded); shard = (rank, world): compute them here, split over the
     ranks of the process group (every rank must call with the same points; all return the same labels)."""
@@ -686,14 +691,19 @@ def hdbscan_device(points, min_cluster_size, device=None, stats=None, core=None,
                                            vp(w.data_ptr()), vp(ws2.data_ptr() + off2), stream, ctypes.cast(st3, ctypes.c_void_p)))
             if stats is not None:
                 stats["prim_launches"], stats["prim_stalls"], stats["prim_censuses"] = int(st3[0]), int(st3[1]), int(st3[2])
+                stats["mst_path"], stats["mst_groups"] = "lazy", n_groups
         else:
             _lib.check(L.idl_mst_prim_local(vp(xt.data_ptr()), 0 if f32_exact else 1, vp(core_o.data_ptr()), n, d, vp(orig.data_ptr()), start,
                                             vp(codes.data_ptr()), vp(resid.data_ptr()), vp(gid32.data_ptr()), vp(glo.data_ptr()),
                                             vp(gscale.data_ptr()), vp(cur.data_ptr()), vp(nxt.data_ptr()), vp(w.data_ptr()), vp(ws.data_ptr() + off), stream))
+            if stats is not None:
+                stats["mst_path"], stats["mst_groups"] = "local", n_groups
     else:
         xt = x64.t().contiguous().to(torch.float32 if f32_exact else torch.float64)
         _lib.check(L.idl_mst_prim(vp(xt.data_ptr()), 0 if f32_exact else 1, vp(core.data_ptr()), n, d, vp(cur.data_ptr()), vp(nxt.data_ptr()),
                                   vp(w.data_ptr()), vp(ws.data_ptr() + off), stream))
+        if stats is not None:
+            stats["mst_path"] = "plain"                                               # (no order, no groups: "mst_groups" stays unset)
     mst = np.empty(n - 1, dtype=MST_edge_dtype)
     mst["current_node"], mst["next_node"], mst["distance"] = cur.cpu().numpy(), nxt.cpu().numpy(), w.cpu().numpy()
     if stats is not None:

@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+from mst_ref import core_by_definition
+
 pytestmark = pytest.mark.gpu
 
 
@@ -16,19 +18,6 @@ def _blobs(n, seed, noise=20, spread=(0.3, 0.9), offset=0.0):
     if noise:
         x[: n // noise] = rng.uniform(-8, 8, size=(n // noise, 64)) + offset
     return x.astype(np.float32).astype(np.float64)
-
-
-def _kth_by_definition(x, rows, k):
-    """sqrt of the k-th smallest of sum_c (a_c - b_c)^2, the sum taken coordinate by coordinate in float64 (sklearn's
-    EuclideanDistance: _dist_metrics.pyx.tp rdist loop), the row itself included."""
-    out = np.empty(len(rows))
-    for i, r in enumerate(rows):
-        acc = np.zeros(len(x))
-        for c in range(x.shape[1]):
-            t = x[r, c] - x[:, c]
-            acc += t * t
-        out[i] = np.sqrt(np.partition(acc, k - 1)[k - 1])
-    return out
 
 
 @pytest.mark.parametrize("n,sample,offset", [(40000, None, 0.0), (9000, 1024, 0.0), (20000, 4096, 37.5)])
@@ -53,7 +42,7 @@ def test_window_core_distances_are_the_kth_neighbour_distances(n, sample, offset
     print(stats)
     assert stats["missed"] <= max(8, n // 2000), "the bracket misses far more rows than its 4.5 sigma promise"
     rows = np.random.default_rng(1).choice(n, 48, replace=False)
-    assert np.array_equal(got[rows], _kth_by_definition(x, rows, k))
+    assert np.array_equal(got[rows], core_by_definition(x, k, rows))
     assert np.array_equal(got, ref)
 
 
@@ -75,7 +64,7 @@ def test_window_core_distances_with_duplicates_and_tiny_k(monkeypatch):
         print(k, stats)
         assert np.array_equal(got, ref)
         rows = np.r_[0:8, 6000:6008]
-        assert np.array_equal(got[rows], _kth_by_definition(x, rows, k))
+        assert np.array_equal(got[rows], core_by_definition(x, k, rows))
 
 
 def test_hdbscan_labels_do_not_depend_on_the_core_distance_path(monkeypatch):
@@ -174,7 +163,7 @@ def test_core_distances_when_no_bracket_exists(monkeypatch):
     monkeypatch.setattr(posthoc, "KNN_WINDOW_MIN", 0)
     got = posthoc.core_distances_device(xd, k, dev).cpu().numpy()
     rows = np.arange(0, 5003, 500)
-    assert np.array_equal(got[rows], _kth_by_definition(x, rows, k))
+    assert np.array_equal(got[rows], core_by_definition(x, k, rows))
     monkeypatch.setitem(__import__("idelucs_amd.posthoc", fromlist=["OPTIONS"]).OPTIONS, "knn", "window")
     with pytest.raises(ValueError):
         posthoc.core_distances_device(xd, k, dev)
