@@ -41,10 +41,10 @@ def _random_net(F, C, dev, seed=0):
     return net.to(dev)
 
 
-def _autograd_step(net, x, masks=None):
+def _autograd_step(net, x, masks=None, float64_grads=False):
     """The reference step (models.py:117-133) written out on a float64 copy of net: dropout off, or the given keep masks x 2 in place
     of nn.Dropout.  -> (loss, [8 gradients as float32]).  (float64: the bars below then measure the step's own rounding, not the sum
-    of two fp32 implementations'.)"""
+    of two fp32 implementations'.)  float64_grads: the gradients as autograd left them (tests/test_small_reference.py)."""
     import copy
     import torch
     import torch.nn.functional as Fn
@@ -70,7 +70,7 @@ def _autograd_step(net, x, masks=None):
     nce = (torch.logsumexp(s, dim=1) - pos).mean()
     loss = 0.75 * nce + 0.25 * IID_loss(z[:b], z[b:], lamb=2.8)
     loss.backward()
-    return float(loss.item()), [p.grad.detach().float().clone() for p in ps]
+    return float(loss.item()), [(p.grad.detach() if float64_grads else p.grad.detach().float()).clone() for p in ps]
 
 
 # ------------------------------------------------------------------------------------------------ 1. the reference's goldens
@@ -135,7 +135,7 @@ def _check_against_autograd(tr, p0, loss_ref, grads_ref):
     for i, n_ in enumerate(NAMES):
         got, want = tr.gradient(i), grads_ref[i]
         err = (got - want).abs().max().item()
-        print(f"{n_}: max error {err / want.abs().max().item():.2e} of the gradient's max")
+        print(f"{n_}: max error {err:.2e}, the gradient's max {want.abs().max().item():.2e}")
         assert err <= 2e-3 * want.abs().max().item() + 1e-12, (n_, err, want.abs().max().item())
     # RMSprop on the trainer's own gradients (torch.optim.RMSprop from the same starting parameters): rel 1e-5
     ps = [p.clone().requires_grad_(True) for p in p0]
@@ -179,6 +179,108 @@ def test_dropout_step_matches_autograd_with_the_trainers_masks(dev, F, m, C):
     bf.x.copy_(x)
     tr.step_on_batch(bf, train=True)
     torch.cuda.synchronize()
+    _check_against_autograd(tr, p0, loss_ref, grads_ref)
+
+
+# ------------------------------------------------------------------------------------------------ 3b. the partial last batch
+# An epoch's last batch is any even m from 2 up.  m % 32 != 0 takes the unfused InfoNCE route (one part of G), and with it every
+# n_clusters > 48 reads dP0 and the partner's z from global memory in the middle backward; m = 96 keeps the fused InfoNCE kernels at
+# a size no full batch has.  F alternates over the (m, C) grid so that every m and every C meets both widths.
+RAGGED_M, RAGGED_C, RAGGED_F = [2, 18, 34, 62, 96, 440], [5, 49, 130, 201, 256], [136, 512]
+
+
+def _crossed_a_kink(p0, x, masks, bf):
+    """True when the step's float32 forward put a hidden unit on the other side of 0 than float64 does.  ReLU' and LeakyReLU' jump
+    there, so that unit then takes the other slope in the backward, and with a handful of rows one unit is a large share of its
+    rows of dW1, dW2: not an error of the step, and not what a comparison with autograd can judge (tests/test_gpu_small_stages.py
+    takes every sign from the kernel's own activations and has no such case).  A sign may differ only where the float64
+    pre-activation is within a float32 forward's rounding of 0 -- the product bound of small_ref.py, (K + 16) 2^-23 sum |a||b|, plus
+    layer 1's own error carried through |W2|; anywhere else it is an error, and is raised as one."""
+    import torch
+    x, W1, b1, W2, b2 = (t.detach().double() for t in (x, *p0[:4]))      # (p0: the parameters before the step, in myNet's order)
+    u = 2.0 ** -23
+    keep = masks[0].double() * 2.0 if masks is not None else torch.ones((x.shape[0], W1.shape[0]), dtype=torch.float64, device=x.device)
+    v1 = x @ W1.t() + b1
+    e1 = (x.shape[1] + 16) * u * (x.abs() @ W1.abs().t() + b1.abs())
+    a1 = torch.relu(v1) * keep
+    v2 = a1 @ W2.t() + b2
+    e2 = (W2.shape[1] + 16) * u * (a1.abs() @ W2.abs().t() + b2.abs()) + (e1 * keep) @ W2.abs().t()
+    off1, off2 = (bf.a1 > 0) != (a1 > 0), (bf.a2 > 0) != (v2 > 0)
+    assert bool((v1.abs()[off1] <= e1[off1]).all()) and bool((v2.abs()[off2] <= e2[off2]).all())
+    return bool(off1.any()) or bool(off2.any())
+
+
+def _ragged_step(dev, m, C, F, dropout):
+    import torch
+    for draw in range(4):                                # (the first draw but for m = 2, C = 201, F = 512 with dropout: one unit of
+        #                                                  layer 2 lies 1.3e-6 from 0 there and the float32 forward lands beyond it)
+        net = _random_net(F, C, dev, seed=F + m + C)
+        p0 = [p.detach().clone() for p in net.parameters()]
+        tr = _trainer(net)
+        tr.begin_voter(2)
+        masks = tr.dropout_masks(int(tr.ctl[0].item()), m) if dropout else None
+        x = torch.randn((m, F), device=dev, generator=torch.Generator(device=dev).manual_seed(F * 7 + m + C + 1000 * draw))
+        loss_ref, grads_ref = _autograd_step(net, x, masks=masks)
+        bf = tr.buffers(m)
+        bf.x.copy_(x)
+        tr.step_on_batch(bf, train=dropout)
+        torch.cuda.synchronize()
+        if not _crossed_a_kink(p0, x, masks, bf):
+            return tr, bf, p0, loss_ref, grads_ref
+        print(f"draw {draw}: a hidden unit crossed 0 in float32, next draw")
+    raise AssertionError("four draws of x in a row put a hidden unit across 0")
+
+
+@pytest.mark.parametrize("dropout", [False, True])
+@pytest.mark.parametrize("m,C,F", [(m, C, RAGGED_F[(i + j) % 2]) for i, m in enumerate(RAGGED_M) for j, C in enumerate(RAGGED_C)])
+def test_partial_batch_step_matches_autograd(dev, m, C, F, dropout):
+    """step_on_batch against float64 autograd at the shapes of a partial last batch, dropout off and on with the trainer's own masks:
+    the bars of the full-batch tests (the sharp, per-stage bars are tests/test_gpu_small_stages.py's)."""
+    import torch
+    tr, bf, p0, loss_ref, grads_ref = _ragged_step(dev, m, C, F, dropout)
+    assert bf.nce_fused == (m % 32 == 0) and (bf.dzs is not None) == (48 < C <= 200)
+    for t in [tr.out] + tr.grads + [p.detach() for p in tr.params] + tr.square_avg:
+        assert bool(torch.isfinite(t).all())
+    _check_against_autograd(tr, p0, loss_ref, grads_ref)
+    assert tr.ctl.tolist() == [(2 << 24) + 1, 0]
+    if m == 2:
+        _check_one_pair(tr, p0, grads_ref)
+
+
+def _check_one_pair(tr, p0, grads_ref):
+    """m = 2 is one pair: each row's only other row is its positive, so InfoNCE is 0 and its gradient (the instance head's, which nothing
+    else reaches) exactly 0; and the parameters are those of RMSprop fed the reference's gradients.
+
+    The parameter bar.  With R = tests/small_ref.py and the trainer's float32 hyperparameters, |p - R.rmsprop(p0, 0, g_ref)| <=
+    |p - R.rmsprop(p0, 0, g)| + |R.rmsprop(p0, 0, g) - R.rmsprop(p0, 0, g_ref)|, g the step's own gradient.  The first term is one float32
+    update: R.rmsprop_bound.  The second: the first update moves p by lr g' / (sqrt(1 - alpha) |g'| + eps), g' = g + wd p, a function of
+    g' whose slope eps / (sqrt(1 - alpha) |g'| + eps)^2 is largest at the smaller |g'| where the two agree in sign and at most 1 / eps
+    where they do not: lr slope |g - g_ref|, with the two gradients this test has just compared."""
+    import small_ref as R
+    # (the loss itself is lse - s_partner / T of two sums each rounded a few times at |s| / T <= 1 / 0.85: 0 to 4 * 2^-23 / 0.85)
+    print(f"InfoNCE of one pair: {tr.out[2].item():.3e}")
+    assert abs(tr.out[2].item()) <= 4 * 2.0 ** -23 / 0.85
+    assert float(tr.gradient(4).abs().max()) == 0.0 and float(tr.gradient(5).abs().max()) == 0.0
+    assert float(grads_ref[4].abs().max()) == 0.0 and float(grads_ref[5].abs().max()) == 0.0
+    h = R.f64(tr.hyper)
+    for n_, p, start, g_ref, g_got in zip(NAMES, tr.params, p0, grads_ref, tr.grads):
+        start, g_ref, g_got = R.f64(start), R.f64(g_ref), R.f64(g_got)
+        zero = np.zeros_like(start)
+        want, own = R.rmsprop(start, zero, g_ref, h)[0], R.rmsprop_bound(start, zero, g_got, h)[0]
+        gi_ref, gi_got = g_ref + h[3] * start, g_got + h[3] * start
+        low = np.where(gi_ref * gi_got > 0, np.minimum(np.abs(gi_ref), np.abs(gi_got)), 0.0)
+        bar = own + h[0] * h[2] / (np.sqrt(h[4]) * low + h[2]) ** 2 * np.abs(gi_got - gi_ref)
+        worst = (np.abs(R.f64(p) - want) / bar).max()
+        print(f"{n_}: parameter error / bar {worst:.3f}")
+        assert worst <= 1.0, (n_, worst)
+
+
+def test_full_batch_step_at_256_clusters_matches_autograd(dev):
+    """C = 256 (above the 200 the fine-grained mode uses, the most the kernels take), m = 512: a full batch on the fused InfoNCE
+    kernels with dP0 read from global memory in the middle backward."""
+    import torch
+    tr, bf, p0, loss_ref, grads_ref = _ragged_step(dev, 512, 256, 136, False)
+    assert bf.nce_fused and bf.dzs is None
     _check_against_autograd(tr, p0, loss_ref, grads_ref)
 
 
