@@ -8,8 +8,8 @@ One step of reference idelucs/models.py:117-133 takes one of five launch sequenc
     planes_rows  the same for n_clusters > 48 (the fine-grained mode's 200 output units: joint + IIC core with z dP0, dW3 on idl_at_b)
     tiles        IDELUCS_PLANES=0 (or shapes the planes do not take): own fp32 tiles, idl_l1_fwd -> idl_mid_fwd_gather -> InfoNCE + IIC ->
                  idl_mid_bwd_gather -> idl_wgrad_rmsprop; the optimizer's tail rides in the NEXT step's layer-1 launch (idl_l1_fwd_rms)
-    record_planes the planes sequence recorded for BatchedLinearTrainer
-    record_planes_rows  the planes_rows sequence (48 < n_clusters <= 200) recorded for BatchedLinearTrainer
+    record_planes, record_planes_rows (48 < n_clusters <= 200)  the SAME bodies (_step_planes, _step_planes_rows) issued through the recorder
+                 for BatchedLinearTrainer: every launch recorded instead of performed, no step state kept
     general      everything else on library GEMMs + the unfused kernels: a lockstep step on batched fp32 GEMMs, n_clusters > 48 in fp32,
                  partial batches and the shapes the own tiles do not take
 (DESIGN.md 4.4 has the table of what each launch carries).  Batches are assembled from the HBM feature store at a device-resident
@@ -79,10 +79,21 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# the arguments of a launch that can assemble the next batch into bf.x (the store, the pair list, the destination) when it assembles none
+_NO_GATHER = (None, 0, 0, 0, None, 0, 0, None, None, None, None)
+# idl_reduce_parts_rms with no optimizer tail beside the sum: the 23 arguments _tail / _wg would fill (FusedLinearTrainer._reduce)
+_NO_TAIL = (0, None, None, None, None, None, None, None, None, 0, 0.0, 0.0, None, 0, -1, None, None, 0, 0, 0, 0, None, 0)
+
+
+def _tile_per_cu(H1, F, cus):
+    """Whether the dW1 launch has a tile per CU and one CU for each block of the optimizer's tail on its loader waves (idl_wgrad_xplanes_rms)."""
+    return 144 <= (H1 // 64) * (F // 128) <= cus
+
+
 def rows_shape_applies(m, H1, F, cus):
-    """Whether a batch shape takes the two-plane step of n_clusters > 48 (FusedLinearTrainer._step_planes_rows and its recorded form): the layer-1
+    """Whether a batch shape takes the two-plane step of n_clusters > 48 (FusedLinearTrainer._step_planes_rows, lone or recorded): the layer-1
     tiles with the operands' roles swapped, dW1 from the batch's planes, a dW1 tile per CU with one for each block of the tail on its loader waves."""
-    return bool(_L.idl_l1_planes_supported(H1, m, F)) and bool(_L.idl_wgrad_xplanes_supported(m, H1, F)) and 144 <= (H1 // 64) * (F // 128) <= cus
+    return bool(_L.idl_l1_planes_supported(H1, m, F)) and bool(_L.idl_wgrad_xplanes_supported(m, H1, F)) and _tile_per_cu(H1, F, cus)
 
 
 def rows_lockstep_applies(m, H1, F, C, n_rows, cus):
@@ -95,6 +106,11 @@ def rows_lockstep_applies(m, H1, F, C, n_rows, cus):
 def _launch(fn, *args):
     """One kernel launch, performed now (the launcher of launch_losses outside a recording)."""
     _lib.check(fn(*args))
+
+
+def _mm_now(a, b, out):
+    """One library product, performed now (beside _launch what FusedLinearTrainer._mm / _k are while nothing is recorded)."""
+    torch.mm(a, b, out=out)
 
 
 def launch_losses(k, bf, lamb, weight, out, dz=False):
@@ -208,7 +224,41 @@ class _Recorder:
 class _LinearStepParts:
     """What every explicit NetLinear step shares whichever optimizer ends it (FusedLinearTrainer; fused_opt.FusedLinearOptTrainer): the
     buffers of a batch shape, the argument lists of the optimizer-free launches, the prologue gather and the two ways a step is issued.
-    A user provides params / grads / parts, the network's shapes, weight, ctl, _perm, _bufs, _shared_buffers and step_on_batch."""
+    _init_network provides the network's tensors and shapes, grads / parts, weight, ctl and the launches' pointer arrays; a user adds its
+    optimizer's state and step_on_batch."""
+
+    _cold, _cold_buf = False, None       # (FusedLinearTrainer's test hook: a fill in front of the hand-scheduled launches)
+
+    def _init_network(self, net, weight, lamb, seed, grad_w1=None, shared_buffers=None):
+        """The part of __init__ that knows no optimizer.  grad_w1 / shared_buffers: a BatchedLinearTrainer's stacked dW1 slice and buffer views."""
+        lin1, lin2, lin3 = net.layers[0], net.layers[3], net.classifier[2]
+        self.net = net
+        self.W1, self.b1, self.W2, self.b2, self.W3, self.b3 = lin1.weight, lin1.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias
+        self.params = [self.W1, self.b1, self.W2, self.b2, self.W3, self.b3]
+        self.dev = self.W1.device
+        self.F, self.H1, self.H2, self.C = lin1.in_features, lin1.out_features, lin2.out_features, lin3.out_features
+        if self.H1 != 512 or self.H2 != 64 or self.C > 256 or lin2.in_features != self.H1 or lin3.in_features != 64:
+            raise ValueError(f"{type(self).__name__} needs NetLinear (hidden 512, latent 64) and n_clusters <= 256")
+        # bias gradients are kept as COL_PARTS stacked partial column sums, added up inside the optimizer's launch
+        self.parts = [1 if p.dim() == 2 else _L.idl_col_sum_parts() for p in self.params]
+        # the last layer's weight gradient (C x 64) is produced as partials by the middle-backward launch when C <= 48
+        if self.C <= 48:
+            self.parts[4] = _L.idl_col_sum_parts()
+        self.grads = [torch.zeros((q,) + tuple(p.shape), dtype=p.dtype, device=p.device) if q > 1 else torch.zeros_like(p)
+                      for p, q in zip(self.params, self.parts)]
+        if grad_w1 is not None:                  # this voter's slice of a BatchedLinearTrainer's stacked dW1
+            assert tuple(grad_w1.shape) == tuple(self.W1.shape) and grad_w1.is_contiguous()
+            self.grads[0] = grad_w1
+        self.weight, self.lamb, self.seed = float(weight), float(lamb), int(seed) & (2 ** 64 - 1)
+        self.ctl = torch.zeros(2, dtype=torch.int64, device=self.dev)        # [dropout step counter, batch offset]
+        self.out = torch.zeros(4, dtype=torch.float32, device=self.dev)      # [step loss, running sum, nce, iic]
+        self._bufs, self._graphs, self._perm = {}, {}, None
+        self._shared_buffers = shared_buffers    # {m: {...}} views handed to _Buffers
+        n = len(self.params)
+        self._pp = (ctypes.c_void_p * n)(*[p.data_ptr() for p in self.params])
+        self._gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in self.grads])
+        self._sz = (ctypes.c_int64 * n)(*[p.numel() for p in self.params])
+        self._parts = (ctypes.c_int32 * n)(*self.parts)
 
     def gradient(self, i):
         """Gradient of parameter i as a tensor of the parameter's shape (sums the stacked partials)."""
@@ -234,6 +284,87 @@ class _LinearStepParts:
         return (_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), _p(self.W2), _p(r1), m, self.C, tr,
                 (1.0 - self.weight) / (m * TEMPERATURE), _p(bf.dlogits), _p(bf.dlat), _p(bf.dr1), _p(gb1), _p(gb2), _p(gb3), _p(gW3))
 
+    def _evict(self):
+        if self._cold_buf is None:
+            self._cold_buf = torch.empty(128 << 20, dtype=torch.float32, device=self.dev)
+        self._cold_buf.fill_(1.0)
+
+    def _tiles_middle(self, k, bf, tr, st, xi, r1):
+        """The middle of a step at n_clusters <= 48 on fp32 operands, behind the layer-1 product W1 x^T in r1 ([H1, m]; mid_fwd adds the bias):
+        mid_fwd + its share of the next batch (into bf.xs[1 - xi]), InfoNCE + IIC, mid_bwd + the rest of the next batch -- each through the
+        launcher k."""
+        m = bf.m
+        nxt = (*self._next_batch(st, m), _p(bf.xs[1 - xi]))
+        k(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *nxt, 0, GATHER_SPLIT, 8, _stream())
+        launch_losses(k, bf, self.lamb, self.weight, self.out)
+        k(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *nxt, GATHER_SPLIT, 8, 8, 1, _stream())
+
+    def _early(self, bf, st):
+        """Whether the middle launches of a general step on bf assemble the next batch from st (else the step's last launch does, or nobody)."""
+        return st is not None and bf.m % 16 == 0 and self.F % 4 == 0
+
+    def _general_fwd_bwd(self, bf, tr, batch_advance, st, xi, *, k, mm, dz, dw2):
+        """Forward and backward of the general step form on the batch in bf.xs[xi]: library products and the unfused kernels where a shape
+        needs them.  An early step (_early): the middle launches assemble the next batch into bf.xs[1 - xi]
+        (n_clusters <= 48: both of them, _tiles_middle; else the forward alone); otherwise the backward's last launch advances the batch offset
+        by batch_advance and the caller's optimizer launch assembles the batch.  What the two callers do differently is an argument:
+          k, mm  the launcher and the layer-1 product W1 x^T of an early step at n_clusters <= 48: FusedLinearTrainer's _k (in an early step;
+                 else _launch) and _mm, both recordable; fused_opt's _launch / _mm_now
+          dz     the IIC core writes z dP0 (launch_losses): fused_opt.FusedLinearOptTrainer.step_on_batch passes nce_fused and
+                 48 < n_clusters <= 200, FusedLinearTrainer._step_general never -- it runs joint + core and, beyond 64 output units, z dP0
+                 as a library product.  (The two have drifted apart; which one RMSprop should take is a measurement, not a refactor.)
+          dw2    dW2 = dlat^T r1 as a library product here (FusedLinearTrainer when st is None: its idl_rmsprop_step has no dW2 tiles); else
+                 it is left to the caller's last launch
+        On return dr1 and every gradient but dW1 (and dW2 unless dw2) are written: dW1 and the optimizer are the caller's ending."""
+        m, C, H1 = bf.m, self.C, self.H1
+        early = self._early(bf, st)
+        both = early and C <= 48
+        x, r1 = bf.xs[xi], bf.r1
+        _, gb1, gW2, gb2, gW3, gb3 = self.grads
+        adv_ctl, adv = (_p(self.ctl), batch_advance) if (st is not None and not early) else (None, 0)
+        # ---- forward
+        if both:    # a1^T = W1 x^T: the orientation hipBLASLt runs this product fastest in; mid_fwd adds the bias
+            mm(self.W1, x.t(), r1.view(H1, m))
+        else:
+            torch.addmm(self.b1, x, self.W1.t(), out=r1)
+        if self._cold:
+            self._evict()
+        if both:
+            self._tiles_middle(k, bf, tr, st, xi, r1)
+            return
+        if early:       # (n_clusters > 48: ALL of the next batch's tiles ride in the mid-forward launch)
+            k(_L.idl_mid_fwd_gather, _p(r1), None, 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]), 0, 8, 8, _stream())
+        elif m % 16 == 0:   # ReLU/Dropout + Linear(512,64) + head in one MFMA kernel
+            k(_L.idl_mid_fwd, _p(r1), *self._mid_fwd_args(bf, tr), _stream())
+        else:
+            k(_L.idl_relu_dropout_fwd, _p(r1), r1.numel(), tr, self.seed, _p(self.ctl), 1, _stream())
+            torch.addmm(self.b2, r1, self.W2.t(), out=bf.lat)
+            k(_L.idl_head_fwd, _p(bf.lat), _p(self.W3), _p(self.b3), m, C, tr, self.seed, _p(self.ctl), _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
+              _stream())
+        launch_losses(k, bf, self.lamb, self.weight, self.out, dz=dz)
+        # ---- backward
+        if C <= 48:     # head backward + dr1 = dlat W2 (MFMA) + ReLU/Dropout backward + every bias gradient + dW3 in one launch
+            k(_L.idl_mid_bwd, *self._mid_bwd_args(bf, tr, r1, gW3), adv_ctl, adv, _stream())
+            if dw2:
+                torch.mm(bf.dlat.t(), r1, out=gW2)
+            return
+        # (at n_clusters = 200 the per-row C x C products want all 256 CUs: separate kernels)
+        head = (_p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0])
+        rest = (_p(self.W3), m, C, tr, (1.0 - self.weight) / (m * TEMPERATURE), _p(bf.dlogits), _p(bf.dlat), _stream())
+        if dz or C > 64:    # z_partner dP0 for all rows from the IIC core, or as one GEMM, instead of 40 000 FMAs per row inside the kernel
+            if not dz:
+                torch.mm(bf.z, bf.P0, out=bf.dzs)
+            k(_L.idl_head_bwd_dz, *head, _p(bf.dzs), *rest)
+        else:
+            k(_L.idl_head_bwd, *head, _p(bf.P0), *rest)
+        torch.mm(bf.dlogits.t(), bf.r2, out=gW3)
+        if dw2:
+            torch.mm(bf.dlat.t(), r1, out=gW2)
+        torch.mm(bf.dlat, self.W2, out=bf.dr1)
+        # (one launch for the three bias gradients + the ReLU/Dropout backward of layer 1)
+        k(_L.idl_bias_grads, _p(bf.dr1), _p(r1), H1, _p(gb1), _p(bf.dlat), self.H2, _p(gb2), _p(bf.dlogits), C, _p(gb3),
+          m, tr, adv_ctl, adv, None, None, _stream())
+
     def _gather(self, store, bf):
         b = bf.m // 2
         _lib.check(_L.idl_gather_pairs_at(_p(store.feats), store.n, store.f, store.n * store.f, _p(self._perm), _p(self.ctl[1:]),
@@ -255,39 +386,14 @@ class _LinearStepParts:
 
 class FusedLinearTrainer(_LinearStepParts):
     def __init__(self, net, lr, weight, lamb, weight_decay=0.01, alpha=0.99, eps=1e-8, seed=0, grad_w1=None, shared_buffers=None):
-        lin1, lin2, lin3 = net.layers[0], net.layers[3], net.classifier[2]
-        self.net = net
-        self.W1, self.b1, self.W2, self.b2, self.W3, self.b3 = (lin1.weight, lin1.bias, lin2.weight, lin2.bias,
-                                                                  lin3.weight, lin3.bias)
-        self.params = [self.W1, self.b1, self.W2, self.b2, self.W3, self.b3]
-        self.dev = self.W1.device
-        self.F, self.H1, self.H2, self.C = lin1.in_features, lin1.out_features, lin2.out_features, lin3.out_features
-        if self.H1 != 512 or self.H2 != 64 or self.C > 256 or lin2.in_features != self.H1 or lin3.in_features != 64:
-            raise ValueError("FusedLinearTrainer needs NetLinear (hidden 512, latent 64) and n_clusters <= 256")
-        # bias gradients are kept as COL_PARTS stacked partial column sums, added up inside idl_rmsprop_step
-        self.parts = [1 if p.dim() == 2 else _L.idl_col_sum_parts() for p in self.params]
-        # the last layer's weight gradient (C x 64) is produced as partials by the middle-backward launch when C <= 48
-        if self.C <= 48:
-            self.parts[4] = _L.idl_col_sum_parts()
-        self.grads = [torch.zeros((q,) + tuple(p.shape), dtype=p.dtype, device=p.device) if q > 1 else torch.zeros_like(p)
-                      for p, q in zip(self.params, self.parts)]
-        if grad_w1 is not None:                  # this voter's slice of a BatchedLinearTrainer's stacked dW1
-            assert tuple(grad_w1.shape) == tuple(self.W1.shape) and grad_w1.is_contiguous()
-            self.grads[0] = grad_w1
-        self._shared_buffers = shared_buffers    # {m: {...}} views handed to _Buffers
+        self._init_network(net, weight, lamb, seed, grad_w1, shared_buffers)
         self._rec = None                         # a _Recorder while a BatchedLinearTrainer records this voter's launches
         self.square_avg = [torch.zeros_like(p) for p in self.params]
-        self.weight, self.lamb, self.seed = float(weight), float(lamb), int(seed) & (2 ** 64 - 1)
         self.hyper = torch.tensor([lr, alpha, eps, weight_decay, 1.0 - alpha], dtype=torch.float32, device=self.dev)
-        self.ctl = torch.zeros(2, dtype=torch.int64, device=self.dev)        # [step counter, batch offset]
-        self.out = torch.zeros(4, dtype=torch.float32, device=self.dev)      # [step loss, running sum, nce, iic]
-        self._bufs = {}
-        self._graphs = {}
         # TEST HOOK (IDELUCS_DEV=test_cold=1; tests/test_gpu_planes.py): a 512 MB fill in front of the step's middle and of each plane kernel, so that every load of
         # the hand-scheduled kernels comes from HBM instead of a warm L2/MALL -- a load consumed before its wait is right when it landed
         # early and wrong when it did not (DESIGN.md History, round 5), and only cold caches show that
         self._cold = _v("test_cold") == "1"
-        self._cold_buf = None
         # Round 5, default (IDELUCS_PLANES=0: the fp32 tiles below; csrc/planes.h): the two big products on the fp16 matrix cores from operands kept
         # as two fp16 planes (22 significand bits a factor, three products, fp32 accumulators: closer to a float64 product than an fp32 GEMM) --
         # the batch's planes written by the workgroups that assemble it, W1's by the epilogue of the dW1 tiles that update it.  A step
@@ -298,7 +404,7 @@ class FusedLinearTrainer(_LinearStepParts):
         # library GEMMs instead): the six launches of the two-plane step recorded per voter and run once for all of them, blockIdx.y = voter
         # -- the lone voters' steps bit for bit (tests/test_gpu_planes.py), 47.5 / 45.4 / 43.6 ms a voter-epoch in batches of 2 / 4 / 8
         # against 54.2 alone (fp32 GEMMs: 58.9 / 54.8 / 52.6); at 48 < n_clusters <= 200 the eight launches of _step_planes_rows the same way
-        # (_record_planes_rows_step: 58.1 / 53.9 / 51.4 ms at 200 output units against 74.6 alone, tools/bench_lockstep_rows.py)
+        # (recorded: 58.1 / 53.9 / 51.4 ms at 200 output units against 74.6 alone, tools/bench_lockstep_rows.py)
         self._planes_lockstep = _v("lockstep_planes") != "0"
         # ... and dW1 from the batch's planes too (csrc/wgrad_planes.hip); the assembling workgroups then write the planes ONLY
         self._planes_wgrad = _v("planes_wgrad") != "0"
@@ -319,13 +425,8 @@ class FusedLinearTrainer(_LinearStepParts):
         # (idl_l1_fwd_rms), where they have 30 us of slack.  A step then ends with the dW1 tiles alone; its tail is pending until the
         # next step's first launch, or flush_tail().
         self._pending = None                     # (buffers, parity) of the step whose tail has not run yet
-        self._perm = None
         n = len(self.params)
-        self._pp = (ctypes.c_void_p * n)(*[p.data_ptr() for p in self.params])
-        self._gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in self.grads])
         self._vp = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.square_avg])
-        self._sz = (ctypes.c_int64 * n)(*[p.numel() for p in self.params])
-        self._parts = (ctypes.c_int32 * n)(*self.parts)
         self._sz_no_w1 = (ctypes.c_int64 * n)(*([0] + [p.numel() for p in self.params[1:]]))     # W1 updated by idl_wgrad_rmsprop
 
     def begin_voter(self, voter, keep_state=False):
@@ -366,10 +467,9 @@ class FusedLinearTrainer(_LinearStepParts):
             return "general"
         planes = self._planes and st.n < PLANES_MAX_ROWS
         xplanes = bool(_L.idl_wgrad_xplanes_supported(m, H1, F))
-        wide = 144 <= (H1 // 64) * (F // 128) <= self._cus      # (a dW1 tile per CU, and one for each block of the tail on its loader waves)
         if self._rec is not None:
             if (self.C <= 48 and planes and self._planes_lockstep and bf.nce_fused and bool(_L.idl_l1_planes_supported(m, H1, F)) and xplanes
-                    and wide):
+                    and _tile_per_cu(H1, F, self._cus)):
                 return "record_planes"
             if (48 < self.C <= 200 and planes and self._planes_lockstep and self._planes_wgrad and self._planes_tail_wgrad and bf.nce_fused
                     and rows_shape_applies(m, H1, F, self._cus)):
@@ -393,15 +493,11 @@ class FusedLinearTrainer(_LinearStepParts):
         planes / tiles forms may leave its optimizer tail pending for the next step's first launch (flush_tail)."""
         tr, st = 1 if train else 0, next_from
         form = self._form(bf, st)
-        if form == "record_planes":
-            return self._record_planes_step(bf, tr, st, xi)
-        if form == "record_planes_rows":
-            return self._record_planes_rows_step(bf, tr, st, xi)
-        if form not in ("planes", "tiles"):
-            self.flush_tail()                   # (a step of another form: whatever is pending goes first)
-        if form == "planes":
+        if form not in ("planes", "tiles", "record_planes", "record_planes_rows"):
+            self.flush_tail()                   # (a step of another form: whatever is pending goes first; a recording touches nothing pending)
+        if form in ("planes", "record_planes"):
             self._step_planes(bf, tr, st, xi, defer_tail)
-        elif form == "planes_rows":
+        elif form in ("planes_rows", "record_planes_rows"):
             self._step_planes_rows(bf, tr, st, xi)
         elif form == "tiles":
             self._step_tiles(bf, tr, st, xi, defer_tail)
@@ -423,8 +519,7 @@ class FusedLinearTrainer(_LinearStepParts):
 
     def _reduce(self, part, m):
         """The sum of idl_l1_planes' eight K-slice partial sums, with no optimizer tail beside it."""
-        _launch(_L.idl_reduce_parts_rms, _p(part), self.H1 * m, _p(self.ctl), _p(self._ctl_snap), 0, None, None, None, None, None, None, None, None,
-                0, 0.0, 0.0, None, 0, -1, None, None, 0, 0, 0, 0, None, 0, _stream())
+        self._k(_L.idl_reduce_parts_rms, _p(part), self.H1 * m, _p(self.ctl), _p(self._ctl_snap), *_NO_TAIL, _stream())
 
     def _check_x32(self, bf, xi):
         if getattr(bf, "_planes", None) is not None and not bf._planes["x32"][xi]:
@@ -443,42 +538,60 @@ class FusedLinearTrainer(_LinearStepParts):
         if not defer_tail:
             self.flush_tail()
 
+    def _planes_operands(self, bf, pb, xi):
+        """W1's planes and the overflow flag for a two-plane step on bf.xs[xi].  A lone step makes the planes it lacks (_prepare_planes); a
+        recording performs nothing and only allocates them: BatchedLinearTrainer.run_epoch splits W1 and batch 0 after it has recorded."""
+        if self._rec is not None:
+            return self._w1_planes_of()
+        self._prepare_planes(bf, pb, xi)
+        return self._w1_planes
+
     def _step_planes(self, bf, tr, st, xi, defer_tail):
         """n_clusters <= 48, the two big products from two-plane operands: a1^T = W1 x^T as eight K-slice partial sums on the fp16 matrix
         cores, ONE launch that adds them up on every CU (beside the previous step's pending tail, if any), mid_fwd (its spare workgroups
-        assemble the first half of the next batch AND its planes), InfoNCE + IIC, mid_bwd (the other half; dr1 as planes), the dW1 tiles."""
+        assemble the first half of the next batch AND its planes), InfoNCE + IIC, mid_bwd (the other half; dr1 as planes), the dW1 tiles.
+        Lone, or recorded for BatchedLinearTrainer (self._rec: every launch through self._k becomes a record): a recording performs nothing
+        and keeps no step state, and it is always the six launches with the tail on the dW1 tiles -- _form's recording branch asks for that
+        shape and does not consult planes_wgrad / planes_tail, which choose among the lone step's endings only."""
         m, H1, F = bf.m, self.H1, self.F
+        rec = self._rec is not None
+        cold = self._cold and not rec           # (the fill is work: BatchedLinearTrainer._step evicts in front of the batched launches itself)
         pb = _planes_of(bf, F)
-        plw = self._planes_wgrad and bool(_L.idl_wgrad_xplanes_supported(m, H1, F))     # dW1 from the batch's planes: both operands by LDS-DMA
+        xplanes, wide = bool(_L.idl_wgrad_xplanes_supported(m, H1, F)), _tile_per_cu(H1, F, self._cus)
+        # (the lone-only endings below are unreachable while recording only as long as _form's recording branch asks for this shape)
+        assert not rec or (xplanes and wide), "a recorded two-plane step ends with the tail on the dW1 tiles: _form must not record another shape"
+        plw = xplanes and (rec or self._planes_wgrad)                   # dW1 from the batch's planes: both operands by LDS-DMA
+        tail_on_wgrad = plw and wide and (rec or self._planes_tail_wgrad)
         if not plw:
             self._check_x32(bf, xi)
         part, x = pb["part"][xi], bf.xs[xi]
         r1 = part[0]                            # [H1, m]: slab 0 of the partial sums, where mid_fwd leaves the activations
-        self._prepare_planes(bf, pb, xi)
-        wh, wl, flag = self._w1_planes
-        if self._cold:
+        wh, wl, flag = self._planes_operands(bf, pb, xi)
+        if cold:
             self._evict()
-        _launch(_L.idl_l1_planes, _p(wh), _p(wl), F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, _p(part), _stream())
-        if self._pending is not None:
+        self._k(_L.idl_l1_planes, _p(wh), _p(wl), F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, _p(part), _stream())
+        if self._pending is not None and not rec:       # (a recording looks at no pending tail: a lockstep voter never leaves one)
             self._tail_launch(*self._pending, red=(part, H1 * m))
         else:
             self._reduce(part, m)
-        if self._cold:
+        if cold:
             self._evict()
         nxt = (None if plw else _p(bf.xs[1 - xi]), _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
-        _launch(_L.idl_mid_fwd_gather_planes, _p(part), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
+        self._k(_L.idl_mid_fwd_gather_planes, _p(part), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
                 0, GATHER_SPLIT, 8, _stream())
-        launch_losses(_launch, bf, self.lamb, self.weight, self.out)
-        _launch(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), *nxt,
+        launch_losses(self._k, bf, self.lamb, self.weight, self.out)
+        self._k(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), *nxt,
                 GATHER_SPLIT, 8, 8, 1, *self._dr1_planes_args(pb, plw), _stream())
-        pb["valid"][1 - xi] = True
-        pb["x32"][1 - xi] = not plw
-        w1 = (self._gw1(), _p(self.W1), _p(self.square_avg[0]))
-        if plw and self._planes_tail_wgrad and 144 <= (H1 // 64) * (F // 128) <= self._cus:
+        if not rec:     # a recording assembled nothing: run_epoch records both parities between _gather (which clears valid[0]) and the split of
+            #             batch 0, so a recording at parity 1 that set valid[0] would let the first step run on stale planes
+            pb["valid"][1 - xi] = True
+            pb["x32"][1 - xi] = not plw
+        w1 = (None if rec else self._gw1(), _p(self.W1), _p(self.square_avg[0]))       # (a recorded dW1 launch never writes dW1 out)
+        if tail_on_wgrad:
             # ... and THIS step's optimizer tail is run by the tiles' loader waves under the tiles' epilogue: nothing is pending
-            if self._cold:
+            if cold:
                 self._evict()
-            _launch(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, *w1, _p(wh), _p(wl), _p(flag),
+            self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, *w1, _p(wh), _p(wl), _p(flag),
                     *self._tail(bf), 0, *self._wg(bf, r1, 1, m // 2))
             return
         if plw:
@@ -493,36 +606,41 @@ class FusedLinearTrainer(_LinearStepParts):
         the operands' roles swapped give part[8][m][512] (activations NOT transposed), mid_fwd assembles the whole next batch as planes
         only, the IIC core writes z dP0, ONE launch for the rest of the middle backward (softmax / Linear(64,C) / normalise backward per
         row, dr1 = dlat W2 as planes for the dW1 tiles, every bias gradient), dW3 on idl_at_b, and the dW1 tiles with the whole
-        optimizer tail on their loader waves end the step."""
+        optimizer tail on their loader waves end the step.  Lone, or recorded for BatchedLinearTrainer at 48 < n_clusters <= 200 (eight
+        records, ten kernels): a recording performs nothing and keeps no step state (_step_planes)."""
         m, C, H1, F = bf.m, self.C, self.H1, self.F
+        rec = self._rec is not None
+        cold = self._cold and not rec
         pb = _planes_of(bf, F)
         part = pb["part"][xi]
         r1 = part.view(-1, m, H1)[0]            # [m, H1]: slab 0 of part[8][m][512]
-        self._prepare_planes(bf, pb, xi)
-        wh, wl, flag = self._w1_planes
-        if self._cold:
+        wh, wl, flag = self._planes_operands(bf, pb, xi)
+        if cold:
             self._evict()
-        _launch(_L.idl_l1_planes, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, _p(wh), _p(wl), F, H1, m, F, _p(part), _stream())
+        self._k(_L.idl_l1_planes, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, _p(wh), _p(wl), F, H1, m, F, _p(part), _stream())
         self._reduce(part, m)
-        if self._cold:
+        if cold:
             self._evict()
         nxt = (None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
         # (the bias of Linear(F,512) is added here)
-        _launch(_L.idl_mid_fwd_gather_planes, _p(r1), _p(self.b1), 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
+        self._k(_L.idl_mid_fwd_gather_planes, _p(r1), _p(self.b1), 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
                 0, GATHER_SPLIT, 8, _stream())
-        dz = 48 < C <= 200
-        launch_losses(_launch, bf, self.lamb, self.weight, self.out, dz=dz)
+        # the core writes z dP0 up to 200 output units, a library product beyond them (lone only: _form records no wider head, and a
+        # recording takes no library product)
+        dz = rec or 48 < C <= 200
+        launch_losses(self._k, bf, self.lamb, self.weight, self.out, dz=dz)
         if not dz:
             torch.mm(bf.z, bf.P0, out=bf.dzs)
-        _launch(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, None), *self._next_batch(st, m), *nxt,
+        self._k(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, None), *self._next_batch(st, m), *nxt,
                 GATHER_SPLIT, 8, 8, 0, *self._dr1_planes_args(pb, True, bf.dzs), _stream())
-        pb["valid"][1 - xi] = True
-        pb["x32"][1 - xi] = False
-        _launch(_L.idl_at_b, _p(bf.dlogits), C, _p(bf.r2), self.H2, m, C, self.H2, _p(self.grads[4]), self.H2, _stream())      # dW3 = dlogits^T r2
-        if self._cold:
+        if not rec:     # (a recording assembled nothing: _step_planes)
+            pb["valid"][1 - xi] = True
+            pb["x32"][1 - xi] = False
+        self._k(_L.idl_at_b, _p(bf.dlogits), C, _p(bf.r2), self.H2, m, C, self.H2, _p(self.grads[4]), self.H2, _stream())      # dW3 = dlogits^T r2
+        if cold:
             self._evict()
-        _launch(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, self._gw1(), _p(self.W1),
-                _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *self._tail(bf), 0, *self._wg(bf, r1, 0, m // 2))
+        self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, None if rec else self._gw1(),
+                _p(self.W1), _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *self._tail(bf), 0, *self._wg(bf, r1, 0, m // 2))
 
     def _step_tiles(self, bf, tr, st, xi, defer_tail):
         """n_clusters <= 48 on the fp32 tiles: a1^T = W1 x^T on own tiles (the previous step's optimizer tail rides in the same launch),
@@ -536,69 +654,21 @@ class FusedLinearTrainer(_LinearStepParts):
             _launch(_L.idl_l1_fwd, _p(self.W1), _p(x), m, F, _p(r1.view(H1, m)), _stream())
         if self._cold:
             self._evict()
-        _launch(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
-                0, GATHER_SPLIT, 8, _stream())
-        launch_losses(_launch, bf, self.lamb, self.weight, self.out)
-        _launch(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
-                GATHER_SPLIT, 8, 8, 1, _stream())
+        self._tiles_middle(_launch, bf, tr, st, xi, r1)
         _launch(_L.idl_wgrad_rmsprop, _p(bf.dr1), _p(x), m, H1, F, self._gw1(), _p(self.W1), _p(self.square_avg[0]), _p(self.hyper), _stream())
         self._leave_tail_pending(bf, xi, r1, defer_tail)
 
     def _step_general(self, bf, tr, batch_advance, st, xi):
-        """Library GEMMs and the unfused kernels where a shape needs them.  A pipelined step with m % 16 == 0 has the next batch
-        assembled by its middle launches (n_clusters <= 48: both, the launches recordable for BatchedLinearTrainer; else the forward
-        alone); any other pipelined step assembles it into bf.x in its optimizer launch."""
-        m, C, H1, F = bf.m, self.C, self.H1, self.F
-        early = st is not None and m % 16 == 0 and F % 4 == 0
-        both = early and C <= 48
+        """Library GEMMs and the unfused kernels where a shape needs them (_general_fwd_bwd), then dW1 and RMSprop.  A pipelined step with
+        m % 16 == 0 has the next batch assembled by its middle launches (n_clusters <= 48: both, the launches recordable for
+        BatchedLinearTrainer; else the forward alone); any other pipelined step assembles it into bf.x in its optimizer launch."""
+        m, H1, F = bf.m, self.H1, self.F
+        early = self._early(bf, st)
+        both = early and self.C <= 48
         k = self._k if early else _launch
         self._fp32_step(bf, xi)
         x, r1 = bf.xs[xi], bf.r1
-        gW1, gb1, gW2, gb2, gW3, gb3 = self.grads
-        # ---- forward
-        if both:    # a1^T = W1 x^T: the orientation hipBLASLt runs this product fastest in; mid_fwd adds the bias
-            self._mm(self.W1, x.t(), r1.view(H1, m))
-        else:
-            torch.addmm(self.b1, x, self.W1.t(), out=r1)
-        if self._cold:
-            self._evict()
-        if both:
-            k(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
-              0, GATHER_SPLIT, 8, _stream())
-        elif early:     # (n_clusters > 48: ALL of the next batch's tiles ride in the mid-forward launch)
-            k(_L.idl_mid_fwd_gather, _p(r1), None, 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]), 0, 8, 8, _stream())
-        elif m % 16 == 0:   # ReLU/Dropout + Linear(512,64) + head in one MFMA kernel
-            k(_L.idl_mid_fwd, _p(r1), *self._mid_fwd_args(bf, tr), _stream())
-        else:
-            k(_L.idl_relu_dropout_fwd, _p(r1), r1.numel(), tr, self.seed, _p(self.ctl), 1, _stream())
-            torch.addmm(self.b2, r1, self.W2.t(), out=bf.lat)
-            k(_L.idl_head_fwd, _p(bf.lat), _p(self.W3), _p(self.b3), m, C, tr, self.seed, _p(self.ctl), _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
-              _stream())
-        launch_losses(k, bf, self.lamb, self.weight, self.out)
-        # ---- backward
-        adv_ctl, adv = (_p(self.ctl), batch_advance) if (st is not None and not early) else (None, 0)
-        nce_coef = (1.0 - self.weight) / (m * TEMPERATURE)
-        if both:
-            k(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, gW3), *self._next_batch(st, m), _p(bf.xs[1 - xi]), GATHER_SPLIT, 8, 8, 1, _stream())
-        elif C <= 48:   # head backward + dr1 = dlat W2 (MFMA) + ReLU/Dropout backward + every bias gradient + dW3 in one launch
-            k(_L.idl_mid_bwd, *self._mid_bwd_args(bf, tr, r1, gW3), adv_ctl, adv, _stream())
-            if st is None:
-                torch.mm(bf.dlat.t(), r1, out=gW2)
-        else:           # (at n_clusters = 200 the per-row C x C products want all 256 CUs: separate kernels)
-            if C > 64:      # z_partner dP0 for all rows as one GEMM instead of 40 000 FMAs per row inside the kernel
-                torch.mm(bf.z, bf.P0, out=bf.dzs)
-                k(_L.idl_head_bwd_dz, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.dzs), _p(self.W3), m, C, tr,
-                  nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream())
-            else:
-                k(_L.idl_head_bwd, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), m, C, tr,
-                  nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream())
-            torch.mm(bf.dlogits.t(), bf.r2, out=gW3)
-            if st is None:
-                torch.mm(bf.dlat.t(), r1, out=gW2)
-            torch.mm(bf.dlat, self.W2, out=bf.dr1)
-            # (one launch for the three bias gradients + the ReLU/Dropout backward of layer 1)
-            k(_L.idl_bias_grads, _p(bf.dr1), _p(r1), H1, _p(gb1), _p(bf.dlat), self.H2, _p(gb2), _p(bf.dlogits), C, _p(gb3),
-              m, tr, adv_ctl, adv, None, None, _stream())
+        self._general_fwd_bwd(bf, tr, batch_advance, st, xi, k=k, mm=self._mm, dz=False, dw2=st is None)
         # ---- dW1 on own MFMA tiles with RMSprop in their epilogue: at the head of the optimizer launch of a pipelined step, else a
         # launch of its own (a recorded step takes the tiles only inside its optimizer launch); dW1 as a GEMM where the tiles do not apply
         w1_tiles = bool(_L.idl_wgrad_supported(m, H1, F))
@@ -607,13 +677,12 @@ class FusedLinearTrainer(_LinearStepParts):
             _launch(_L.idl_wgrad_rmsprop, _p(bf.dr1), _p(x), m, H1, F, self._gw1(), _p(self.W1), _p(self.square_avg[0]), _p(self.hyper), _stream())
             sizes = self._sz_no_w1
         elif not (w1_tiles and early):
-            self._mm(bf.dr1.t(), x, gW1)
+            self._mm(bf.dr1.t(), x, self.grads[0])
         # ---- RMSprop (and advance the device-side step counter / batch offset)
         if w1_tiles and early:
             k(_L.idl_wgrad_rmsprop_step, *self._tail(bf, sizes), 0, _p(bf.dr1), _p(x), m, H1, F, self._gw1(), *self._wg(bf, r1, int(both), m // 2))
         elif early:     # no batch assembly here; the offset moves on at the end of the step
-            k(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, sizes), None, 0, 0, 0, None, 0, 0, None, None, None, None,
-              *self._wg(bf, r1, int(both), m // 2))
+            k(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, sizes), *_NO_GATHER, *self._wg(bf, r1, int(both), m // 2))
         elif st is not None:
             _launch(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, sizes), _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs,
                     m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.x), *self._wg(bf, r1, 0, 0))
@@ -627,50 +696,6 @@ class FusedLinearTrainer(_LinearStepParts):
             self._w1_planes = (torch.empty(self.W1.shape, dtype=torch.int16, device=self.dev), torch.empty(self.W1.shape, dtype=torch.int16, device=self.dev),
                                torch.zeros(1, dtype=torch.int32, device=self.dev))
         return self._w1_planes
-
-    def _record_planes_step(self, bf, tr, st, xi):
-        """The two-plane step (the planes form of a lone voter: layer-1 tiles, the sum of their partials, mid_fwd, InfoNCE + IIC,
-        mid_bwd, the dW1 tiles with the tail on their loader waves) as six RECORDED launches: BatchedLinearTrainer runs each once for all the
-        voters of a rank.  Nothing is launched here but what allocates this voter's plane buffers."""
-        m, H1, F = bf.m, self.H1, self.F
-        pb = _planes_of(bf, F)
-        wh, wl, flag = self._w1_planes_of()
-        part = pb["part"][xi]
-        r1 = part[0]
-        nxt = (None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
-        self._k(_L.idl_l1_planes, _p(wh), _p(wl), F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, _p(part), _stream())
-        self._k(_L.idl_reduce_parts_rms, _p(part), H1 * m, _p(self.ctl), _p(self._ctl_snap), 0, None, None, None, None, None, None, None, None, 0, 0.0, 0.0,
-                None, 0, -1, None, None, 0, 0, 0, 0, None, 0, _stream())
-        self._k(_L.idl_mid_fwd_gather_planes, _p(part), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
-                0, GATHER_SPLIT, 8, _stream())
-        launch_losses(self._k, bf, self.lamb, self.weight, self.out)
-        self._k(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), *nxt, GATHER_SPLIT, 8, 8, 1,
-                *self._dr1_planes_args(pb, True), _stream())
-        self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, None, _p(self.W1),
-                _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *self._tail(bf), 0, *self._wg(bf, r1, 1, m // 2))
-
-    def _record_planes_rows_step(self, bf, tr, st, xi):
-        """The two-plane step of 48 < n_clusters <= 200 (_step_planes_rows: layer-1 tiles with the roles swapped, the sum of their partials, mid_fwd,
-        InfoNCE with the joint's tiles, the IIC core with z dP0, mid_bwd, dW3, the dW1 tiles with the tail on their loader waves) as eight RECORDED
-        launches, ten kernels: BatchedLinearTrainer runs each once for all the voters of a rank.  Nothing is launched here but what allocates this
-        voter's plane buffers."""
-        m, C, H1, F = bf.m, self.C, self.H1, self.F
-        pb = _planes_of(bf, F)
-        wh, wl, flag = self._w1_planes_of()
-        part = pb["part"][xi]
-        r1 = part.view(-1, m, H1)[0]            # [m, H1]: slab 0 of part[8][m][512]
-        nxt = (None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
-        self._k(_L.idl_l1_planes, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, _p(wh), _p(wl), F, H1, m, F, _p(part), _stream())
-        self._k(_L.idl_reduce_parts_rms, _p(part), H1 * m, _p(self.ctl), _p(self._ctl_snap), 0, None, None, None, None, None, None, None, None, 0, 0.0, 0.0,
-                None, 0, -1, None, None, 0, 0, 0, 0, None, 0, _stream())
-        self._k(_L.idl_mid_fwd_gather_planes, _p(r1), _p(self.b1), 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
-                0, GATHER_SPLIT, 8, _stream())
-        launch_losses(self._k, bf, self.lamb, self.weight, self.out, dz=True)
-        self._k(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, None), *self._next_batch(st, m), *nxt, GATHER_SPLIT, 8, 8, 0,
-                *self._dr1_planes_args(pb, True, bf.dzs), _stream())
-        self._k(_L.idl_at_b, _p(bf.dlogits), C, _p(bf.r2), self.H2, m, C, self.H2, _p(self.grads[4]), self.H2, _stream())      # dW3 = dlogits^T r2
-        self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, None, _p(self.W1),
-                _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *self._tail(bf), 0, *self._wg(bf, r1, 0, m // 2))
 
     def _dr1_planes_args(self, pb, on, dzs=None):
         """idl_mid_bwd_gather_planes' last arguments: dr1's planes and the words of their scale (or none of them: dr1 in fp32), and z dP0 as an
@@ -701,7 +726,7 @@ class FusedLinearTrainer(_LinearStepParts):
             x, m1, r1T = l1
             _launch(_L.idl_l1_fwd_rms, _p(self.W1), _p(x), m1, self.F, _p(r1T), *self._tail(bf), 0, *wg)
         else:       # (sizes without W1: the tiles' own launch updated it)
-            _launch(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, self._sz_no_w1), None, 0, 0, 0, None, 0, 0, None, None, None, None, *wg)
+            _launch(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, self._sz_no_w1), *_NO_GATHER, *wg)
         self._pending = None
 
     def flush_tail(self):
@@ -722,11 +747,6 @@ class FusedLinearTrainer(_LinearStepParts):
             x = bf.xs[xi]
             _lib.check(_L.idl_split_planes(_p(x), x.numel(), int(_L.idl_planes_exponent(0)), _p(pb["xh"][xi]), _p(pb["xl"][xi]), _p(flag), _stream()))
             pb["valid"][xi] = True
-
-    def _evict(self):
-        if self._cold_buf is None:
-            self._cold_buf = torch.empty(128 << 20, dtype=torch.float32, device=self.dev)
-        self._cold_buf.fill_(1.0)
 
     def planes_overflowed(self):
         """Whether an entry of W1 (|w| >= 15.8) or of a standardised batch (|x| > 8 125: a mimic's feature thousands of the originals' standard

@@ -7,7 +7,7 @@ Nothing in the forward or backward of the fp32 step forms of fused.FusedLinearTr
 those launches with the gradient-only dW1 tiles and ONE new last launch (csrc/opt_step.hip):
     n_clusters <= 48     idl_l1_fwd -> idl_mid_fwd_gather -> InfoNCE + IIC -> idl_mid_bwd_gather -> idl_wgrad_rmsprop (gradient only)
                          -> idl_opt_step_gather_wgrad (dW2 tiles, SGD / Adam on every tensor, step loss, counters)
-    anything else        the choices of FusedLinearTrainer._step_general (library products for odd shapes and n_clusters > 48; at
+    anything else        the general form's forward and backward (_LinearStepParts._general_fwd_bwd: library products for odd shapes and n_clusters > 48; at
                          48 < n_clusters <= 200 the IIC core writes z dP0 itself), dW1 on the tiles where they apply, the same last launch
 The next batch rides in the two middle launches where it does for RMSprop.  SGD keeps momentum_buffer per tensor, RMSprop square_avg and
 momentum_buffer, Adam exp_avg and exp_avg_sq plus its step count in two words that swap roles from step to step (the launch reads one and writes the other).  The
@@ -18,12 +18,10 @@ import ctypes
 
 import torch
 
-from . import _lib
 from ._lib import lib as _L
-from .fused import GATHER_SPLIT, STEPS_PER_GRAPH, TEMPERATURE, _LinearStepParts, _launch, _p, _stream, launch_losses
+from .fused import STEPS_PER_GRAPH, _LinearStepParts, _NO_GATHER, _launch, _mm_now, _p, _stream
 
 KIND_SGD, KIND_ADAM, KIND_RMSPROP = 1, 2, 3
-_NO_GATHER = (None, 0, 0, 0, None, 0, 0, None, None, None, None)
 
 
 class FusedLinearOptTrainer(_LinearStepParts):
@@ -42,24 +40,8 @@ class FusedLinearOptTrainer(_LinearStepParts):
             raise ValueError("FusedLinearOptTrainer: centered and maximize are not supported with RMSprop")
         if grp.get('nesterov') or grp.get('dampening') or grp.get('amsgrad') or grp.get('maximize'):
             raise ValueError("FusedLinearOptTrainer: nesterov, dampening, amsgrad and maximize are not supported")
-        lin1, lin2, lin3 = net.layers[0], net.layers[3], net.classifier[2]
-        self.net, self.optimizer = net, optimizer
-        self.W1, self.b1, self.W2, self.b2, self.W3, self.b3 = lin1.weight, lin1.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias
-        self.params = [self.W1, self.b1, self.W2, self.b2, self.W3, self.b3]
-        self.dev = self.W1.device
-        self.F, self.H1, self.H2, self.C = lin1.in_features, lin1.out_features, lin2.out_features, lin3.out_features
-        if self.H1 != 512 or self.H2 != 64 or self.C > 256 or lin2.in_features != self.H1 or lin3.in_features != 64:
-            raise ValueError("FusedLinearOptTrainer needs NetLinear (hidden 512, latent 64) and n_clusters <= 256")
-        # gradients as FusedLinearTrainer keeps them: the biases (and dW3 at n_clusters <= 48, from the middle backward) as stacked partial sums
-        self.parts = [1 if p.dim() == 2 else _L.idl_col_sum_parts() for p in self.params]
-        if self.C <= 48:
-            self.parts[4] = _L.idl_col_sum_parts()
-        self.grads = [torch.zeros((q,) + tuple(p.shape), dtype=p.dtype, device=p.device) if q > 1 else torch.zeros_like(p)
-                      for p, q in zip(self.params, self.parts)]
-        self.weight, self.lamb, self.seed = float(weight), float(lamb), int(seed) & (2 ** 64 - 1)
-        self.ctl = torch.zeros(2, dtype=torch.int64, device=self.dev)        # [dropout step counter, batch offset]
-        self.out = torch.zeros(4, dtype=torch.float32, device=self.dev)      # [step loss, running sum, nce, iic]
-        self._bufs, self._graphs, self._perm, self._shared_buffers = {}, {}, None, None
+        self.optimizer = optimizer
+        self._init_network(net, weight, lamb, seed)     # (gradients as FusedLinearTrainer keeps them)
         self.state1 = [torch.zeros_like(p) for p in self.params]             # SGD: momentum_buffer; Adam: exp_avg; RMSprop: square_avg
         self.state2 = [torch.zeros_like(p) for p in self.params] if self.kind != KIND_SGD else []      # Adam: exp_avg_sq; RMSprop: momentum_buffer
         self.hyper64 = torch.zeros(5, dtype=torch.float64, device=self.dev)      # [lr, momentum | beta1, beta2 | alpha, eps, weight_decay]
@@ -67,10 +49,6 @@ class FusedLinearOptTrainer(_LinearStepParts):
         self.steps = torch.zeros(2, dtype=torch.int64, device=self.dev)          # the optimizer's step count: steps[_tpar] is current
         self._tpar = 0
         n = len(self.params)
-        self._pp = (ctypes.c_void_p * n)(*[p.data_ptr() for p in self.params])
-        self._gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in self.grads])
-        self._sz = (ctypes.c_int64 * n)(*[p.numel() for p in self.params])
-        self._parts = (ctypes.c_int32 * n)(*self.parts)
         self._s1p = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.state1])
         self._s2p = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.state2]) if self.state2 else None
         self.sync_hyper()
@@ -137,70 +115,19 @@ class FusedLinearOptTrainer(_LinearStepParts):
         (defer_tail, which _full_step passes on, has no meaning here: the step ends with its own last launch)."""
         tr, st = 1 if train else 0, next_from
         m, C, H1, F = bf.m, self.C, self.H1, self.F
-        early = st is not None and m % 16 == 0 and F % 4 == 0      # the middle launches assemble the next batch into bf.xs[1 - xi]
+        early = self._early(bf, st)                                 # the middle launches assemble the next batch into bf.xs[1 - xi]
         if not early:
             xi = 0                                                  # (otherwise the last launch does, into bf.x)
-        x, r1 = bf.xs[xi], bf.r1
-        bf._r1_transposed = early and C <= 48
-        if early and C <= 48 and _L.idl_l1_fwd_supported(m, H1, F) and _L.idl_wgrad_supported(m, H1, F):
-            _launch(_L.idl_l1_fwd, _p(self.W1), _p(x), m, F, _p(r1.view(H1, m)), _stream())
-            _launch(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
-                    0, GATHER_SPLIT, 8, _stream())
-            launch_losses(_launch, bf, self.lamb, self.weight, self.out)
-            _launch(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
-                    GATHER_SPLIT, 8, 8, 1, _stream())
-            self._dw1(bf, x)
-            self._opt(bf, r1, 1, m // 2)
-            return
-        self._step_general_opt(bf, tr, batch_advance, st, xi, early)
-
-    def _step_general_opt(self, bf, tr, batch_advance, st, xi, early):
-        """FusedLinearTrainer._step_general's forward and backward (library products and the unfused kernels where a shape needs them)."""
-        m, C, H1, F = bf.m, self.C, self.H1, self.F
         both = early and C <= 48
         x, r1 = bf.xs[xi], bf.r1
-        _, gb1, _, gb2, gW3, gb3 = self.grads
-        k = _launch
-        # ---- forward
-        if both:
-            torch.mm(self.W1, x.t(), out=r1.view(H1, m))
-            k(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]),
-              0, GATHER_SPLIT, 8, _stream())
+        bf._r1_transposed = both
+        if both and _L.idl_l1_fwd_supported(m, H1, F) and _L.idl_wgrad_supported(m, H1, F):
+            _launch(_L.idl_l1_fwd, _p(self.W1), _p(x), m, F, _p(r1.view(H1, m)), _stream())
+            self._tiles_middle(_launch, bf, tr, st, xi, r1)
         else:
-            torch.addmm(self.b1, x, self.W1.t(), out=r1)
-            if early:       # (n_clusters > 48: ALL of the next batch's tiles ride in the mid-forward launch)
-                k(_L.idl_mid_fwd_gather, _p(r1), None, 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]), 0, 8, 8, _stream())
-            elif m % 16 == 0:
-                k(_L.idl_mid_fwd, _p(r1), *self._mid_fwd_args(bf, tr), _stream())
-            else:
-                k(_L.idl_relu_dropout_fwd, _p(r1), r1.numel(), tr, self.seed, _p(self.ctl), 1, _stream())
-                torch.addmm(self.b2, r1, self.W2.t(), out=bf.lat)
-                k(_L.idl_head_fwd, _p(bf.lat), _p(self.W3), _p(self.b3), m, C, tr, self.seed, _p(self.ctl), _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z),
-                  _stream())
-        # (48 < n_clusters <= 200 with the fused InfoNCE kernels: the joint rides in InfoNCE pass 1 and the IIC core writes z dP0 -- two launches
-        #  and one library product fewer than joint + core + z dP0 as a GEMM)
-        dz = bf.nce_fused and 48 < C <= 200
-        launch_losses(k, bf, self.lamb, self.weight, self.out, dz=dz)
-        # ---- backward
-        adv_ctl, adv = (_p(self.ctl), batch_advance) if (st is not None and not early) else (None, 0)
-        nce_coef = (1.0 - self.weight) / (m * TEMPERATURE)
-        if both:
-            k(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, gW3), *self._next_batch(st, m), _p(bf.xs[1 - xi]), GATHER_SPLIT, 8, 8, 1, _stream())
-        elif C <= 48:
-            k(_L.idl_mid_bwd, *self._mid_bwd_args(bf, tr, r1, gW3), adv_ctl, adv, _stream())
-        else:
-            if dz or C > 64:
-                if not dz:
-                    torch.mm(bf.z, bf.P0, out=bf.dzs)
-                k(_L.idl_head_bwd_dz, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.dzs), _p(self.W3), m, C, tr,
-                  nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream())
-            else:
-                k(_L.idl_head_bwd, _p(bf.z), _p(bf.r2), _p(bf.f), _p(bf.inv), _p(bf.G), bf.G.shape[0], _p(bf.P0), _p(self.W3), m, C, tr,
-                  nce_coef, _p(bf.dlogits), _p(bf.dlat), _stream())
-            torch.mm(bf.dlogits.t(), bf.r2, out=gW3)
-            torch.mm(bf.dlat, self.W2, out=bf.dr1)
-            k(_L.idl_bias_grads, _p(bf.dr1), _p(r1), H1, _p(gb1), _p(bf.dlat), self.H2, _p(gb2), _p(bf.dlogits), C, _p(gb3),
-              m, tr, adv_ctl, adv, None, None, _stream())
+            # (48 < n_clusters <= 200 with the fused InfoNCE kernels: the joint rides in InfoNCE pass 1 and the IIC core writes z dP0 -- two
+            #  launches and one library product fewer than joint + core + z dP0 as a GEMM, which FusedLinearTrainer._step_general still runs)
+            self._general_fwd_bwd(bf, tr, batch_advance, st, xi, k=_launch, mm=_mm_now, dz=bf.nce_fused and 48 < C <= 200, dw2=False)
         # ---- dW1, then the optimizer (dW2 inside its launch)
         self._dw1(bf, x)
         if early:

@@ -1,5 +1,6 @@
 """Lockstep training of a rank's voters at 48 < n_clusters <= 200 (the fine-grained mode's 200 output units): the eight launches of the
-two-plane step of FusedLinearTrainer._step_planes_rows recorded per voter and run once for all voters (BatchedLinearTrainer).  The batched
+two-plane step of FusedLinearTrainer._step_planes_rows, the body the lone voters run, recorded per voter and run once for all voters
+(BatchedLinearTrainer); and the six of _step_planes at n_clusters <= 48 held to the same bits.  The batched
 kernels are the lone kernels' bodies on a voter's record, so everything here is compared with torch.equal, never within a tolerance.  Reference: the step of
 idelucs/models.py:117-133, one voter after the other (idelucs/__main__.py:100-123)."""
 import copy
@@ -35,7 +36,8 @@ def _variants():
 
 def _lockstep_is_lone(dev, monkeypatch, n, graph, lanes, C=200):
     """An epoch of `lanes` voters (weights scaled apart, dropout on, a generator each) alone and in lockstep: every parameter, every RMSprop running
-    average, the loss sum and ctl are the same bits.  -> the batched trainer."""
+    average, the loss sum and ctl are the same bits.  The form and the records per parity follow from C: planes_rows and eight beyond 48 output
+    units, planes and six up to them.  -> the batched trainer."""
     import torch
     import test_gpu_encoder as E
     from idelucs_amd.fused import FusedLinearTrainer, BatchedLinearTrainer
@@ -43,6 +45,7 @@ def _lockstep_is_lone(dev, monkeypatch, n, graph, lanes, C=200):
     monkeypatch.setitem(_variants(), "lockstep_planes", "1")
     store, net0 = E._cfg2_store_and_net(dev, n, seed=4, C=C)
     B = 512
+    form, records = ("planes_rows", 8) if C > 48 else ("planes", 6)
     nets_a, nets_b = [], []
     for l in range(lanes):
         net = copy.deepcopy(net0)
@@ -55,7 +58,7 @@ def _lockstep_is_lone(dev, monkeypatch, n, graph, lanes, C=200):
     for l, net in enumerate(nets_a):
         tr = FusedLinearTrainer(net, lr=1e-3, weight=0.25, lamb=2.8, seed=11)
         tr.begin_voter(l)
-        assert tr._form(tr.buffers(2 * B), store) == "planes_rows"
+        assert tr._form(tr.buffers(2 * B), store) == form
         gen = torch.Generator(device=dev); gen.manual_seed(100 + l)
         total, nb = tr.run_epoch(store, B, use_graph=graph, generator=gen)
         torch.cuda.synchronize()
@@ -70,10 +73,10 @@ def _lockstep_is_lone(dev, monkeypatch, n, graph, lanes, C=200):
         gens.append(g)
     res = bt.run_epoch(store, B, gens, use_graph=graph)
     torch.cuda.synchronize()
-    # the feature was exercised: the recorded two-plane step, eight records per parity, nothing left the planes' range, one captured graph
+    # the feature was exercised: the recorded two-plane step, eight (six) records per parity, nothing left the planes' range, one captured graph
     assert bt._planes_step and bt.L == lanes
     prog = next(iter(bt._programs.values()))
-    assert [len(ops) for ops in prog] == [8, 8]
+    assert [len(ops) for ops in prog] == [records, records]
     assert not any(t.planes_overflowed() for t in bt.trainers) and not bt.planes_overflowed()
     assert len(bt._graphs) == (1 if graph else 0)
     for l, ((total, nb), tr) in enumerate(zip(res, bt.trainers)):
@@ -102,6 +105,13 @@ def test_lockstep_voters_at_200_units_are_the_lone_voters(dev, monkeypatch, n, g
     24 full batches of 512 + a partial one, dropout on), launch by launch or as a captured graph, leaves the lone voters' bits in every parameter,
     every RMSprop running average, the loss sum and the counters."""
     _lockstep_is_lone(dev, monkeypatch, n, graph, lanes)
+
+
+@pytest.mark.parametrize("n,graph,lanes,C", [(1500, False, 3, 20), (4200, True, 2, 20)])
+def test_lockstep_voters_at_20_units_are_the_lone_voters(dev, monkeypatch, n, graph, lanes, C):
+    """The same at n_clusters <= 48: the six launches of _step_planes recorded and run once for all voters leave the lone voters' bits (the lone
+    step and the recorded one are one body, so what tests/test_gpu_encoder.py holds within a tolerance for both lockstep forms is held exactly here)."""
+    _lockstep_is_lone(dev, monkeypatch, n, graph, lanes, C=C)
 
 
 def test_cold_caches_leave_lockstep_voters_at_200_units_the_lone_voters(dev, monkeypatch):
