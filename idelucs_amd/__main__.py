@@ -196,12 +196,18 @@ def run(args):
         print("stages: " + ", ".join(f"{name} {t1 - t0:.1f} s" for (_, t0), (name, t1) in zip(marks[:-1], marks[1:])))
 
     if args.get("plot"):
+        emb = None
         try:
             import umap
         except ImportError:
-            print("--plot needs the `umap-learn` package (reference __main__.py:239); skipping the plot")
+            # reference __main__.py:239 needs `umap-learn`; without it the same picture from the embedding built here
+            if len(latent) <= posthoc.UMAP_NEIGHBORS:
+                print(f"--plot: {len(latent)} points are too few for an embedding with {posthoc.UMAP_NEIGHBORS} neighbours; skipping the plot")
+            else:
+                emb = posthoc.umap_embedding_device(latent, n_neighbors=posthoc.UMAP_NEIGHBORS, seed=42, device=model.device)
         else:
             emb = umap.UMAP(random_state=42).fit_transform(latent)
+        if emb is not None:
             fig, ax = plt.subplots(nrows=1, ncols=1)
             ax.set_title("Representation of the Latent Space"); ax.set_xlabel("UMAP 1"); ax.set_ylabel("UMAP 2")
             ax.scatter(emb[:, 0], emb[:, 1], c=y_pred, s=1, alpha=0.5)

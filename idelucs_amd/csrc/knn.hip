@@ -390,6 +390,63 @@ __global__ __launch_bounds__(256) void silhouette_sums_kernel(SilArgs a)
     flush(cur_c);
 }
 
+
+// ---------------------------------------------------------------- kNN graph: the k nearest of every row WITH their indices (posthoc.knn_graph_device)
+// idl_knn_window has kept, for every row, the columns whose computed squared distance came out under hi = (exact k-th distance)^2 plus a
+// margin of at least the pass's delta: every column at or inside the k-th distance is among them, whatever the Gram form's rounding did.
+// One wave per row forms their float64 distances (difference vector, coordinate by coordinate, product and sum each rounded, one
+// correctly rounded sqrt: idl_knn_select's form), ranks them by (distance, original index) and writes the first k.
+constexpr int GRAPH_CAP = 512;    // kept columns a row can bring
+
+struct GraphArgs {
+    const float *x;               // [n, 64] the points in the window pass's (padded) order
+    const int32_t *orig;          // [n] original index of each position, -1 for padding
+    const double *kth;            // [n] exact k-th neighbour distance of each position
+    const float *hi, *delta;      // per row of this launch
+    int64_t n, row0, rows; int k;
+    const int32_t *cand_cnt, *cand_idx; int cap;
+    int32_t *out_idx; double *out_dist;    // [points, k], indexed by ORIGINAL row
+    int32_t *status;              // per row of this launch: 0 done; 2 slot full; 3 margin under delta; 5 the kept columns do not hold the k nearest
+};
+
+__global__ __launch_bounds__(256) void knn_graph_kernel(GraphArgs a)
+{
+    __shared__ double val[4][GRAPH_CAP];
+    __shared__ int32_t oix[4][GRAPH_CAP];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t rloc = (int64_t)blockIdx.x * 4 + wv, row = a.row0 + rloc;
+    const bool inside = rloc < a.rows;
+    const int me = inside ? a.orig[row] : -1;
+    int cnt = 0, st = 0;
+    if (me >= 0) {
+        cnt = a.cand_cnt[rloc];
+        const double kd = a.kth[row];
+        if (cnt > a.cap) { st = 2; cnt = 0; }
+        else if (!(kd * kd + (double)a.delta[rloc] <= (double)a.hi[rloc])) { st = 3; cnt = 0; }
+        else if (cnt < a.k) { st = 5; cnt = 0; }
+    }
+    const int32_t *ix = a.cand_idx + rloc * a.cap;
+    for (int p = lane; p < cnt; p += 64) {
+        const int64_t j = ix[p];
+        const float *pa = a.x + row * KD, *pb = a.x + j * KD;
+        double d = 0.0;
+        for (int c = 0; c < KD; ++c) { const double t = (double)pa[c] - (double)pb[c]; d = idl_dev::square_then_add(d, t); }
+        val[wv][p] = __dsqrt_rn(d); oix[wv][p] = a.orig[j];
+    }
+    __syncthreads();
+    for (int p = lane; p < cnt; p += 64) {
+        const double mv = val[wv][p];
+        const int32_t mi = oix[wv][p];
+        int r = 0;
+        for (int o = 0; o < cnt; ++o) { const double ov = val[wv][o]; r += (ov < mv || (ov == mv && oix[wv][o] < mi)) ? 1 : 0; }
+        if (r < a.k) { a.out_idx[(int64_t)me * a.k + r] = mi; a.out_dist[(int64_t)me * a.k + r] = mv; }
+        if (r == a.k - 1 && mv != a.kth[row]) st = 5;
+    }
+    st = max(st, __shfl_xor(st, 1, 64)); st = max(st, __shfl_xor(st, 2, 64)); st = max(st, __shfl_xor(st, 4, 64));
+    st = max(st, __shfl_xor(st, 8, 64)); st = max(st, __shfl_xor(st, 16, 64)); st = max(st, __shfl_xor(st, 32, 64));
+    if (inside && lane == 0) a.status[rloc] = st;
+}
+
 }  // namespace
 
 extern "C" {
@@ -429,6 +486,20 @@ int idl_silhouette_sums(const float *x, const float *w, const int32_t *tile_clus
     IDL_REQUIRE((((uintptr_t)x) & 15u) == 0, "silhouette_sums: x must be 16-byte aligned");
     SilArgs a{x, w, tile_cluster, n, n_clusters, sums};
     hipLaunchKernelGGL(silhouette_sums_kernel, dim3((unsigned)((n + ROWS_WG - 1) / ROWS_WG)), dim3(256), 0, (hipStream_t)stream, a);
+    IDL_HIP_TRY(hipGetLastError());
+    return IDL_OK;
+}
+
+int idl_knn_graph(const float *x, const int32_t *orig, const double *kth, int64_t n, int d, const float *hi, const float *delta, int64_t row0,
+                  int64_t rows, int k, const int32_t *cand_cnt, const int32_t *cand_idx, int cap, int32_t *out_idx, double *out_dist,
+                  int32_t *status, void *stream)
+{
+    IDL_REQUIRE(x && orig && kth && hi && delta && cand_cnt && cand_idx && out_idx && out_dist && status, "knn_graph: NULL buffer");
+    IDL_REQUIRE(d == KD, "knn_graph: points must have 64 coordinates");
+    IDL_REQUIRE(n >= 1 && n < (1ll << 31) && row0 >= 0 && rows >= 1 && row0 + rows <= n && k >= 1 && k <= n, "knn_graph: bad sizes");
+    IDL_REQUIRE(cap >= 1 && cap <= GRAPH_CAP && k <= cap, "knn_graph: needs k <= cap <= 512");
+    GraphArgs a{x, orig, kth, hi, delta, n, row0, rows, k, cand_cnt, cand_idx, cap, out_idx, out_dist, status};
+    hipLaunchKernelGGL(knn_graph_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }

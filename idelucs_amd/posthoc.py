@@ -5,7 +5,7 @@ on the host with sklearn/scipy, as in the reference, on the outputs gathered fro
 import os
 
 # Variants kept for the tests that compare them with the default path (not environment switches; a test sets an entry with monkeypatch.setitem)
-OPTIONS = {"knn": "",            # matrix | window: force one of the core-distance paths
+OPTIONS = {"knn": "",            # matrix | window: force one of the core-distance / kNN-graph paths
            "mst": "lazy",        # lazy | local | plain: which Prim
            "mst_filter": "1",    # 0: no 8-bit lower bound in front of the exact distances
            "silhouette": "",     # gemm: the float64 GEMM form instead of the one-pass kernel
@@ -555,6 +555,324 @@ def core_distances_device(x64, k, device, f32_exact=None, stats=None, order=None
     elif todo.numel():
         _core_distances_rows(x64, sq, todo, k, device, core)
     return core
+
+
+KNN_GRAM_ERR = 144.0 * 2.0 ** -23      # csrc/knn.hip GRAM_ERR: idl_knn_window's rounding bound per unit of |a - m|^2 + |b - m|^2
+KNN_GRAPH_CAP = 512                    # kept columns a row of the window route can bring (idl_knn_graph's LDS; csrc/knn.hip GRAPH_CAP)
+KNN_GRAPH_K_MAX = 128                  # neighbours the window route of knn_graph_device takes
+
+
+KNN_MATRIX_ERR = 1e-13                 # float64 Gram form of centred points: |computed - true d^2| <= this * (|a|^2 + max |b|^2) (64-term sums: 3e-14)
+
+
+def _knn_graph_rows(x64, rows_idx, k, device, idx_out, dist_out, stats=None):
+    """The kNN graph of the rows `rows_idx` (None = all) by the float64 matrix: row blocks of the Gram-form squared distances (centred
+    points, one GEMM each) FIND a shortlist of the k + pad nearest columns; their exact distances (_distance_in_sklearns_order)
+    sorted by (distance, index) are the result -- once the shortlist is CLOSED: every column outside it has a Gram value of at least
+    the shortlist's largest, g, so it can neither beat nor tie the k-th exact neighbour when (k-th exact distance)^2 < g - the Gram
+    form's error.  A row whose shortlist is not closed (more than pad columns tied at or inside its k-th distance: many exact
+    copies of one point, of which topk keeps an arbitrary subset) is taken again with pad 8 times as wide, until closed or until the
+    shortlist holds every column."""
+    import torch
+    n = x64.shape[0]
+    todo = torch.arange(n, device=device) if rows_idx is None else rows_idx
+    xc = x64 - x64.mean(0, keepdim=True)
+    sq = (xc * xc).sum(1)
+    sq_max = sq.max()
+    xt = xc.t()
+    pad = min(32, n - k)
+    while todo.numel():
+        m = int(todo.numel())
+        rows = max(1, min(m, (1 << 30) // max(n, 1), (1 << 31) // (8 * x64.shape[1] * (k + pad))))     # 8 GB of distances, 2 GB of exact operands
+        open_rows = []
+        for lo in range(0, m, rows):
+            ridx = todo[lo:lo + rows]
+            d2 = torch.mm(xc[ridx], xt).mul_(-2.0).add_(sq[None, :]).add_(sq[ridx, None])
+            d2[torch.arange(ridx.numel(), device=device), ridx] = -1.0     # a point is its own neighbour whatever the rounding
+            vals, cols = torch.topk(d2, k + pad, dim=1, largest=False, sorted=False)
+            g = vals.max(1).values
+            cols = cols.sort(1).values
+            del d2, vals
+            xb = x64[ridx]
+            ex = _distance_in_sklearns_order(xb[:, None, :].expand(-1, cols.shape[1], -1).reshape(-1, xb.shape[1]),
+                                             x64[cols.reshape(-1)]).view(xb.shape[0], -1)
+            order = torch.argsort(ex, dim=1, stable=True)[:, :k]             # columns ascending, stable: ties by ascending index
+            dk = ex.gather(1, order[:, -1:]).squeeze(1)
+            closed = (dk * dk < g - KNN_MATRIX_ERR * (sq[ridx] + sq_max)) if k + pad < n else torch.ones_like(dk, dtype=torch.bool)
+            done = ridx[closed]
+            idx_out[done] = cols.gather(1, order)[closed].to(torch.int32)
+            dist_out[done] = ex.gather(1, order)[closed]
+            open_rows.append(ridx[~closed])
+            del cols, ex, order
+        todo = torch.cat(open_rows)
+        if stats is not None and todo.numel():
+            stats["matrix_widened"] = stats.get("matrix_widened", 0) + int(todo.numel())
+        pad = min(8 * max(pad, 1), n - k)
+
+
+def _knn_graph_window(x64, k, core, device, idx_out, dist_out, stats=None, order=None):
+    """The kNN graph behind the exact k-th distances `core` (csrc/knn.hip): the points in _spatial_order's memory order, every group
+    padded to whole waves; ONE idl_knn_window pass that keeps every column under hi = core^2 + margin (lo below everything: the
+    Gram form may put the point itself slightly under 0, and a column under lo is counted, not kept); idl_knn_graph ranks the kept
+    columns by their exact distances.  margin = 2 GRAM_ERR (|a - m|^2 + 4 R^2), R = |a - m| + core: the pass's own bound
+    delta = 2 GRAM_ERR (|a - m|^2 + 1.001 (|a - m| + sqrt(hi))^2) stays under it, since sqrt(hi) <= core + 0.014 R
+    (idl_knn_graph checks hi - core^2 >= delta per row all the same), and hi >= 1e-30 so that it lies above the exact zeros of copies.  -> the rows to recompute (status != 0), int64."""
+    import ctypes
+    import torch
+    from . import _lib
+    L = _lib.lib
+    vp = ctypes.c_void_p
+    n, d = x64.shape
+    perm, gid = order if order is not None else _spatial_order(x64)
+    counts = torch.bincount(gid)
+    padded = (counts + 63) // 64 * 64
+    first, start = torch.cumsum(counts, 0) - counts, torch.cumsum(padded, 0) - padded
+    pos = start[gid] + (torch.arange(n, device=device) - first[gid])
+    npad = int(padded.sum())
+    xo = x64[perm]
+    centre = torch.empty(npad, dtype=torch.int64, device=device)
+    centre[pos] = torch.arange(n, device=device)
+    centre = centre[pos // 64 * 64]                              # memory-order index of the first row of every row's wave (a point of the same group)
+    sqa = (xo - xo[centre]).pow_(2).sum(1)
+    core_o = core[perm]
+    R = sqa.sqrt() + core_o
+    hi = core_o * core_o + 2.0 * KNN_GRAM_ERR * (sqa + 4.0 * R * R)
+    hi.clamp_min_(1.0e-30)                                       # k copies of a wave's own first row: core = |a - m| = 0 and the computed values are exactly 0 -- hi must lie above them
+    hi32 = hi.to(torch.float32)
+    hi32 = torch.where(hi32.double() < hi, torch.nextafter(hi32, torch.full_like(hi32, float("inf"))), hi32)
+    x32 = torch.zeros((npad, d), dtype=torch.float32, device=device)
+    x32[:, 0] = 1.0e18                                           # padding: infinitely far from everything
+    x32[pos] = xo.to(torch.float32)
+    lo_p = torch.full((npad,), -1.0e30, dtype=torch.float32, device=device)
+    hi_p = torch.full((npad,), -1.0, dtype=torch.float32, device=device)
+    hi_p[pos] = hi32
+    kth_p = torch.zeros(npad, dtype=torch.float64, device=device)
+    kth_p[pos] = core_o
+    orig = torch.full((npad,), -1, dtype=torch.int32, device=device)
+    orig[pos] = perm.to(torch.int32)
+    del xo, sqa, R, hi, hi32, core_o, centre
+    cap = KNN_GRAPH_CAP
+    chunk = max(256, min(-(-npad // 256) * 256, (KNN_SLOT_BYTES // (8 * cap)) // 256 * 256))
+    cand_d2 = torch.empty(chunk * cap, dtype=torch.float32, device=device)
+    cand_ix = torch.empty(chunk * cap, dtype=torch.int32, device=device)
+    delta = torch.empty(chunk, dtype=torch.float32, device=device)
+    cnt_lo = torch.empty(chunk, dtype=torch.int32, device=device)
+    cnt_in = torch.empty(chunk, dtype=torch.int32, device=device)
+    status_p = torch.zeros(npad, dtype=torch.int32, device=device)
+    stream = vp(torch.cuda.current_stream().cuda_stream)
+    for row0 in range(0, npad, chunk):
+        rows = min(chunk, npad - row0)
+        _lib.check(L.idl_knn_window(vp(x32.data_ptr()), npad, d, vp(lo_p[row0:].data_ptr()), vp(hi_p[row0:].data_ptr()), row0, rows, vp(cnt_lo.data_ptr()),
+                                    vp(cnt_in.data_ptr()), vp(delta.data_ptr()), vp(cand_d2.data_ptr()), vp(cand_ix.data_ptr()), cap, stream))
+        _lib.check(L.idl_knn_graph(vp(x32.data_ptr()), vp(orig.data_ptr()), vp(kth_p.data_ptr()), npad, d, vp(hi_p[row0:].data_ptr()), vp(delta.data_ptr()),
+                                   row0, rows, k, vp(cnt_in.data_ptr()), vp(cand_ix.data_ptr()), cap, vp(idx_out.data_ptr()), vp(dist_out.data_ptr()),
+                                   vp(status_p[row0:].data_ptr()), stream))
+        if stats is not None:
+            stats["graph_kept_max"] = max(stats.get("graph_kept_max", 0), int(cnt_in[:rows].max()))
+    status = status_p[pos]
+    missed = perm[torch.nonzero(status).squeeze(1)]
+    if stats is not None:
+        stats.update(graph_cap=cap, graph_missed=int(missed.numel()), graph_status_counts=torch.bincount(status, minlength=6).tolist())
+    return missed
+
+
+def knn_graph_device(x, k, device=None, stats=None):
+    """The exact k-nearest-neighbour graph of the points x [N, d] rounded to float32 -> (idx int32 [N, k], dist float64 [N, k]),
+    numpy.  Row i lists its k nearest points INCLUDING ITSELF (sklearn's kneighbors(X) on its own training set), by ascending
+    distance, ties -- also across the k-th place -- by ascending index; the distances are the float64 `t = a - b; d += t * t` over
+    the coordinates in order, without contraction, and one correctly rounded sqrt (idl_knn_select's form).
+    Two routes, as core_distances_device ($IDELUCS_DEV=knn = matrix | window forces one):
+      matrix  (below KNN_WINDOW_MIN points, other widths than 64, k > KNN_GRAPH_K_MAX) the float64 Gram matrix in row blocks finds
+              a shortlist of k + 32 columns per row -- wider where ties leave it open -- whose exact distances are sorted (_knn_graph_rows);
+      window  core_distances_device for the exact k-th distance, one more idl_knn_window pass that keeps everything up to it, and
+              idl_knn_graph to rank what was kept (_knn_graph_window); a row it flags (more than KNN_GRAPH_CAP columns kept: that many
+              copies of one point) goes through the matrix route (stats["graph_missed"] counts them).
+    tests/test_gpu_embedding.py holds both to tests/umap_ref.py bit for bit."""
+    import torch
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    pts = np.asarray(x.detach().cpu() if torch.is_tensor(x) else x)
+    if pts.ndim != 2:
+        raise ValueError("knn_graph_device: the points must be [N, d]")
+    n, d = pts.shape
+    k = int(k)
+    mode = OPTIONS["knn"]
+    if k < 2 or k > n:
+        raise ValueError(f"knn_graph_device: needs 2 <= k <= N (k = {k}, N = {n})")
+    if mode == "window" and d != 64:
+        raise ValueError("knn_graph_device: the window route needs 64 coordinates (IDELUCS_DEV=knn=window)")
+    if mode == "window" and k > KNN_GRAPH_K_MAX:
+        raise ValueError(f"knn_graph_device: the window route takes k <= {KNN_GRAPH_K_MAX} (IDELUCS_DEV=knn=window)")
+    pts = np.ascontiguousarray(pts.astype(np.float32))
+    if not np.all(np.isfinite(pts)):
+        raise ValueError("knn_graph_device: non-finite coordinates")
+    x64 = torch.from_numpy(pts).to(dev).double()
+    idx = torch.empty((n, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((n, k), dtype=torch.float64, device=dev)
+    todo = None
+    if mode != "matrix" and d == 64 and k <= KNN_GRAPH_K_MAX and (n >= KNN_WINDOW_MIN or mode == "window"):
+        order = _spatial_order(x64)                              # one memory order for both passes
+        core = core_distances_device(x64, k, dev, f32_exact=True, stats=stats, order=order)
+        todo = _knn_graph_window(x64, k, core, dev, idx, dist, stats=stats, order=order)
+    if stats is not None:
+        stats["graph_path"] = "matrix" if todo is None else "window"
+    if todo is None or todo.numel():
+        _knn_graph_rows(x64, todo, k, dev, idx, dist, stats=stats)
+    return idx.cpu().numpy(), dist.cpu().numpy()
+
+
+UMAP_NEIGHBORS = 15                    # umap-learn's default n_neighbors, what the reference's umap.UMAP(random_state=42) takes
+
+
+def umap_ab_params(min_dist=0.1, spread=1.0):
+    """The curve constants a, b of 1 / (1 + a x^(2b)), fitted as umap-learn's find_ab_params does: scipy.optimize.curve_fit on 300
+    points of [0, 3 spread] against 1 for x < min_dist, exp(-(x - min_dist) / spread) beyond."""
+    from scipy.optimize import curve_fit
+    xv = np.linspace(0, spread * 3, 300)
+    yv = np.where(xv < min_dist, 1.0, np.exp(-(xv - min_dist) / spread))
+    params, _ = curve_fit(lambda x_, a, b: 1.0 / (1.0 + a * x_ ** (2 * b)), xv, yv)
+    return float(params[0]), float(params[1])
+
+
+def umap_default_epochs(n):
+    """umap-learn's rule: 500 epochs up to 10 000 points, 200 beyond."""
+    return 500 if n <= 10000 else 200
+
+
+def umap_smooth_knn_device(idx, dist, device=None):
+    """UMAP's per-row calibration of a kNN graph (idl_umap_smooth_knn, csrc/embed.hip) -> (rho [N], sigma [N], w [N, k]) float64
+    device tensors; idx int32 / dist float64 [N, k] as knn_graph_device returns them."""
+    import ctypes
+    import torch
+    from . import _lib
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    idx_t = torch.as_tensor(idx).to(dev, torch.int32).contiguous()
+    dist_t = torch.as_tensor(dist).to(dev, torch.float64).contiguous()
+    n, k = dist_t.shape
+    if idx_t.shape != dist_t.shape or k < 2 or k > n:
+        raise ValueError("umap_smooth_knn_device: idx and dist must be [N, k] with 2 <= k <= N")
+    rho = torch.empty(n, dtype=torch.float64, device=dev)
+    sigma = torch.empty(n, dtype=torch.float64, device=dev)
+    w = torch.empty((n, k), dtype=torch.float64, device=dev)
+    vp = ctypes.c_void_p
+    _lib.check(_lib.lib.idl_umap_smooth_knn(vp(dist_t.data_ptr()), vp(idx_t.data_ptr()), n, k, float(dist_t.mean()), vp(rho.data_ptr()), vp(sigma.data_ptr()),
+                                            vp(w.data_ptr()), vp(torch.cuda.current_stream().cuda_stream)))
+    return rho, sigma, w
+
+
+def umap_fuzzy_union_device(idx, w, n_epochs):
+    """The fuzzy union P = A + A^T - A o A^T of the directed weights w [N, k] on the edges (i, idx[i, j]), pruned of the entries
+    below max(P) / n_epochs, as a CSR with both directions of every edge -> (indptr int64 [N + 1], indices int32, P float64), device
+    tensors.  P_jk and P_kj come out of the same commutative expression -- (a + b) - a * b with the two directed weights in either
+    order, three roundings -- so they are the same bits: the layout's schedule relies on it."""
+    import torch
+    n, k = w.shape
+    dev = w.device
+    rows = torch.arange(n, device=dev, dtype=torch.int64)[:, None].expand(-1, k).reshape(-1)
+    cols = idx.to(torch.int64).reshape(-1)
+    wv = w.reshape(-1)
+    keep = wv > 0.0
+    rows, cols, wv = rows[keep], cols[keep], wv[keep]
+    keys, inv = torch.unique(torch.cat([rows * n + cols, cols * n + rows]), return_inverse=True)
+    m = rows.numel()
+    a = torch.zeros(keys.numel(), dtype=torch.float64, device=dev)
+    b = torch.zeros(keys.numel(), dtype=torch.float64, device=dev)
+    a[inv[:m]] = wv                                              # A_jk at key (j, k)
+    b[inv[m:]] = wv                                              # A_kj at key (j, k)
+    p = a + b
+    p -= a * b
+    keep = p >= p.max() / float(n_epochs)
+    keys, p = keys[keep], p[keep]
+    r = keys // n
+    indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    indptr[1:] = torch.cumsum(torch.bincount(r, minlength=n), 0)
+    return indptr, (keys - r * n).to(torch.int32), p
+
+
+def umap_pca_start_device(x64, seed):
+    """The layout's start: the first two principal components of the points (float64 covariance, torch.linalg.eigh of the d x d matrix on
+    the host, signs fixed so that each component's largest-magnitude entry is positive), scaled so that the largest |coordinate| is 10,
+    float32, plus idl_umap_jitter's 1e-4 so that duplicates separate -> float32 [N, 2] device tensor."""
+    import ctypes
+    import torch
+    from . import _lib
+    n = x64.shape[0]
+    xc = x64 - x64.mean(0, keepdim=True)
+    cov = (xc.t() @ xc) / max(n - 1, 1)
+    evals, evecs = torch.linalg.eigh(cov.cpu())
+    v = evecs[:, [-1, -2]]                                       # (ascending eigenvalues: the two largest)
+    top = v[v.abs().argmax(0), torch.arange(2)]
+    v = v * torch.where(top < 0, -1.0, 1.0).to(v.dtype)[None, :]
+    y = xc @ v.to(x64.device)
+    top = float(y.abs().max())
+    y = (y * (10.0 / top if top > 0 else 1.0)).to(torch.float32).contiguous()
+    _lib.check(_lib.lib.idl_umap_jitter(ctypes.c_void_p(y.data_ptr()), n, 1e-4, int(seed) & (2 ** 64 - 1), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return y
+
+
+def umap_layout_device(y0, indptr, indices, p, n_epochs, a, b, seed, first_epoch=1, last_epoch=None, state=None):
+    """Epochs first_epoch .. last_epoch (default n_epochs) of the layout (idl_umap_layout_epoch, one launch each) from the positions
+    y0 (float32 [N, 2], device) on the pruned union (indptr, indices, p) -> (positions float32 [N, 2], (eps, next, next_neg)).
+    state = (next, next_neg) float64 per directed entry to continue from; default the start of a run, (eps, eps / 5)."""
+    import ctypes
+    import torch
+    from . import _lib
+    vp = ctypes.c_void_p
+    n = y0.shape[0]
+    eps = (p.max() / p).contiguous() if p.numel() else p.clone()
+    nxt, nneg = (eps.clone(), eps / 5.0) if state is None else (state[0].clone(), state[1].clone())
+    bufs = [y0.to(torch.float32).contiguous().clone(), torch.empty((n, 2), dtype=torch.float32, device=y0.device)]
+    indptr, indices = indptr.contiguous(), indices.contiguous()
+    stream = vp(torch.cuda.current_stream().cuda_stream)
+    cur = 0
+    for epoch in range(first_epoch, (n_epochs if last_epoch is None else last_epoch) + 1):
+        alpha = 1.0 - (epoch - 1) / float(n_epochs)
+        _lib.check(_lib.lib.idl_umap_layout_epoch(vp(bufs[cur].data_ptr()), vp(bufs[1 - cur].data_ptr()), n, vp(indptr.data_ptr()), vp(indices.data_ptr()),
+                                                  vp(eps.data_ptr()), vp(nxt.data_ptr()), vp(nneg.data_ptr()), epoch, alpha, a, b,
+                                                  int(seed) & (2 ** 64 - 1), stream))
+        cur = 1 - cur
+    return bufs[cur], (eps, nxt, nneg)
+
+
+def umap_embedding_device(latent, n_neighbors=UMAP_NEIGHBORS, min_dist=0.1, n_epochs=None, seed=42, device=None, stats=None):
+    """A UMAP-style 2-D embedding of the latent [N, d] on the GPU -> float64 [N, 2]: the exact kNN graph
+    (knn_graph_device), UMAP's calibration (idl_umap_smooth_knn; 64 fixed bisection rounds), the fuzzy union pruned at
+    max(P) / n_epochs, a PCA start, and n_epochs Jacobi sweeps of optimize_layout_euclidean with counter-based draws
+    (idl_umap_layout_epoch).  The same latent, parameters, seed and device give the same bits on every run.  n_epochs defaults to
+    umap-learn's rule (500 up to 10 000 points, 200 beyond).  stats (a dict) receives the three stages' times."""
+    import time
+    import torch
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    pts = np.ascontiguousarray(np.asarray(latent, dtype=np.float32))
+    n = pts.shape[0]
+    k = int(n_neighbors)
+    if pts.ndim != 2 or k < 2 or n <= k:
+        raise ValueError(f"umap_embedding_device: needs [N, d] points with N > n_neighbors >= 2 (N = {n}, n_neighbors = {k})")
+    n_epochs = umap_default_epochs(n) if n_epochs is None else int(n_epochs)
+    if n_epochs < 1:
+        raise ValueError("umap_embedding_device: n_epochs must be positive")
+    a, b = umap_ab_params(min_dist, 1.0)
+
+    def lap(name, t0):
+        if stats is not None:
+            torch.cuda.synchronize(dev)
+            stats[name] = time.time() - t0
+        return time.time()
+
+    with torch.cuda.device(dev):
+        t0 = time.time()
+        idx, dist = knn_graph_device(pts, k, device=dev, stats=stats)
+        t0 = lap("knn_s", t0)
+        idx_t = torch.from_numpy(idx).to(dev)
+        _, _, w = umap_smooth_knn_device(idx_t, dist, device=dev)
+        indptr, indices, p = umap_fuzzy_union_device(idx_t, w, n_epochs)
+        t0 = lap("graph_s", t0)
+        y0 = umap_pca_start_device(torch.from_numpy(pts).to(dev).double(), seed)
+        y, _ = umap_layout_device(y0, indptr, indices, p, n_epochs, a, b, seed)
+        out = y.double().cpu().numpy()
+        lap("layout_s", t0)
+        if stats is not None:
+            stats["entries"] = int(indices.numel())
+    return out
 
 
 MST_LAZY_MIN = 65536             # points from which groups of points may sleep during Prim's scan (idl_mst_prim_lazy)
