@@ -61,6 +61,10 @@ SIGNATURES = {
     "idl_counts_stats_workspace": (_i64, [_i64, _i64]),
     "idl_counts_stats": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "idl_counts_standardise": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "idl_row_totals_i32": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "idl_counts_stream_workspace": (_i64, [_i64, _i64]),
+    "idl_counts_stream_stats": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "idl_counts_stream_finish": (_int, [_i64, _i64, _vp, _vp, _vp, _vp]),
     "idl_gather_pairs": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "idl_gather_pairs_at": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "idl_relu_dropout_fwd": (_int, [_vp, _i64, _int, _c.c_uint64, _vp, _int, _vp]),

@@ -237,6 +237,113 @@ __global__ __launch_bounds__(256) void counts_standardise_kernel(const int32_t *
     }
 }
 
+// ---------------------------------------------------------------- the same statistics from a STREAM of count rows (any f with 4 | f)
+// counts_stats_kernel needs a whole row in one workgroup (f <= 16384) and the whole [n, f] matrix in memory.  Here the matrix arrives a
+// chunk of rows at a time and is never kept: row totals first (an exact integer sum, any order), then column slabs.
+
+constexpr int RT_THREADS = 256;
+
+// int32 sum of every row of counts [rows, 4 f4]: LANES threads per row (one wave, or the workgroup), four 16-byte loads in flight
+template <int LANES>
+__global__ __launch_bounds__(RT_THREADS) void row_totals_kernel(const int32_t *counts, int64_t rows, int64_t f4, int32_t *totals)
+{
+    __shared__ int wsum[RT_THREADS / 64];
+    constexpr int RPW = RT_THREADS / LANES;                   // rows per workgroup
+    const int t = threadIdx.x % LANES, sub = threadIdx.x / LANES;
+    const int64_t row = (int64_t)blockIdx.x * RPW + sub;
+    int acc = 0;                                              // (a row's counts add up to its windows + 4^k < 2^31)
+    if (row < rows) {
+        const int4 *p = (const int4 *)counts + row * f4;
+        int64_t i = t;
+        for (; i + 3 * LANES < f4; i += 4 * LANES) {
+            int4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = p[i + u * LANES];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc += (v[u].x + v[u].y) + (v[u].z + v[u].w);
+        }
+        for (; i < f4; i += LANES) { const int4 v = p[i]; acc += (v.x + v.y) + (v.z + v.w); }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if constexpr (LANES == 64) {
+        if (t == 0 && row < rows) totals[row] = acc;
+    } else {
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+        __syncthreads();                                      // (the row is the workgroup's: every thread arrives)
+        if (threadIdx.x == 0 && row < rows) {
+            int s = 0;
+#pragma unroll
+            for (int w = 0; w < RT_THREADS / 64; ++w) s += wsum[w];
+            totals[row] = s;
+        }
+    }
+}
+
+constexpr int SLAB_ROWS = 8;      // independent 16-byte row loads a thread has in flight before the float64 arithmetic
+
+// Rows [row_lo, row_lo + rows) of the n-row matrix, given as a chunk (counts and totals address the chunk's first row).  A thread owns 4
+// consecutive columns, a workgroup a slab of 1024 columns inside ONE row block of the whole matrix (blockIdx.y counts from the block
+// row_lo falls in).  Per column the shifted sums of col_shifted_sums_kernel<double>, in ascending row order: a chunk that begins inside
+// a row block continues from the partial the previous chunk stored for it, so the sums do not depend on where the chunks were cut.
+// The shift x0 is row 0 of the matrix: the chunk that holds it forms it (and publishes it), the others read it.
+__global__ __launch_bounds__(STAT_THREADS) void counts_slab_stats_kernel(const int32_t *counts, const int32_t *totals, int64_t row_lo, int64_t rows,
+                                                                         int64_t f, int64_t rows_per_block, double *x0, double *partial1,
+                                                                         double *partial2)
+{
+    const int64_t c = ((int64_t)blockIdx.x * STAT_THREADS + threadIdx.x) * 4;
+    if (c >= f) return;
+    const int64_t blk = row_lo / rows_per_block + blockIdx.y;
+    const int64_t b0 = blk * rows_per_block;
+    const int64_t r0 = b0 > row_lo ? b0 : row_lo;
+    int64_t r1 = b0 + rows_per_block;
+    if (r1 > row_lo + rows) r1 = row_lo + rows;
+    double sh[4], a1[4], a2[4];
+    if (row_lo == 0) {
+        const int4 v = *(const int4 *)(counts + c);
+        const double T = (double)totals[0], rT = 1.0 / T;
+        sh[0] = count_freq(v.x, T, rT); sh[1] = count_freq(v.y, T, rT); sh[2] = count_freq(v.z, T, rT); sh[3] = count_freq(v.w, T, rT);
+        if (blockIdx.y == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x0[c + e] = sh[e];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sh[e] = x0[c + e];
+    }
+    double *p1 = partial1 + blk * f + c, *p2 = partial2 + blk * f + c;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        a1[e] = r0 == b0 ? 0.0 : p1[e];
+        a2[e] = r0 == b0 ? 0.0 : p2[e];
+    }
+    const int32_t *rowp = counts + (r0 - row_lo) * f + c;      // row r of the matrix is row r - row_lo of the chunk
+    const int32_t *tp = totals + (r0 - row_lo);
+    int64_t left = r1 - r0;
+    for (; left >= SLAB_ROWS; left -= SLAB_ROWS, rowp += SLAB_ROWS * f, tp += SLAB_ROWS) {
+        int4 v[SLAB_ROWS];
+        int32_t tt[SLAB_ROWS];
+#pragma unroll
+        for (int u = 0; u < SLAB_ROWS; ++u) { v[u] = *(const int4 *)(rowp + (int64_t)u * f); tt[u] = tp[u]; }
+#pragma unroll
+        for (int u = 0; u < SLAB_ROWS; ++u) {
+            const double T = (double)tt[u], rT = 1.0 / T;
+            const int32_t c4[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const double t = count_freq(c4[e], T, rT) - sh[e]; a1[e] += t; a2[e] += t * t; }
+        }
+    }
+    for (; left > 0; --left, rowp += f, ++tp) {
+        const int4 v = *(const int4 *)rowp;
+        const double T = (double)*tp, rT = 1.0 / T;
+        const int32_t c4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const double t = count_freq(c4[e], T, rT) - sh[e]; a1[e] += t; a2[e] += t * t; }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { p1[e] = a1[e]; p2[e] = a2[e]; }
+}
+
 __global__ __launch_bounds__(256) void gather_pairs_kernel(idl_dev::GatherArgs g)
 {
     idl_dev::gather_block(g, blockIdx.x, threadIdx.x);
@@ -387,6 +494,59 @@ int idl_counts_standardise(const int32_t *counts, const int32_t *row_totals, int
     if (g > (int64_t)di.cus * 16) g = (int64_t)di.cus * 16;
     hipLaunchKernelGGL(counts_standardise_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, counts, row_totals, total4, f / 4, mean, scale,
                        (float4 *)y);
+    IDL_HIP_TRY(hipGetLastError());
+    return IDL_OK;
+}
+
+/* int32 sum of every row of counts [rows, f] (4 | f) */
+int idl_row_totals_i32(const int32_t *counts, int64_t rows, int64_t f, int32_t *totals, void *stream)
+{
+    IDL_REQUIRE(rows >= 0 && f >= 4 && (f & 3) == 0 && rows <= 0x7FFFFFFFll, "row_totals_i32 needs 0 <= rows < 2^31 and 4 | f");
+    if (rows == 0) return IDL_OK;
+    IDL_REQUIRE(counts && totals && (((uintptr_t)counts) & 15u) == 0, "row_totals_i32: NULL or misaligned buffer");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t f4 = f / 4;
+    if (f4 <= 1024) hipLaunchKernelGGL(row_totals_kernel<64>, dim3((unsigned)((rows + 3) / 4)), dim3(RT_THREADS), 0, st, counts, rows, f4, totals);
+    else hipLaunchKernelGGL(row_totals_kernel<RT_THREADS>, dim3((unsigned)rows), dim3(RT_THREADS), 0, st, counts, rows, f4, totals);
+    IDL_HIP_TRY(hipGetLastError());
+    return IDL_OK;
+}
+
+/* idl_counts_stats for a matrix that arrives a chunk of rows at a time and is never held as a whole: any f with 4 | f.
+ * workspace: idl_counts_stream_workspace(n, f) bytes, kept from the first chunk to the finish.  idl_counts_stream_stats takes rows
+ * [row_lo, row_lo + rows) of the n-row matrix: `counts` [rows, f] and `totals` [rows] (idl_row_totals_i32) address the chunk.  The
+ * chunks come in ascending row order without gaps, on one stream, cut anywhere; idl_counts_stream_finish then gives mean / scale --
+ * those of idl_col_stats on the materialised float64 rows, bit for bit, whatever the cuts. */
+int64_t idl_counts_stream_workspace(int64_t n, int64_t f)
+{
+    return idl_counts_stats_workspace(n, f);
+}
+
+int idl_counts_stream_stats(const int32_t *counts, const int32_t *totals, int64_t row_lo, int64_t rows, int64_t n, int64_t f, void *workspace,
+                            void *stream)
+{
+    IDL_REQUIRE(n >= 1 && f >= 4 && (f & 3) == 0, "counts_stream_stats needs n >= 1 and 4 | f");
+    IDL_REQUIRE(row_lo >= 0 && rows >= 0 && rows <= n && row_lo <= n - rows, "counts_stream_stats: the chunk leaves the matrix");
+    if (rows == 0) return IDL_OK;
+    IDL_REQUIRE(counts && totals && workspace && (((uintptr_t)counts) & 15u) == 0 && (((uintptr_t)workspace) & 7u) == 0,
+                "counts_stream_stats: NULL or misaligned buffer");
+    const int64_t blocks = stat_row_blocks(n);
+    const int64_t rpb = (n + blocks - 1) / blocks;
+    double *p1 = (double *)workspace, *p2 = p1 + blocks * f, *x0 = p2 + blocks * f;
+    const int64_t touched = (row_lo + rows - 1) / rpb - row_lo / rpb + 1;          // <= blocks <= 256
+    const dim3 grid((unsigned)((f / 4 + STAT_THREADS - 1) / STAT_THREADS), (unsigned)touched);
+    hipLaunchKernelGGL(counts_slab_stats_kernel, grid, dim3(STAT_THREADS), 0, (hipStream_t)stream, counts, totals, row_lo, rows, f, rpb, x0, p1, p2);
+    IDL_HIP_TRY(hipGetLastError());
+    return IDL_OK;
+}
+
+int idl_counts_stream_finish(int64_t n, int64_t f, const void *workspace, double *mean, double *scale, void *stream)
+{
+    IDL_REQUIRE(n >= 1 && f >= 4 && (f & 3) == 0, "counts_stream_finish needs n >= 1 and 4 | f");
+    IDL_REQUIRE(workspace && mean && scale, "counts_stream_finish: NULL buffer");
+    const int64_t blocks = stat_row_blocks(n);
+    const double *p1 = (const double *)workspace, *p2 = p1 + blocks * f, *x0 = p2 + blocks * f;
+    hipLaunchKernelGGL(col_finish_kernel<double>, dim3((unsigned)((f + 63) / 64)), dim3(1024), 0, (hipStream_t)stream, x0, p1, p2, blocks, f, n, mean, scale);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }

@@ -86,6 +86,7 @@ class IID_model():
         self.n_voters = args.get('n_voters', 1)
         self.rng = args.get('rng')            # None -> $IDELUCS_RNG or "philox"
         self.seed = args.get('seed', 0)
+        self.predict_chunk_rows = args.get('predict_chunk_rows')     # rows per chunk of a streamed predict (None: utils.predict_chunk_rows)
 
         if self.optimizer == 'RMSprop':                         # models.py:87-94
             self.optimizer = optim.RMSprop(self.net.parameters(), lr=self.lr, weight_decay=0.01)
@@ -322,7 +323,37 @@ class IID_model():
             self._shared["predict_inputs"] = (key, feats, ready)
         return feats
 
+    def _predict_streams(self):
+        """The predict inputs go through utils.predict_feature_chunks -- chunk by chunk, nothing of [N, F] kept -- when the whole file's
+        float32 inputs would not fit PREDICT_CACHE_BYTES: there _predict_inputs stops caching them anyway, and its float64 rows
+        (12 N F bytes with the float32 result) are what runs out of memory.  N is the store's; without a store, the route below.
+        IDELUCS_DEV=predict_stream=1 / 0: always (where the rows allow it) / never."""
+        want = utils.OPTIONS["predict_stream"]
+        if want == "0" or not utils.stream_route_ok(self.k, self.reduce):
+            return False
+        if want == "1":
+            return True
+        return self.store is not None and self.store.n * self.n_features * 4 > PREDICT_CACHE_BYTES
+
+    def _predict_outputs_streamed(self, rows):
+        outs, lats = [], []
+        with torch.no_grad():
+            self.net.eval()
+            # the forward runs on the generator's whole buffer, every row where it stands in the chunk grid of the file: each chunk is the
+            # same product shape and a row's place in it does not depend on `rows`, so a row shard has the bits of those rows in a full predict
+            for lo, hi, x, at in utils.predict_feature_chunks(self.sequence_file, k=self.k, reduce=self.reduce, device=self.device, rows=rows,
+                                                              chunk_rows=self.predict_chunk_rows, padded=True):
+                o, l = self.net(x)
+                outs.append(o[at:at + hi - lo])
+                lats.append(l[at:at + hi - lo])
+            if not outs:
+                o, l = self.net(torch.zeros((1, self.n_features), dtype=torch.float32, device=self.device))
+                return o[:0], l[:0]
+        return torch.cat(outs), torch.cat(lats)
+
     def _predict_outputs(self, rows=None):
+        if self._predict_streams():
+            return self._predict_outputs_streamed(rows)
         feats = self._predict_inputs(rows)
         outs, lats = [], []
         with torch.no_grad():

@@ -33,6 +33,7 @@ _CODE[[A, C, G, T]] = [0, 1, 2, 3]
 # Variants kept for the tests that compare them with the default path (not environment switches; a test sets an entry with monkeypatch.setitem)
 OPTIONS = {"mimic_slots": "1",       # 0: the exact two-call protocol of the site generator (count, scan, fill) instead of one pass into slots
            "predict_counts": "1",    # 0: predict inputs through float64 rows instead of int32 counts
+           "predict_stream": "",     # IID_model's predict inputs chunk by chunk (predict_feature_chunks): 1 always, 0 never, empty: by size
            "one_pass": "1"}          # 0: the general three-pass FASTA reader instead of idl_fasta_parse_pack
 OPTIONS.update({k: v for k, v in _lib.DEV.items() if k in OPTIONS})
 
@@ -688,6 +689,97 @@ def predict_inputs_from_counts(din, k, rows=None, workspace=None):
     if hi > lo:
         _lib.check(_L.idl_counts_standardise(_ptr(counts[lo:hi]), _ptr(totals[lo:hi]), hi - lo, f, _ptr(mean), _ptr(scale), _ptr(out), _stream_ptr()))
     return out
+
+
+PREDICT_STREAM_CHUNK_BYTES = 8 << 30      # int32 counts + float32 result of one chunk of predict_feature_chunks
+
+
+def stream_route_ok(k, reduce=False):
+    """predict_feature_chunks can form these rows: plain or canonical k-mer rows whose length is a multiple of 4 (16-byte row loads)."""
+    row = int(_L.idl_row_len(_lib.MODE_CANONICAL if reduce else _lib.MODE_KMER, k))
+    return 1 <= k <= _lib.MAX_K and row >= 4 and row % 4 == 0
+
+
+def predict_chunk_rows(f, chunk_rows=None):
+    """Rows per chunk of predict_feature_chunks: the caller's, or what PREDICT_STREAM_CHUNK_BYTES holds of 8-byte-per-entry rows, 256..32768."""
+    if chunk_rows is None:
+        chunk_rows = min(32768, max(256, PREDICT_STREAM_CHUNK_BYTES // (8 * f)))
+    return max(1, int(chunk_rows))
+
+
+class _RowRange:
+    """Records [lo, hi) of a device input as an input of their own: the same packed buffers (slot_off holds offsets into the whole
+    buffer, n + 1 of them), slot_off and lengths advanced."""
+
+    def __init__(self, din, lo, hi):
+        self.n = hi - lo
+        self.codes, self.mask = din.codes, din.mask
+        self.slot_off, self.lengths = din.slot_off[lo:hi + 1], din.lengths[lo:hi]
+        self.max_len = din.max_len            # (a bound is all the vectoriser asks for)
+
+
+def predict_feature_chunks(sequence_file, k=6, reduce=False, device=None, rows=None, chunk_rows=None, padded=False):
+    """predict_features(...)[2] a chunk of rows at a time, bit for bit, with no [N, F] matrix in memory: a generator of
+    (lo, hi, float32 [hi - lo, F]) in row order.  Pass 1 vectorises every chunk of the file into one int32 buffer and accumulates the
+    scaler's statistics (idl_row_totals_i32, idl_counts_stream_stats; the [N] row totals are kept); pass 2 vectorises the chunks of
+    rows = (lo, hi) (default: all rows) again and standardises them (idl_counts_standardise).  The yielded tensor is a view of ONE reused
+    buffer: use it (or clone it) before asking for the next.
+    padded=True yields (lo, hi, buffer [chunk_rows, F], at) instead: the rows are buffer[at:at + hi - lo], where they stand in a chunk grid
+    counted from row 0 of the file; the buffer's other rows hold zeros or earlier rows.  A consumer that runs one fixed-shape product over
+    the whole buffer computes a row from the same operands at the same place whichever row range was asked for."""
+    dev = _device(device)
+    if not stream_route_ok(k, reduce):
+        raise ValueError(f"predict_feature_chunks: k={k}, reduce={reduce} gives no row length that is a multiple of 4")
+    din = None
+    if OPTIONS["one_pass"] != "0":
+        din = _OnePassInput.create(sequence_file, dev)             # (as predict_features)
+        if din is not None:
+            ff = din.ff
+            din.fill()
+    if din is None:
+        ff = FastaFile(sequence_file, check=True)
+        din = _DeviceInput(ff, dev)
+    try:
+        yield from feature_chunks_of_input(din, k, reduce, rows, chunk_rows, padded)
+    finally:
+        ff.close()
+
+
+def feature_chunks_of_input(din, k, reduce=False, rows=None, chunk_rows=None, padded=False):
+    """predict_feature_chunks on packed bases that are on the device already (a _DeviceInput or its like)."""
+    mode = _lib.MODE_CANONICAL if reduce else _lib.MODE_KMER
+    f = int(_L.idl_row_len(mode, k))
+    dev = din.codes.device
+    n = din.n
+    lo, hi = (0, n) if rows is None else rows
+    if not 0 <= lo <= n or not lo <= hi <= n:
+        raise ValueError(f"rows={rows} outside 0..{n}")
+    if hi <= lo:
+        return
+    cr = min(predict_chunk_rows(f, chunk_rows), n)
+    counts = torch.empty((cr, f), dtype=torch.int32, device=dev)
+    totals = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(_L.idl_counts_stream_workspace(n, f), 8), dtype=torch.uint8, device=dev)
+    for a in range(0, n, cr):
+        b = min(a + cr, n)
+        _vectorise(_RowRange(din, a, b), k, mode, _lib.INIT_ONE, _lib.OUT_COUNTS_I32, out=counts[:b - a].unsqueeze(0))
+        _lib.check(_L.idl_row_totals_i32(_ptr(counts), b - a, f, _ptr(totals[a:b]), _stream_ptr()))
+        _lib.check(_L.idl_counts_stream_stats(_ptr(counts), _ptr(totals[a:b]), a, b - a, n, f, _ptr(ws), _stream_ptr()))
+    mean = torch.empty(f, dtype=torch.float64, device=dev)
+    scale = torch.empty(f, dtype=torch.float64, device=dev)
+    _lib.check(_L.idl_counts_stream_finish(n, f, _ptr(ws), _ptr(mean), _ptr(scale), _stream_ptr()))
+    del ws
+    # pass 2 on the chunk grid of pass 1 (multiples of cr from row 0), each row at its place in its grid chunk: a row range asked for
+    # alone is cut where the whole file is cut
+    out = (torch.zeros if padded else torch.empty)((cr, f), dtype=torch.float32, device=dev)
+    for g in range(lo // cr * cr, hi, cr):
+        a, b = max(g, lo), min(g + cr, hi)
+        _vectorise(_RowRange(din, a, b), k, mode, _lib.INIT_ONE, _lib.OUT_COUNTS_I32, out=counts[:b - a].unsqueeze(0))
+        _lib.check(_L.idl_counts_standardise(_ptr(counts), _ptr(totals[a:b]), b - a, f, _ptr(mean), _ptr(scale), _ptr(out[a - g:]), _stream_ptr()))
+        if padded:
+            yield a, b, out, a - g
+        else:
+            yield a, b, out[a - g:b - g]
 
 
 def ingest_threads():
