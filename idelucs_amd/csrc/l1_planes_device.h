@@ -15,7 +15,8 @@
 // of 32 x 32) read their fragments with ds_read_b128 one K-step ahead of the MFMAs (v_mfma_f32_32x32x16_f16); one barrier a chunk.  The
 // partial sums go out as part[8][512][m] fp32 (scaled back by 2^-(W_EXP + X_EXP)); idl_reduce_parts_rms adds the eight in a fixed order.
 // The operands' roles are symmetric: called with the batch's planes as "W1" and W1's as the "batch" the same tiles give part[8][m][512]
-// (the step of n_clusters > 48, whose activations are not transposed).
+// (the step of n_clusters > 48, whose activations are not transposed).  L1pArgs::rows stores THIS call's sums in that orientation instead (the swapped call
+// adds the two low-plane products in the other order: other bits) -- for the launch that adds the slabs and runs the forward middle on whole rows.
 // WHERE IT STANDS (round 6): 15.3 us in the step (round 5: 18.5-19.8).  The loaders alone, free-running, stream the launch's 134 MB out of L2 in 4 us (33 TB/s; 13 us
 // without the K-slice-per-XCD mapping); computing alone 6.4 us; together 11 + 3.8 us of partial-sum stores + launch: per K-step the LDS serves 32 KB of fragment reads and
 // 16 KB of DMA writes (384 clocks at 128 B a clock) beside 384 clocks of MFMAs per SIMD -- two pipes at equal load that a one-step look-ahead keeps ~half busy (MFMA 0.23).
@@ -49,6 +50,7 @@ struct L1pArgs {
     int m, n_out, K, n_tiles;      // n_tiles = (n_out / 128) (m / 128) KSPLIT
     int ldw, ldx;                  // elements between two rows of W1's / the batch's planes (>= K, multiples of 8)
     int dbg;                       // diagnostics (IDELUCS_DEV=l1p_dbg; wrong results): 1 no DMA, 4 no stores of the partial sums
+    int rows;                      // 1: the same sums stored as part[KSPLIT][m][n_out] (a row of the batch contiguous; idl_l1_planes_rows)
 };
 
 __host__ __device__ inline bool supported(int m, int n_out, int K)
@@ -211,6 +213,32 @@ __device__ __forceinline__ void l1p_body(const L1pArgs &g, const int bid, unsign
     constexpr int EP = 68;
     static_assert(4 * 64 * EP * 4 <= LDS_BYTES, "the four waves' epilogue images");
     float *img = (float *)smem + wv * (64 * EP);
+    if (g.rows) {
+        // part[KSPLIT][m][n_out]: the image is written turned (img[batch row][hidden unit]: an accumulator's four consecutive hidden units are one
+        // 16-byte LDS store) and leaves as 16 bytes a lane along n_out -- the values are those of the form below, element for element
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e4 = 0; e4 < 4; ++e4) {
+                    const int rl = 32 * i + e4 * 8 + (lane >> 5) * 4, cl = 32 * j + (lane & 31);
+                    float4 v;
+                    v.x = (hi[i][j][4 * e4] + lo[i][j][4 * e4]) * inv; v.y = (hi[i][j][4 * e4 + 1] + lo[i][j][4 * e4 + 1]) * inv;
+                    v.z = (hi[i][j][4 * e4 + 2] + lo[i][j][4 * e4 + 2]) * inv; v.w = (hi[i][j][4 * e4 + 3] + lo[i][j][4 * e4 + 3]) * inv;
+                    *(float4 *)(img + cl * EP + rl) = v;
+                }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        float *outr = g.part + (int64_t)s * g.n_out * g.m + (int64_t)(n0 + wn) * g.n_out + m0 + wm;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int idx = lane + 64 * u, cl = idx >> 4, c4 = idx & 15;
+            const float4 v = *(const float4 *)(img + cl * EP + 4 * c4);
+            *(float4 *)(outr + (int64_t)cl * g.n_out + 4 * c4) = v;
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll

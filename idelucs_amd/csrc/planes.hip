@@ -56,7 +56,8 @@ int idl_l1_planes_parts(void) { return l1p_dev::KSPLIT; }
 
 int idl_l1_planes_supported(int m, int n_out, int n_in) { return l1p_dev::supported(m, n_out, n_in) ? 1 : 0; }
 
-int idl_l1_planes(const void *w_hi, const void *w_lo, int ld_w, const void *x_hi, const void *x_lo, int ld_x, int m, int n_out, int n_in, float *part, void *stream)
+static int l1_planes_impl(const void *w_hi, const void *w_lo, int ld_w, const void *x_hi, const void *x_lo, int ld_x, int m, int n_out, int n_in, float *part, int rows,
+                          void *stream)
 {
     IDL_REQUIRE(ld_w >= n_in && ld_x >= n_in && ld_w <= n_in + 1024 && ld_x <= n_in + 1024 && (ld_w & 7) == 0 && (ld_x & 7) == 0, "l1_planes: n_in <= ld <= n_in + 1024, 8 | ld");
     IDL_REQUIRE(w_hi && w_lo && x_hi && x_lo && part && l1p_dev::supported(m, n_out, n_in),
@@ -64,7 +65,7 @@ int idl_l1_planes(const void *w_hi, const void *w_lo, int ld_w, const void *x_hi
     IDL_REQUIRE(((((uintptr_t)w_hi) | ((uintptr_t)w_lo) | ((uintptr_t)x_hi) | ((uintptr_t)x_lo) | ((uintptr_t)part)) & 15u) == 0, "l1_planes: buffers must be 16-byte aligned");
     static const int l1p_dbg = idl::dev_env("l1p_dbg") ? atoi(idl::dev_env("l1p_dbg")) : 0;      // (timing ablations; l1_planes_device.h)
     l1p_dev::L1pArgs a{(const uint16_t *)w_hi, (const uint16_t *)w_lo, (const uint16_t *)x_hi, (const uint16_t *)x_lo, part, m, n_out, n_in,
-                       (n_out / l1p_dev::TM) * (m / l1p_dev::TN) * l1p_dev::KSPLIT, ld_w, ld_x, l1p_dbg};
+                       (n_out / l1p_dev::TM) * (m / l1p_dev::TN) * l1p_dev::KSPLIT, ld_w, ld_x, l1p_dbg, rows};
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin): several voters in one launch, train_step.hip
         static_assert(sizeof(l1p_dev::L1pArgs) + idl::PLAN_PARAMS <= idl::PLAN_BYTES, "L1pArgs does not fit a plan record");
         idl::PlanHead h{};
@@ -83,6 +84,17 @@ int idl_l1_planes(const void *w_hi, const void *w_lo, int ld_w, const void *x_hi
     hipLaunchKernelGGL(l1_planes_kernel, dim3((unsigned)a.n_tiles), dim3(l1p_dev::THREADS), l1p_dev::LDS_BYTES, (hipStream_t)stream, a);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
+}
+
+int idl_l1_planes(const void *w_hi, const void *w_lo, int ld_w, const void *x_hi, const void *x_lo, int ld_x, int m, int n_out, int n_in, float *part, void *stream)
+{
+    return l1_planes_impl(w_hi, w_lo, ld_w, x_hi, x_lo, ld_x, m, n_out, n_in, part, 0, stream);
+}
+
+// ... the same sums, bit for bit, stored as part[8][m][n_out]: a row of the batch contiguous (idl_reduce_mid_fwd_gather_planes reads whole rows)
+int idl_l1_planes_rows(const void *w_hi, const void *w_lo, int ld_w, const void *x_hi, const void *x_lo, int ld_x, int m, int n_out, int n_in, float *part, void *stream)
+{
+    return l1_planes_impl(w_hi, w_lo, ld_w, x_hi, x_lo, ld_x, m, n_out, n_in, part, 1, stream);
 }
 
 }  // extern "C"

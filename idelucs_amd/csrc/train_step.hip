@@ -150,7 +150,8 @@ constexpr int H1 = 512;
 constexpr int MID_WAVES = 16;
 constexpr int MID_GATHER_ROWS = 4;   // rows per 256-thread gather tile when the batch assembly rides in mid_fwd / mid_bwd
 
-// (Round 5's variant that added idl_l1_planes' eight K-slice partial sums up HERE -- 16 MB read by 64 workgroups: +8 us -- left in round 6: idl_reduce_parts_rms does it on every CU.)
+// (Round 5's variant that added idl_l1_planes' eight K-slice partial sums up HERE -- 16 MB read by 64 workgroups: +8 us -- left in round 6: idl_reduce_parts_rms does it on every CU.
+//  The lone voter's default step runs this chain inside the sums launch instead, on workgroups of 8 whole rows: sums_fwd_body.)
 template <bool TIN>       // TIN: a1 is stored transposed, [512, m] (the orientation hipBLASLt runs the layer-1 product fastest in)
 __device__ __forceinline__ void mid_fwd_body(float *__restrict__ a1, const float *__restrict__ b1, const float *__restrict__ W2,
                                                                   const float *__restrict__ b2, const float *__restrict__ W3,
@@ -1244,8 +1245,207 @@ struct ReduceArgs { float4 *part; int64_t slab4; int n_parts, blocks; const int6
 //  the counter when they start and its own loader waves move it when they end: on a GPU shared with another process not every tile starts
 //  before the first one ends)
 constexpr int RED_U = 2;
-__global__ __launch_bounds__(256) void reduce_rms_kernel(ReduceArgs r, RmsArgs a, const float *hyper, int64_t *ctl, int64_t batch_advance, int with_tail)
+// ROWS = 4 or 8 (1024 threads): the instance that ALSO runs the forward middle on the rows it has just summed (sums_fwd_body below); its second argument is
+// the middle's (SumsFwdArgs), the rest unused.  ROWS = 0: the sums (and the tail) alone, as ever.
+struct SumsFwdArgs {
+    const float *b1, *W2, *b2, *W3, *b3; float *r1T; int m, C, train; uint64_t seed; float *f, *inv, *r2, *z; int tile0, tile1; idl_dev::GatherArgs gth;
+};
+template <int ROWS> struct RedSecond { typedef SumsFwdArgs type; };
+template <> struct RedSecond<0> { typedef RmsArgs type; };
+
+// The sums launch carrying the whole forward middle (n_clusters <= 48, the lone voter's step): the partial sums come as part[8][m][512] (idl_l1_planes_rows) and a
+// workgroup owns ROWS whole rows of the batch -- m / ROWS computing workgroups instead of mid_fwd's m / 16 -- with the batch-assembly riders behind them as in
+// mid_fwd_body.  The 16-row MFMA tile keeps its shape; the rows the workgroup does not own are zero, and their lanes share out the partial-sum loads: lane row
+// l = ROWS g + r loads slabs [SPL g, SPL g + SPL) of row r (SPL = ROWS / 2), the running sum is handed from group g to group g + 1 by DPP row_shr:ROWS, so row r is
+// ((p0 + p1) + p2) + ... + p7 in the LAST group's lanes -- reduce_rms_kernel<0>'s bits -- and the tile's rows [16 - ROWS, 16) are the valid ones.  From there on it
+// is mid_fwd_body<true>'s arithmetic on the same operands (rows of an MFMA tile are independent): the same Philox counters (the flat index of [m][512]), the
+// same 32 MFMAs a wave over its 32-k slice, the 16-slice add in the same order, normalise, the head, logits, softmax.  r1 goes to a buffer of its own, transposed
+// [512][m] as mid_bwd and the dW2 tiles read it; part is only read.  Every global read is issued before the first dependent instruction, 16 bytes a lane.
+template <int ROWS>
+__device__ __forceinline__ void sums_fwd_body(const ReduceArgs &r, const SumsFwdArgs &p, float *smem, const int bid)
 {
+    static_assert(ROWS == 4 || ROWS == 8, "rows of the batch a workgroup owns");
+    constexpr int GROUPS = 16 / ROWS, SPL = l1p_dev::KSPLIT / GROUPS, Q0 = 4 - ROWS / 4;      // Q0: the first lane quarter whose C/D rows are valid
+    if (bid >= r.blocks) {           // riders: tiles [tile0, tile1) of the next batch (mid_fwd_body)
+        const int blk = p.tile0 + (bid - r.blocks) * 4 + (int)(threadIdx.x >> 8);
+        if (blk < p.tile1) idl_dev::gather_tile<MID_GATHER_ROWS>(p.gth, (int64_t)blk, (int)(threadIdx.x & 255));
+        return;
+    }
+    // LDS: ps[wave][owned row][64] the K-slices' partial tiles | R2t[16][68] the r2 tile (A operand of the logits; rows >= ROWS zero) | LG[ROWS][257] the logits
+    float (*ps)[ROWS][H2] = (float (*)[ROWS][H2])smem;
+    float (*R2t)[H2 + 4] = (float (*)[H2 + 4])(smem + MID_WAVES * ROWS * H2);
+    float (*LG)[64 * MAX_CPL + 1] = (float (*)[64 * MAX_CPL + 1])(smem + MID_WAVES * ROWS * H2 + 16 * (H2 + 4));
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l = lane & 15, q = lane >> 4;
+    const int grp = l / ROWS, rr = l % ROWS;
+    const bool own = grp == GROUPS - 1;          // this lane ends up with row r0 + rr's sums
+    const int m = p.m, C = p.C, train = p.train;
+    const int r0 = bid * ROWS;
+    const int k0 = 32 * wv + 8 * q;              // this lane's 8 consecutive k
+    // ---- every global read of the kernel is issued here, before the first dependent instruction
+    const int64_t e4 = ((int64_t)(r0 + rr) * H1 + k0) / 4;       // float4 index of (row, k0) in a slab == the dropout counter of mid_fwd_body
+    float4 pv[SPL][2];
+#pragma unroll
+    for (int j = 0; j < SPL; ++j) {
+        const float4 *src = r.part + (int64_t)(SPL * grp + j) * r.slab4 + e4;
+        pv[j][0] = src[0]; pv[j][1] = src[1];
+    }
+    float4 bb[2];
+    bb[0] = *(const float4 *)(p.b1 + k0); bb[1] = *(const float4 *)(p.b1 + k0 + 4);
+    float4 bw[4][2];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {             // lat[:, 16 ct .. 16 ct + 15]: B[k][c] = W2[16 ct + c][k]
+        const float4 *wsrc = (const float4 *)(p.W2 + (int64_t)(16 * ct + l) * H1 + k0);
+        bw[ct][0] = wsrc[0]; bw[ct][1] = wsrc[1];
+    }
+    const int nct = (C + 15) / 16;               // column tiles of the logits; wave wv < nct owns tile wv
+    float4 w3f[4];                               // B[k = 16 q + s][c = l] = W3[16 wv + l][16 q + s]
+    float b3v = 0.f;
+    if (wv < nct) {
+        const int c = min(16 * wv + l, C - 1);
+        const float4 *wsrc = (const float4 *)(p.W3 + (int64_t)c * H2 + 16 * q);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w3f[i] = wsrc[i];
+        b3v = p.b3[c];
+    }
+    const float b2v = p.b2[lane];
+    const int64_t ctl0 = r.ctl_src[0];
+    const uint32_t step = (uint32_t)ctl0;
+    // ---- the eight slabs in ascending order: group 0 starts, each group adds its own behind what the group before hands over
+    float sum[8];
+    {
+        float mine[SPL][8];
+#pragma unroll
+        for (int j = 0; j < SPL; ++j) {
+            mine[j][0] = pv[j][0].x; mine[j][1] = pv[j][0].y; mine[j][2] = pv[j][0].z; mine[j][3] = pv[j][0].w;
+            mine[j][4] = pv[j][1].x; mine[j][5] = pv[j][1].y; mine[j][6] = pv[j][1].z; mine[j][7] = pv[j][1].w;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float acc = mine[0][i];
+#pragma unroll
+            for (int j = 1; j < SPL; ++j) acc += mine[j][i];
+#pragma unroll
+            for (int t = 1; t < GROUPS; ++t) {
+                float got = idl_dev::dpp_f<0x110 + ROWS>(acc);       // row_shr:ROWS -- lane l takes lane l - ROWS's running sum
+#pragma unroll
+                for (int j = 0; j < SPL; ++j) got += mine[j][i];
+                acc = grp == t ? got : acc;
+            }
+            sum[i] = acc;
+        }
+    }
+    // ---- bias, ReLU + Dropout of layer 1; r1 out, transposed
+    float a[8];
+    float *dstT = p.r1T + (int64_t)k0 * m + r0 + rr;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float4 v = make_float4(sum[4 * i], sum[4 * i + 1], sum[4 * i + 2], sum[4 * i + 3]);
+        v.x += bb[i].x; v.y += bb[i].y; v.z += bb[i].z; v.w += bb[i].w;
+        float s0 = 1.f, s1 = 1.f, s2 = 1.f, s3 = 1.f;
+        if (train) {                             // identical stream to relu_dropout_fwd_kernel: counter = float4 index of the flat array
+            const int64_t idx4 = e4 + i;
+            const U4 rn = philox((uint32_t)idx4, 1u, step, (uint32_t)(idx4 >> 32), (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+            s0 = (rn.x >> 31) ? 2.f : 0.f; s1 = (rn.y >> 31) ? 2.f : 0.f;
+            s2 = (rn.z >> 31) ? 2.f : 0.f; s3 = (rn.w >> 31) ? 2.f : 0.f;
+        }
+        v.x = v.x > 0.f ? v.x * s0 : 0.f; v.y = v.y > 0.f ? v.y * s1 : 0.f;
+        v.z = v.z > 0.f ? v.z * s2 : 0.f; v.w = v.w > 0.f ? v.w * s3 : 0.f;
+        if (own) {
+            dstT[(int64_t)(4 * i) * m] = v.x; dstT[(int64_t)(4 * i + 1) * m] = v.y; dstT[(int64_t)(4 * i + 2) * m] = v.z; dstT[(int64_t)(4 * i + 3) * m] = v.w;
+        }
+        a[4 * i] = own ? v.x : 0.f; a[4 * i + 1] = own ? v.y : 0.f; a[4 * i + 2] = own ? v.z : 0.f; a[4 * i + 3] = own ? v.w : 0.f;
+    }
+    // ---- lat = r1 W2^T: this wave's K-slice; the owned rows are C/D rows 4 q + reg of the quarters q >= Q0
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const float4 b = bw[ct][i];
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i], b.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i + 1], b.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i + 2], b.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i + 3], b.w, acc, 0, 0, 0);
+        }
+        if (q >= Q0) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) ps[wv][4 * (q - Q0) + reg][16 * ct + l] = acc[reg];
+        }
+    }
+    if (r.ctl_snap != nullptr && bid == 0 && threadIdx.x == 0) *r.ctl_snap = ctl0;      // (here: no trip of its own in front of workgroup 0's loads)
+    __syncthreads();
+    // ---- wave wv < ROWS owns row wv: add the 16 K-slices and the bias; normalise; ReLU + Dropout of the latent
+    const int row = r0 + wv;
+    float ar = 0.f;
+    if (wv < ROWS) {
+        float x = b2v;
+#pragma unroll
+        for (int w = 0; w < MID_WAVES; ++w) x += ps[w][wv][lane];
+        const float nrm = fmaxf(sqrtf(wave_sum(x * x)), 1e-12f);       // F.normalize(dim=1), eps 1e-12
+        float sc = 1.f;
+        if (train) {                             // as head_row
+            const U4 rn = philox((uint32_t)row, 2u, step, 0u, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+            const uint32_t word = (lane < 32) ? rn.x : rn.y;
+            sc = ((word >> (lane & 31)) & 1u) ? 2.f : 0.f;
+        }
+        ar = x > 0.f ? x * sc : 0.f;
+        p.f[(int64_t)row * H2 + lane] = x / nrm;
+        if (lane == 0) p.inv[row] = 1.f / nrm;
+        p.r2[(int64_t)row * H2 + lane] = ar;
+    }
+    R2t[wv][lane] = ar;                          // (its own memory: no barrier between the reads of ps and this)
+    __syncthreads();
+    // ---- logits tile wv = r2[16 x 64] W3[16 wv .. 16 wv + 15]^T + b3; the owned rows are the tile's first ROWS here
+    if (wv < nct) {
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float4 t = *(const float4 *)&R2t[l][16 * q + 4 * i];
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.x, w3f[i].x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.y, w3f[i].y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.z, w3f[i].z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.w, w3f[i].w, acc, 0, 0, 0);
+        }
+        if (4 * q < ROWS) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) LG[4 * q + reg][16 * wv + l] = acc[reg] + b3v;
+        }
+    }
+    __syncthreads();
+    if (wv >= ROWS) return;
+    // ---- softmax of row wv
+    float lg[MAX_CPL];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < MAX_CPL; ++t) {
+        const int c = t * 64 + lane;
+        lg[t] = c < C ? LG[wv][c] : -INFINITY;
+        mx = fmaxf(mx, lg[t]);
+    }
+    mx = wave_max(mx);
+    float den = 0.f;
+#pragma unroll
+    for (int t = 0; t < MAX_CPL; ++t) {
+        const int c = t * 64 + lane;
+        if (c < C) { lg[t] = __expf(lg[t] - mx); den += lg[t]; }
+    }
+    den = wave_sum(den);
+#pragma unroll
+    for (int t = 0; t < MAX_CPL; ++t) {
+        const int c = t * 64 + lane;
+        if (c < C) p.z[(int64_t)row * C + c] = lg[t] / den;
+    }
+}
+template <int ROWS> constexpr int sums_fwd_lds() { return (MID_WAVES * ROWS * H2 + 16 * (H2 + 4) + ROWS * (64 * MAX_CPL + 1)) * (int)sizeof(float); }
+
+template <int ROWS>
+__global__ __launch_bounds__(ROWS ? 64 * MID_WAVES : 256) void reduce_rms_kernel(ReduceArgs r, typename RedSecond<ROWS>::type a, const float *hyper, int64_t *ctl,
+                                                                                 int64_t batch_advance, int with_tail)
+{
+    if constexpr (ROWS != 0) {
+        extern __shared__ __attribute__((aligned(16))) float sums_fwd_smem[];
+        sums_fwd_body<ROWS>(r, a, sums_fwd_smem, (int)blockIdx.x);
+    } else {
     // grid order: the tail's workgroups FIRST (theirs is the longer chain: 7.1 us on its own against the sums' 4.7), the sums behind them
     const int n_tail = (int)gridDim.x - r.blocks;
     if ((int)blockIdx.x >= n_tail) {
@@ -1270,6 +1470,7 @@ __global__ __launch_bounds__(256) void reduce_rms_kernel(ReduceArgs r, RmsArgs a
     // (the look-ahead form of the dW2 tiles -- every operand of a wave requested before its first product: one trip to memory instead of
     //  three -- as behind the dW1 tiles of wgrad_rmsprop_kernel: here too the tail's chain is the launch's length, 9.3 us without)
     if (with_tail) rmsprop_body<true>(a, hyper, ctl, batch_advance, 0, 0, idl_dev::GatherArgs{}, (int)blockIdx.x, (int)threadIdx.x);
+    }
 }
 
 // The dW1 tiles of the two-plane form (wgrad_planes_device.h) with THIS step's optimizer tail carried by their loader waves: a workgroup's four
@@ -1832,7 +2033,7 @@ static int rmsprop_launch(int count, float *const *params, const float *const *g
     }
     if (red != nullptr) {                   // ... beside the workgroups that add up the two-plane layer-1 tiles' partial sums (reduce_rms_kernel)
         IDL_REQUIRE(big == nullptr && l1 == nullptr && extra == 0 && idl::take_plan() == nullptr, "reduce_parts_rms: no tiles, no batch assembly, not recordable");
-        hipLaunchKernelGGL(reduce_rms_kernel, dim3((unsigned)(red->blocks + nb_total + a.wg_tiles)), dim3(256), 0, (hipStream_t)stream, *red, a, hyper, ctl,
+        hipLaunchKernelGGL(reduce_rms_kernel<0>, dim3((unsigned)(red->blocks + nb_total + a.wg_tiles)), dim3(256), 0, (hipStream_t)stream, *red, a, hyper, ctl,
                            batch_advance, 1);
         IDL_HIP_TRY(hipGetLastError());
         return IDL_OK;
@@ -1994,7 +2195,7 @@ int idl_reduce_parts_rms(float *part, int64_t slab_elems, const int64_t *step_co
             memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &r, sizeof(r));
             return IDL_OK;
         }
-        hipLaunchKernelGGL(reduce_rms_kernel, dim3((unsigned)r.blocks), dim3(256), 0, (hipStream_t)stream, r, RmsArgs{}, (const float *)nullptr, (int64_t *)nullptr,
+        hipLaunchKernelGGL(reduce_rms_kernel<0>, dim3((unsigned)r.blocks), dim3(256), 0, (hipStream_t)stream, r, RmsArgs{}, (const float *)nullptr, (int64_t *)nullptr,
                            (int64_t)0, 0);
         IDL_HIP_TRY(hipGetLastError());
         return IDL_OK;
@@ -2002,6 +2203,45 @@ int idl_reduce_parts_rms(float *part, int64_t slab_elems, const int64_t *step_co
     idl_dev::GatherArgs g{};
     return rmsprop_launch(count, params, grads, grad_parts, square_avg, sizes, hyper, ctl, batch_advance, loss_rows, loss_m, w_nce, w_iic, out, g,
                           stream, wg_index, wg_dy, wg_x, wg_m, wg_n_out, wg_n_in, wg_grad, wg_x_transposed, nullptr, -1, nullptr, w1_index, &r);
+}
+
+// The sums and the forward middle of the two-plane step in one launch (sums_fwd_body): part[8][m][512] from idl_l1_planes_rows, rows_per_wg = 4 or 8.
+int idl_reduce_mid_fwd_gather_planes(const float *part, const int64_t *step_counter, int64_t *step_snapshot, int rows_per_wg, float *r1_transposed,
+                                     const float *b1, const float *W2, const float *b2, const float *W3, const float *b3, int m,
+                                     int C, int train, uint64_t seed, float *f, float *inv, float *r2, float *z,
+                                     const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
+                                     int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale,
+                                     const double *inv_scale, float *y, void *y_hi, void *y_lo, int *overflow_flag, int part_begin, int part_end, int parts,
+                                     void *stream)
+{
+    IDL_REQUIRE(part && step_counter && r1_transposed && b1 && W2 && b2 && W3 && b3 && f && inv && r2 && z, "reduce_mid_fwd: NULL buffer");
+    IDL_REQUIRE(rows_per_wg == 4 || rows_per_wg == 8, "reduce_mid_fwd: 4 or 8 rows a workgroup");
+    IDL_REQUIRE(m >= 16 && (m % 16) == 0 && C >= 1 && C <= 64 * MAX_CPL && (int64_t)m * H1 < (1ll << 31), "reduce_mid_fwd: m must be a multiple of 16, n_clusters in 1..256");
+    IDL_REQUIRE((((uintptr_t)part | (uintptr_t)b1 | (uintptr_t)W2 | (uintptr_t)W3) & 15u) == 0 && (((uintptr_t)r1_transposed) & 3u) == 0,
+                "reduce_mid_fwd: part / b1 / W2 / W3 must be 16-byte aligned");
+    IDL_REQUIRE(parts >= 1 && part_begin >= 0 && part_begin <= part_end && part_end <= parts, "reduce_mid_fwd: need 0 <= part_begin <= part_end <= parts");
+    IDL_REQUIRE((y_hi != nullptr) == (y_lo != nullptr) && (y_hi == nullptr || (feats != nullptr && ((((uintptr_t)y_hi) | ((uintptr_t)y_lo)) & 7u) == 0)),
+                "reduce_mid_fwd: both planes of the next batch (8-byte aligned) or neither; planes need the batch assembly");
+    IDL_REQUIRE(idl::take_plan() == nullptr, "reduce_mid_fwd: the lone voter's launch, not recordable");
+    idl_dev::GatherArgs g{};
+    int64_t t0 = 0, t1 = 0;
+    if (feats != nullptr) {                  // (feats == NULL: no batch assembly in this launch)
+        IDL_REQUIRE(pair_idx && mean && scale && (y || y_hi) && n >= 1 && fdim >= 4 && (fdim & 3) == 0 && batch >= 1 && n_pairs >= 0,
+                    "reduce_mid_fwd: bad gather arguments (4 | f)");
+        g = idl_dev::GatherArgs{feats, n, fdim, view_stride, pair_idx, base, batch, n_pairs, mean, scale, inv_scale, y, base_add, (uint16_t *)y_hi, (uint16_t *)y_lo,
+                                overflow_flag};
+        const int64_t ng = idl_dev::gather_tiles<MID_GATHER_ROWS>(fdim, batch);
+        t0 = ng * part_begin / parts; t1 = ng * part_end / parts;
+    }
+    const ReduceArgs r{(float4 *)const_cast<float *>(part), (int64_t)m * H1 / 4, l1p_dev::KSPLIT, m / rows_per_wg, step_counter, step_snapshot};
+    const SumsFwdArgs p{b1, W2, b2, W3, b3, r1_transposed, m, C, train, seed, f, inv, r2, z, (int)t0, (int)t1, g};
+    const dim3 grid((unsigned)(r.blocks + (t1 - t0 + 3) / 4));
+    if (rows_per_wg == 4) hipLaunchKernelGGL(reduce_rms_kernel<4>, grid, dim3(64 * MID_WAVES), sums_fwd_lds<4>(), (hipStream_t)stream, r, p, (const float *)nullptr,
+                                             (int64_t *)nullptr, (int64_t)0, 0);
+    else hipLaunchKernelGGL(reduce_rms_kernel<8>, grid, dim3(64 * MID_WAVES), sums_fwd_lds<8>(), (hipStream_t)stream, r, p, (const float *)nullptr,
+                            (int64_t *)nullptr, (int64_t)0, 0);
+    IDL_HIP_TRY(hipGetLastError());
+    return IDL_OK;
 }
 
 // idl_wgrad_rmsprop_xplanes (W updated, its planes written) with THIS step's optimizer tail carried by the tiles' loader waves (tail arguments as

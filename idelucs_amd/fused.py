@@ -3,8 +3,9 @@
 
 One step of reference idelucs/models.py:117-133 takes one of five launch sequences (FusedLinearTrainer._form picks it once per step):
     planes       (default, n_clusters <= 48) the two big products on the fp16 matrix cores from two-plane operands:
-                 idl_l1_planes -> idl_reduce_parts_rms -> idl_mid_fwd_gather_planes -> idl_nce_fused_iic_z -> idl_mid_bwd_gather_planes
-                 -> idl_wgrad_xplanes_rms (dW1 with RMSprop in the tiles' epilogue, the optimizer's tail on their loader waves)
+                 idl_l1_planes_rows -> idl_reduce_mid_fwd_gather_planes (the partial sums and the forward middle in one launch) -> idl_nce_fused_iic_z
+                 -> idl_mid_bwd_gather_planes -> idl_wgrad_xplanes_rms (dW1 with RMSprop in the tiles' epilogue, the optimizer's tail on their loader
+                 waves); recorded, or with another ending: idl_l1_planes -> idl_reduce_parts_rms -> idl_mid_fwd_gather_planes -> ...
     planes_rows  the same for n_clusters > 48 (the fine-grained mode's 200 output units: joint + IIC core with z dP0, dW3 on idl_at_b)
     tiles        IDELUCS_PLANES=0 (or shapes the planes do not take): own fp32 tiles, idl_l1_fwd -> idl_mid_fwd_gather -> InfoNCE + IIC ->
                  idl_mid_bwd_gather -> idl_wgrad_rmsprop; the optimizer's tail rides in the NEXT step's layer-1 launch (idl_l1_fwd_rms)
@@ -57,6 +58,8 @@ VARIANTS = {
     "lockstep_planes": "1",  # 0: a rank's voters in lockstep on batched fp32 library GEMMs
     "planes_wgrad": "1",     # 0: dW1 on the fp32 tiles (writing W1's planes) beside the two-plane layer 1
     "planes_tail": "wgrad",  # reduce: the optimizer tail beside the next step's partial sums instead of on the dW1 tiles' loader waves
+    "sums_fwd": "1",         # 0: the lone step's forward middle as a launch of its own behind the partial sums (seven launches a step instead of six)
+    "sums_fwd_rows": "8",    # 4: the merged launch's workgroups own 4 whole rows of the batch instead of 8 (measured slower: DESIGN 4.4)
     "fused": "1",            # 0: models.IID_model trains NetLinear + RMSprop through torch autograd instead of the fused explicit step
 }
 VARIANTS.update({k: v for k, v in _lib.DEV.items() if k in VARIANTS})
@@ -189,6 +192,13 @@ def _r1_of(bf, xi):
     return bf._r1_other
 
 
+def _r1T_of(pb, bf, xi):
+    """The transposed activations [H1, m] of a step of parity xi whose sums launch carries the forward middle (VARIANTS['sums_fwd']), made on first use."""
+    if pb["r1T"][xi] is None:
+        pb["r1T"][xi] = torch.empty((bf._H1, bf.m), dtype=torch.float32, device=bf.f.device)
+    return pb["r1T"][xi]
+
+
 def _planes_of(bf, F):
     """Buffers of the two-plane step form (FusedLinearTrainer._planes), made on first use: the two batches' fp16 planes and the
     two images of idl_l1_planes' K-slice partial sums [8][H1][m] (slab 0 of an image becomes the step's transposed activations)."""
@@ -198,6 +208,7 @@ def _planes_of(bf, F):
         bf._planes = {"xh": [torch.empty((m, F), **h16) for _ in range(2)], "xl": [torch.empty((m, F), **h16) for _ in range(2)],
                       "part": [torch.empty((int(_L.idl_l1_planes_parts()), bf._H1, m), dtype=torch.float32, device=dev) for _ in range(2)],
                       "dh": torch.empty((m, bf._H1), **h16), "dl": torch.empty((m, bf._H1), **h16),      # dr1 as planes (mid_bwd -> the dW1 tiles)
+                      "r1T": [None, None],              # sums_fwd: a parity's activations [H1, m] (its partial sums stay as they are)
                       "valid": [False, False],          # valid[i]: xh[i] / xl[i] hold the planes of the batch in bf.xs[i]
                       "x32": [True, True]}              # x32[i]: bf.xs[i] itself holds that batch (False: it was assembled as planes only)
     return bf._planes
@@ -411,6 +422,8 @@ class FusedLinearTrainer(_LinearStepParts):
         # ... whose loader waves run the step's optimizer tail under the tiles' epilogue (IDELUCS_DEV=planes_tail=reduce: the tail beside the
         # next step's partial sums instead, 9.4 us for that launch against 4.7)
         self._planes_tail_wgrad = _v("planes_tail") != "reduce"
+        # ... and the forward middle inside the launch that adds the partial sums (lone voter, tail on the dW1 tiles: _step_planes)
+        self._sums_fwd = int(_v("sums_fwd_rows")) if _v("sums_fwd") == "1" else 0
         self._cus = torch.cuda.get_device_properties(self.dev).multi_processor_count if self.dev.type == "cuda" else 0
         self._ctl_snap = torch.zeros(1, dtype=torch.int64, device=self.dev)       # the step counter as the step's reduce launch saw it (idl_wgrad_xplanes_rms)
         self._w1_planes = None                   # (W1 hi, W1 lo, overflow flag)
@@ -550,6 +563,7 @@ class FusedLinearTrainer(_LinearStepParts):
         """n_clusters <= 48, the two big products from two-plane operands: a1^T = W1 x^T as eight K-slice partial sums on the fp16 matrix
         cores, ONE launch that adds them up on every CU (beside the previous step's pending tail, if any), mid_fwd (its spare workgroups
         assemble the first half of the next batch AND its planes), InfoNCE + IIC, mid_bwd (the other half; dr1 as planes), the dW1 tiles.
+        The lone step with the tail on the dW1 tiles (the default) has the sums and mid_fwd in ONE launch (VARIANTS['sums_fwd']): six launches.
         Lone, or recorded for BatchedLinearTrainer (self._rec: every launch through self._k becomes a record): a recording performs nothing
         and keeps no step state, and it is always the six launches with the tail on the dW1 tiles -- _form's recording branch asks for that
         shape and does not consult planes_wgrad / planes_tail, which choose among the lone step's endings only."""
@@ -565,20 +579,28 @@ class FusedLinearTrainer(_LinearStepParts):
         if not plw:
             self._check_x32(bf, xi)
         part, x = pb["part"][xi], bf.xs[xi]
-        r1 = part[0]                            # [H1, m]: slab 0 of the partial sums, where mid_fwd leaves the activations
+        # the sums launch carries the forward middle (six launches): the lone step with the tail on the dW1 tiles and no tail pending from another ending
+        merged = self._sums_fwd and tail_on_wgrad and not rec and self._pending is None
+        r1 = _r1T_of(pb, bf, xi) if merged else part[0]      # [H1, m]: (else) slab 0 of the partial sums, where mid_fwd leaves the activations
         wh, wl, flag = self._planes_operands(bf, pb, xi)
         if cold:
             self._evict()
-        self._k(_L.idl_l1_planes, _p(wh), _p(wl), F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, _p(part), _stream())
-        if self._pending is not None and not rec:       # (a recording looks at no pending tail: a lockstep voter never leaves one)
-            self._tail_launch(*self._pending, red=(part, H1 * m))
-        else:
-            self._reduce(part, m)
-        if cold:
-            self._evict()
+        self._k(_L.idl_l1_planes_rows if merged else _L.idl_l1_planes, _p(wh), _p(wl), F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, _p(part), _stream())
         nxt = (None if plw else _p(bf.xs[1 - xi]), _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
-        self._k(_L.idl_mid_fwd_gather_planes, _p(part), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
-                0, GATHER_SPLIT, 8, _stream())
+        if merged:          # part[8][m][512] -> sums, ReLU / Dropout (r1), lat, head, softmax by workgroups of whole rows; the riders as in mid_fwd
+            if cold:
+                self._evict()
+            _launch(_L.idl_reduce_mid_fwd_gather_planes, _p(part), _p(self.ctl), _p(self._ctl_snap), self._sums_fwd, _p(r1), _p(self.b1),
+                    *self._mid_fwd_args(bf, tr)[:8], *self._mid_fwd_args(bf, tr)[9:], *self._next_batch(st, m), *nxt, 0, GATHER_SPLIT, 8, _stream())
+        else:
+            if self._pending is not None and not rec:       # (a recording looks at no pending tail: a lockstep voter never leaves one)
+                self._tail_launch(*self._pending, red=(part, H1 * m))
+            else:
+                self._reduce(part, m)
+            if cold:
+                self._evict()
+            self._k(_L.idl_mid_fwd_gather_planes, _p(part), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
+                    0, GATHER_SPLIT, 8, _stream())
         launch_losses(self._k, bf, self.lamb, self.weight, self.out)
         self._k(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), *nxt,
                 GATHER_SPLIT, 8, 8, 1, *self._dr1_planes_args(pb, plw), _stream())
