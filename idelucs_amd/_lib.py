@@ -111,7 +111,7 @@ SIGNATURES = {
     "idl_l1_planes_supported": (_int, [_int, _int, _int]),
     "idl_l1_planes": (_int, [_vp, _vp, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
     "idl_l1_planes_rows": (_int, [_vp, _vp, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
-    "idl_reduce_mid_fwd_gather_planes": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp] +
+    "idl_reduce_mid_fwd_gather_planes": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp] +
                                          [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
     "idl_reduce_parts_rms": (_int, [_vp, _i64, _vp, _vp,
                                     _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp, _int,

@@ -32,16 +32,16 @@
 #include "l1_device.h"
 #include "l1_planes_device.h"
 #include "wgrad_planes_device.h"
-#include "philox_device.h"
+#include "mid_fwd_device.h"
 
 namespace {
 
-constexpr int H2 = 64;        // latent width of NetLinear == one wavefront
-constexpr int MAX_CPL = 4;    // classes per lane: n_clusters <= 256
+using mid_dev::H1;            // mid_fwd_device.h: width of layer 1,
+using mid_dev::H2;            //   latent width of NetLinear == one wavefront,
+using mid_dev::MAX_CPL;       //   classes per lane: n_clusters <= 256
+using mid_dev::f32x4_t;
 constexpr int COL_PARTS = 64; // row chunks of the partial column sums (bias gradients); 16 rows each at m = 1024
 
-using idl_dev::U4;
-using idl_dev::philox;        // philox_device.h: shared with l1_fwd.hip, which takes over mid_fwd_kernel's layer-1 dropout
 
 // Diagnostic phase stamps of the two middle kernels (a build with -DIDL_PHASE_STAMPS: `make STAMPS=1`; tools/stamps_mid.py): when
 // armed (idl_debug_phase_stamps), workgroups 0..63 of the stamped kernel leave up to eight s_memrealtime marks (100 MHz) each in
@@ -64,18 +64,8 @@ __global__ __launch_bounds__(256) void relu_dropout_fwd_kernel(float4 *a, int64_
                                                                uint32_t layer)
 {
     const uint32_t step = (uint32_t)ctl[0];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 v = a[i];
-        float s0 = 1.f, s1 = 1.f, s2 = 1.f, s3 = 1.f;
-        if (train) {
-            const U4 r = philox((uint32_t)i, layer, step, (uint32_t)(i >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-            s0 = (r.x >> 31) ? 2.f : 0.f; s1 = (r.y >> 31) ? 2.f : 0.f;
-            s2 = (r.z >> 31) ? 2.f : 0.f; s3 = (r.w >> 31) ? 2.f : 0.f;
-        }
-        v.x = v.x > 0.f ? v.x * s0 : 0.f; v.y = v.y > 0.f ? v.y * s1 : 0.f;
-        v.z = v.z > 0.f ? v.z * s2 : 0.f; v.w = v.w > 0.f ? v.w * s3 : 0.f;
-        a[i] = v;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+        a[i] = mid_dev::relu_dropout4(a[i], i, layer, train, seed, step);
 }
 
 // ---------------------------------------------------------------- head forward: one wave per row
@@ -84,47 +74,22 @@ __global__ __launch_bounds__(256) void relu_dropout_fwd_kernel(float4 *a, int64_
 __device__ __forceinline__ void head_row(float x, int row, int lane, float *sh, const float *W3, const float *b3, int C, int train,
                                          uint64_t seed, uint32_t step, float *f, float *inv, float *r2, float *z)
 {
-    const float nrm = fmaxf(sqrtf(wave_sum(x * x)), 1e-12f);       // F.normalize(dim=1), eps 1e-12
-    f[(int64_t)row * H2 + lane] = x / nrm;
-    if (lane == 0) inv[row] = 1.f / nrm;
-    float s = 1.f;
-    if (train) {
-        const U4 r = philox((uint32_t)row, 2u, step, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-        const uint32_t word = (lane < 32) ? r.x : r.y;
-        s = ((word >> (lane & 31)) & 1u) ? 2.f : 0.f;
-    }
-    const float a = x > 0.f ? x * s : 0.f;
-    r2[(int64_t)row * H2 + lane] = a;
-    sh[lane] = a;
+    sh[lane] = mid_dev::latent_row(x, row, lane, true, train, seed, step, f, inv, r2);
     __builtin_amdgcn_wave_barrier();
-    float lg[MAX_CPL];
-    float mx = -INFINITY;
+    mid_dev::RowLogits lg;
 #pragma unroll
     for (int t = 0; t < MAX_CPL; ++t) {
         const int c = t * 64 + lane;
-        lg[t] = -INFINITY;
+        lg.v[t] = -INFINITY;
         if (c < C) {
             float acc = b3[c];
             const float *wr = W3 + (int64_t)c * H2;
 #pragma unroll 8
             for (int h = 0; h < H2; ++h) acc = fmaf(sh[h], wr[h], acc);
-            lg[t] = acc;
-            mx = fmaxf(mx, acc);
+            lg.v[t] = acc;
         }
     }
-    mx = wave_max(mx);
-    float den = 0.f;
-#pragma unroll
-    for (int t = 0; t < MAX_CPL; ++t) {
-        const int c = t * 64 + lane;
-        if (c < C) { lg[t] = __expf(lg[t] - mx); den += lg[t]; }
-    }
-    den = wave_sum(den);
-#pragma unroll
-    for (int t = 0; t < MAX_CPL; ++t) {
-        const int c = t * 64 + lane;
-        if (c < C) z[(int64_t)row * C + c] = lg[t] / den;
-    }
+    mid_dev::softmax_row(lg, row, lane, C, true, z);
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -145,9 +110,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float *lat, const f
 //                            consecutive k of one row, so A is read and masked exactly once -- partial tiles added through LDS)
 //   head_row() one row per wave (normalise, ReLU/Dropout, Linear(64,C), softmax)
 // replacing relu_dropout_fwd + one hipBLASLt GEMM + head_fwd.  Same dropout streams as those kernels.
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-constexpr int H1 = 512;
-constexpr int MID_WAVES = 16;
+constexpr int MID_WAVES = mid_dev::WAVES;
 constexpr int MID_GATHER_ROWS = 4;   // rows per 256-thread gather tile when the batch assembly rides in mid_fwd / mid_bwd
 
 // (Round 5's variant that added idl_l1_planes' eight K-slice partial sums up HERE -- 16 MB read by 64 workgroups: +8 us -- left in round 6: idl_reduce_parts_rms does it on every CU.
@@ -180,13 +143,10 @@ __device__ __forceinline__ void mid_fwd_body(float *__restrict__ a1, const float
     float *srcT = a1 + (int64_t)k0 * m + r0 + l;             // element (row r0 + l, column k0 + i) of the transposed image: srcT[i * m]
     float4 av[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
     float4 bb[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-    float4 bw[4][2];
-    auto load_bw = [&]() {
+    mid_dev::W2Tile bw[4];
+    auto load_bw = [&]() {                       // (stays a lambda: as a plain loop the address arithmetic is scheduled differently)
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {             // lat[:, 16 ct .. 16 ct + 15]: B[k][c] = W2[16 ct + c][k]
-            const float4 *wsrc = (const float4 *)(W2 + (int64_t)(16 * ct + l) * H1 + k0);
-            bw[ct][0] = wsrc[0]; bw[ct][1] = wsrc[1];
-        }
+        for (int ct = 0; ct < 4; ++ct) bw[ct] = mid_dev::load_w2(W2, ct, l, k0);
     };
     float t8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (TIN) {
@@ -201,48 +161,26 @@ __device__ __forceinline__ void mid_fwd_body(float *__restrict__ a1, const float
     const int nct = (C + 15) / 16;               // column tiles of the logits; wave wv < nct owns tile wv
     float4 w3f[4];                               // B[k = 16 q + s][c = l] = W3[16 wv + l][16 q + s]
     float b3v = 0.f;
-    if (wv < nct) {
-        const int c = min(16 * wv + l, C - 1);
-        const float4 *wsrc = (const float4 *)(W3 + (int64_t)c * H2 + 16 * q);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w3f[i] = wsrc[i];
-        b3v = b3[c];
-    }
+    if (wv < nct) mid_dev::load_w3(w3f, b3v, W3, b3, wv, l, q, C);
     const float b2v = b2[lane];
     const uint32_t step = (uint32_t)ctl[0];
     {
-    // ---- ReLU + Dropout of layer 1, in place
-    float a[8];
+    // ---- ReLU + Dropout of layer 1, in place: the counter is the float4 index of the flat [m][512] array
+    mid_dev::R1Frag a;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         float4 v = av[i];
         v.x += bb[i].x; v.y += bb[i].y; v.z += bb[i].z; v.w += bb[i].w;      // Linear(F,512) bias when the product came without it
-        float s0 = 1.f, s1 = 1.f, s2 = 1.f, s3 = 1.f;
-        if (train) {                             // identical stream to relu_dropout_fwd_kernel: counter = float4 index of the flat array
-            const int64_t idx4 = ((int64_t)(r0 + l) * H1 + k0) / 4 + i;
-            const U4 r = philox((uint32_t)idx4, 1u, step, (uint32_t)(idx4 >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-            s0 = (r.x >> 31) ? 2.f : 0.f; s1 = (r.y >> 31) ? 2.f : 0.f;
-            s2 = (r.z >> 31) ? 2.f : 0.f; s3 = (r.w >> 31) ? 2.f : 0.f;
-        }
-        v.x = v.x > 0.f ? v.x * s0 : 0.f; v.y = v.y > 0.f ? v.y * s1 : 0.f;
-        v.z = v.z > 0.f ? v.z * s2 : 0.f; v.w = v.w > 0.f ? v.w * s3 : 0.f;
+        v = mid_dev::relu_dropout4(v, ((int64_t)(r0 + l) * H1 + k0) / 4 + i, 1u, train, seed, step);
         if (TIN) { srcT[(int64_t)(4 * i) * m] = v.x; srcT[(int64_t)(4 * i + 1) * m] = v.y; srcT[(int64_t)(4 * i + 2) * m] = v.z; srcT[(int64_t)(4 * i + 3) * m] = v.w; }
         else src[i] = v;
-        a[4 * i] = v.x; a[4 * i + 1] = v.y; a[4 * i + 2] = v.z; a[4 * i + 3] = v.w;
+        a.k[4 * i] = v.x; a.k[4 * i + 1] = v.y; a.k[4 * i + 2] = v.z; a.k[4 * i + 3] = v.w;
     }
     IDL_PHASE_STAMP(stf, 1);                     // (wave 0: its loads have arrived, ReLU / Dropout done)
     // ---- lat = r1 W2^T: this wave's K-slice
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const float4 b = bw[ct][i];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i], b.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i + 1], b.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i + 2], b.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i + 3], b.w, acc, 0, 0, 0);
-        }
+        const f32x4_t acc = mid_dev::kslice_tile(a, bw[ct]);
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) part[wv][4 * q + reg][(16 * ct + l + 16 * q) & 63] = acc[reg];   // C/D: row = 4q+reg, col = l
     }
@@ -251,67 +189,24 @@ __device__ __forceinline__ void mid_fwd_body(float *__restrict__ a1, const float
     IDL_PHASE_STAMP(stf, 3);
     }
     // ---- wave wv owns row wv of the tile: add the 16 K-slices and the bias; normalise; ReLU + Dropout of the latent
-    const int row = r0 + wv, cs = (lane + 16 * (wv >> 2)) & 63;
-    float x = b2v;
-#pragma unroll
-    for (int w = 0; w < MID_WAVES; ++w) x += part[w][wv][cs];
-    const float nrm = fmaxf(sqrtf(wave_sum(x * x)), 1e-12f);       // F.normalize(dim=1), eps 1e-12
-    float sc = 1.f;
-    if (train) {                                 // as head_row
-        const U4 r = philox((uint32_t)row, 2u, step, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-        const uint32_t word = (lane < 32) ? r.x : r.y;
-        sc = ((word >> (lane & 31)) & 1u) ? 2.f : 0.f;
-    }
-    const float ar = x > 0.f ? x * sc : 0.f;
-    if (row < m) {
-        f[(int64_t)row * H2 + lane] = x / nrm;
-        if (lane == 0) inv[row] = 1.f / nrm;
-        r2[(int64_t)row * H2 + lane] = ar;
-    }
+    const int cs = (lane + 16 * (wv >> 2)) & 63;
+    const float x = mid_dev::add_slices(b2v, &part[0][wv][cs], 16 * H2);
+    const int row = r0 + wv;
+    const float ar = mid_dev::latent_row(x, row, lane, row < m, train, seed, step, f, inv, r2);
     __syncthreads();                             // part is dead
     R2t[wv][lane] = ar;
     __syncthreads();
     IDL_PHASE_STAMP(stf, 4);
     // ---- logits tile wv = r2[16 x 64] W3[16 wv .. 16 wv + 15]^T + b3
     if (wv < nct) {
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 t = *(const float4 *)&R2t[l][16 * q + 4 * i];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.x, w3f[i].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.y, w3f[i].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.z, w3f[i].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.w, w3f[i].w, acc, 0, 0, 0);
-        }
+        const f32x4_t acc = mid_dev::logits_tile(R2t, w3f, l, q);
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) LG[4 * q + reg][16 * wv + l] = acc[reg] + b3v;
     }
     __syncthreads();
     IDL_PHASE_STAMP(stf, 5);
     // ---- softmax of row wv
-    float lg[MAX_CPL];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < MAX_CPL; ++t) {
-        const int c = t * 64 + lane;
-        lg[t] = c < C ? LG[wv][c] : -INFINITY;
-        mx = fmaxf(mx, lg[t]);
-    }
-    mx = wave_max(mx);
-    float den = 0.f;
-#pragma unroll
-    for (int t = 0; t < MAX_CPL; ++t) {
-        const int c = t * 64 + lane;
-        if (c < C) { lg[t] = __expf(lg[t] - mx); den += lg[t]; }
-    }
-    den = wave_sum(den);
-    if (row < m) {
-#pragma unroll
-        for (int t = 0; t < MAX_CPL; ++t) {
-            const int c = t * 64 + lane;
-            if (c < C) z[(int64_t)row * C + c] = lg[t] / den;
-        }
-    }
+    mid_dev::softmax_row(mid_dev::load_logits(LG[wv], lane, C), row, lane, C, row < m, z);
     IDL_PHASE_STAMP(stf, 6);
 }
 struct MidFwdParams {
@@ -1245,27 +1140,51 @@ struct ReduceArgs { float4 *part; int64_t slab4; int n_parts, blocks; const int6
 //  the counter when they start and its own loader waves move it when they end: on a GPU shared with another process not every tile starts
 //  before the first one ends)
 constexpr int RED_U = 2;
-// ROWS = 4 or 8 (1024 threads): the instance that ALSO runs the forward middle on the rows it has just summed (sums_fwd_body below); its second argument is
-// the middle's (SumsFwdArgs), the rest unused.  ROWS = 0: the sums (and the tail) alone, as ever.
+__global__ __launch_bounds__(256) void reduce_rms_kernel(ReduceArgs r, RmsArgs a, const float *hyper, int64_t *ctl, int64_t batch_advance, int with_tail)
+{
+    // grid order: the tail's workgroups FIRST (theirs is the longer chain: 7.1 us on its own against the sums' 4.7), the sums behind them
+    const int n_tail = (int)gridDim.x - r.blocks;
+    if ((int)blockIdx.x >= n_tail) {
+        if (r.ctl_snap != nullptr && (int)blockIdx.x == n_tail && threadIdx.x == 0) *r.ctl_snap = r.ctl_src[0];
+        const int64_t i0 = (int64_t)((int)blockIdx.x - n_tail) * (256 * RED_U) + threadIdx.x;
+        float4 v[RED_U][l1p_dev::KSPLIT];
+#pragma unroll
+        for (int u = 0; u < RED_U; ++u) {
+            const int64_t i = i0 + 256 * u < r.slab4 ? i0 + 256 * u : r.slab4 - 1;     // clamped, not predicated
+#pragma unroll
+            for (int p = 0; p < l1p_dev::KSPLIT; ++p) v[u][p] = r.part[(int64_t)p * r.slab4 + i];
+        }
+#pragma unroll
+        for (int u = 0; u < RED_U; ++u) {
+            float4 acc = v[u][0];
+#pragma unroll
+            for (int p = 1; p < l1p_dev::KSPLIT; ++p) { acc.x += v[u][p].x; acc.y += v[u][p].y; acc.z += v[u][p].z; acc.w += v[u][p].w; }
+            if (i0 + 256 * u < r.slab4) r.part[i0 + 256 * u] = acc;
+        }
+        return;
+    }
+    // (the look-ahead form of the dW2 tiles -- every operand of a wave requested before its first product: one trip to memory instead of
+    //  three -- as behind the dW1 tiles of wgrad_rmsprop_kernel: here too the tail's chain is the launch's length, 9.3 us without)
+    if (with_tail) rmsprop_body<true>(a, hyper, ctl, batch_advance, 0, 0, idl_dev::GatherArgs{}, (int)blockIdx.x, (int)threadIdx.x);
+}
+
+// The sums launch carrying the whole forward middle (n_clusters <= 48, the lone voter's step): the partial sums come as part[8][m][512] (idl_l1_planes_rows) and a
+// workgroup owns ROWS = 8 whole rows of the batch -- m / 8 computing workgroups instead of mid_fwd's m / 16 -- with the batch-assembly riders behind them as in
+// mid_fwd_body.  The 16-row MFMA tile keeps its shape; the rows the workgroup does not own are zero, and their lanes share out the partial-sum loads: lane row
+// l = ROWS g + r loads slabs [SPL g, SPL g + SPL) of row r (SPL = ROWS / 2), the running sum is handed from group g to group g + 1 by DPP row_shr:ROWS, so row r is
+// ((p0 + p1) + p2) + ... + p7 in the LAST group's lanes -- reduce_rms_kernel's bits -- and the tile's rows [16 - ROWS, 16) are the valid ones.  From there on the
+// stages are mid_fwd_body<true>'s (mid_fwd_device.h) on the same operands (rows of an MFMA tile are independent).  r1 goes to a buffer of its own, transposed
+// [512][m] as mid_bwd and the dW2 tiles read it; part is only read.  Every global read is issued before the first dependent instruction, 16 bytes a lane.
+// (An instance of 4 rows a workgroup, twice the workgroups, was measured slower than the two launches and left: DESIGN 4.4.)
 struct SumsFwdArgs {
     const float *b1, *W2, *b2, *W3, *b3; float *r1T; int m, C, train; uint64_t seed; float *f, *inv, *r2, *z; int tile0, tile1; idl_dev::GatherArgs gth;
 };
-template <int ROWS> struct RedSecond { typedef SumsFwdArgs type; };
-template <> struct RedSecond<0> { typedef RmsArgs type; };
+constexpr int SUMS_FWD_ROWS = 8;
+constexpr int SUMS_FWD_LDS = (MID_WAVES * SUMS_FWD_ROWS * H2 + 16 * (H2 + 4) + SUMS_FWD_ROWS * (64 * MAX_CPL + 1)) * (int)sizeof(float);
 
-// The sums launch carrying the whole forward middle (n_clusters <= 48, the lone voter's step): the partial sums come as part[8][m][512] (idl_l1_planes_rows) and a
-// workgroup owns ROWS whole rows of the batch -- m / ROWS computing workgroups instead of mid_fwd's m / 16 -- with the batch-assembly riders behind them as in
-// mid_fwd_body.  The 16-row MFMA tile keeps its shape; the rows the workgroup does not own are zero, and their lanes share out the partial-sum loads: lane row
-// l = ROWS g + r loads slabs [SPL g, SPL g + SPL) of row r (SPL = ROWS / 2), the running sum is handed from group g to group g + 1 by DPP row_shr:ROWS, so row r is
-// ((p0 + p1) + p2) + ... + p7 in the LAST group's lanes -- reduce_rms_kernel<0>'s bits -- and the tile's rows [16 - ROWS, 16) are the valid ones.  From there on it
-// is mid_fwd_body<true>'s arithmetic on the same operands (rows of an MFMA tile are independent): the same Philox counters (the flat index of [m][512]), the
-// same 32 MFMAs a wave over its 32-k slice, the 16-slice add in the same order, normalise, the head, logits, softmax.  r1 goes to a buffer of its own, transposed
-// [512][m] as mid_bwd and the dW2 tiles read it; part is only read.  Every global read is issued before the first dependent instruction, 16 bytes a lane.
-template <int ROWS>
 __device__ __forceinline__ void sums_fwd_body(const ReduceArgs &r, const SumsFwdArgs &p, float *smem, const int bid)
 {
-    static_assert(ROWS == 4 || ROWS == 8, "rows of the batch a workgroup owns");
-    constexpr int GROUPS = 16 / ROWS, SPL = l1p_dev::KSPLIT / GROUPS, Q0 = 4 - ROWS / 4;      // Q0: the first lane quarter whose C/D rows are valid
+    constexpr int ROWS = SUMS_FWD_ROWS, GROUPS = 16 / ROWS, SPL = l1p_dev::KSPLIT / GROUPS, Q0 = 4 - ROWS / 4;      // Q0: the first lane quarter whose C/D rows are valid
     if (bid >= r.blocks) {           // riders: tiles [tile0, tile1) of the next batch (mid_fwd_body)
         const int blk = p.tile0 + (bid - r.blocks) * 4 + (int)(threadIdx.x >> 8);
         if (blk < p.tile1) idl_dev::gather_tile<MID_GATHER_ROWS>(p.gth, (int64_t)blk, (int)(threadIdx.x & 255));
@@ -1291,16 +1210,13 @@ __device__ __forceinline__ void sums_fwd_body(const ReduceArgs &r, const SumsFwd
     }
     float4 bb[2];
     bb[0] = *(const float4 *)(p.b1 + k0); bb[1] = *(const float4 *)(p.b1 + k0 + 4);
-    float4 bw[4][2];
+    mid_dev::W2Tile bw[4];
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {             // lat[:, 16 ct .. 16 ct + 15]: B[k][c] = W2[16 ct + c][k]
-        const float4 *wsrc = (const float4 *)(p.W2 + (int64_t)(16 * ct + l) * H1 + k0);
-        bw[ct][0] = wsrc[0]; bw[ct][1] = wsrc[1];
-    }
+    for (int ct = 0; ct < 4; ++ct) bw[ct] = mid_dev::load_w2(p.W2, ct, l, k0);
     const int nct = (C + 15) / 16;               // column tiles of the logits; wave wv < nct owns tile wv
     float4 w3f[4];                               // B[k = 16 q + s][c = l] = W3[16 wv + l][16 q + s]
     float b3v = 0.f;
-    if (wv < nct) {
+    if (wv < nct) {                              // mid_dev::load_w3's text, written out: through the helper this kernel, at its 128 registers, spills (20 bytes a lane)
         const int c = min(16 * wv + l, C - 1);
         const float4 *wsrc = (const float4 *)(p.W3 + (int64_t)c * H2 + 16 * q);
 #pragma unroll
@@ -1334,39 +1250,23 @@ __device__ __forceinline__ void sums_fwd_body(const ReduceArgs &r, const SumsFwd
             sum[i] = acc;
         }
     }
-    // ---- bias, ReLU + Dropout of layer 1; r1 out, transposed
-    float a[8];
+    // ---- bias, ReLU + Dropout of layer 1; r1 out, transposed; the rows this lane does not own enter the tile as zeros
+    mid_dev::R1Frag a;
     float *dstT = p.r1T + (int64_t)k0 * m + r0 + rr;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         float4 v = make_float4(sum[4 * i], sum[4 * i + 1], sum[4 * i + 2], sum[4 * i + 3]);
         v.x += bb[i].x; v.y += bb[i].y; v.z += bb[i].z; v.w += bb[i].w;
-        float s0 = 1.f, s1 = 1.f, s2 = 1.f, s3 = 1.f;
-        if (train) {                             // identical stream to relu_dropout_fwd_kernel: counter = float4 index of the flat array
-            const int64_t idx4 = e4 + i;
-            const U4 rn = philox((uint32_t)idx4, 1u, step, (uint32_t)(idx4 >> 32), (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-            s0 = (rn.x >> 31) ? 2.f : 0.f; s1 = (rn.y >> 31) ? 2.f : 0.f;
-            s2 = (rn.z >> 31) ? 2.f : 0.f; s3 = (rn.w >> 31) ? 2.f : 0.f;
-        }
-        v.x = v.x > 0.f ? v.x * s0 : 0.f; v.y = v.y > 0.f ? v.y * s1 : 0.f;
-        v.z = v.z > 0.f ? v.z * s2 : 0.f; v.w = v.w > 0.f ? v.w * s3 : 0.f;
+        v = mid_dev::relu_dropout4(v, e4 + i, 1u, train, p.seed, step);
         if (own) {
             dstT[(int64_t)(4 * i) * m] = v.x; dstT[(int64_t)(4 * i + 1) * m] = v.y; dstT[(int64_t)(4 * i + 2) * m] = v.z; dstT[(int64_t)(4 * i + 3) * m] = v.w;
         }
-        a[4 * i] = own ? v.x : 0.f; a[4 * i + 1] = own ? v.y : 0.f; a[4 * i + 2] = own ? v.z : 0.f; a[4 * i + 3] = own ? v.w : 0.f;
+        a.k[4 * i] = own ? v.x : 0.f; a.k[4 * i + 1] = own ? v.y : 0.f; a.k[4 * i + 2] = own ? v.z : 0.f; a.k[4 * i + 3] = own ? v.w : 0.f;
     }
     // ---- lat = r1 W2^T: this wave's K-slice; the owned rows are C/D rows 4 q + reg of the quarters q >= Q0
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const float4 b = bw[ct][i];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i], b.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i + 1], b.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i + 2], b.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * i + 3], b.w, acc, 0, 0, 0);
-        }
+        const f32x4_t acc = mid_dev::kslice_tile(a, bw[ct]);
         if (q >= Q0) {
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) ps[wv][4 * (q - Q0) + reg][16 * ct + l] = acc[reg];
@@ -1377,100 +1277,26 @@ __device__ __forceinline__ void sums_fwd_body(const ReduceArgs &r, const SumsFwd
     // ---- wave wv < ROWS owns row wv: add the 16 K-slices and the bias; normalise; ReLU + Dropout of the latent
     const int row = r0 + wv;
     float ar = 0.f;
-    if (wv < ROWS) {
-        float x = b2v;
-#pragma unroll
-        for (int w = 0; w < MID_WAVES; ++w) x += ps[w][wv][lane];
-        const float nrm = fmaxf(sqrtf(wave_sum(x * x)), 1e-12f);       // F.normalize(dim=1), eps 1e-12
-        float sc = 1.f;
-        if (train) {                             // as head_row
-            const U4 rn = philox((uint32_t)row, 2u, step, 0u, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-            const uint32_t word = (lane < 32) ? rn.x : rn.y;
-            sc = ((word >> (lane & 31)) & 1u) ? 2.f : 0.f;
-        }
-        ar = x > 0.f ? x * sc : 0.f;
-        p.f[(int64_t)row * H2 + lane] = x / nrm;
-        if (lane == 0) p.inv[row] = 1.f / nrm;
-        p.r2[(int64_t)row * H2 + lane] = ar;
-    }
+    if (wv < ROWS) ar = mid_dev::latent_row(mid_dev::add_slices(b2v, &ps[0][wv][lane], ROWS * H2), row, lane, true, train, p.seed, step, p.f, p.inv, p.r2);
     R2t[wv][lane] = ar;                          // (its own memory: no barrier between the reads of ps and this)
     __syncthreads();
     // ---- logits tile wv = r2[16 x 64] W3[16 wv .. 16 wv + 15]^T + b3; the owned rows are the tile's first ROWS here
     if (wv < nct) {
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 t = *(const float4 *)&R2t[l][16 * q + 4 * i];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.x, w3f[i].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.y, w3f[i].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.z, w3f[i].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(t.w, w3f[i].w, acc, 0, 0, 0);
-        }
+        const f32x4_t acc = mid_dev::logits_tile(R2t, w3f, l, q);
         if (4 * q < ROWS) {
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) LG[4 * q + reg][16 * wv + l] = acc[reg] + b3v;
         }
     }
     __syncthreads();
-    if (wv >= ROWS) return;
     // ---- softmax of row wv
-    float lg[MAX_CPL];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < MAX_CPL; ++t) {
-        const int c = t * 64 + lane;
-        lg[t] = c < C ? LG[wv][c] : -INFINITY;
-        mx = fmaxf(mx, lg[t]);
-    }
-    mx = wave_max(mx);
-    float den = 0.f;
-#pragma unroll
-    for (int t = 0; t < MAX_CPL; ++t) {
-        const int c = t * 64 + lane;
-        if (c < C) { lg[t] = __expf(lg[t] - mx); den += lg[t]; }
-    }
-    den = wave_sum(den);
-#pragma unroll
-    for (int t = 0; t < MAX_CPL; ++t) {
-        const int c = t * 64 + lane;
-        if (c < C) p.z[(int64_t)row * C + c] = lg[t] / den;
-    }
+    if (wv < ROWS) mid_dev::softmax_row(mid_dev::load_logits(LG[wv], lane, C), row, lane, C, true, p.z);
 }
-template <int ROWS> constexpr int sums_fwd_lds() { return (MID_WAVES * ROWS * H2 + 16 * (H2 + 4) + ROWS * (64 * MAX_CPL + 1)) * (int)sizeof(float); }
 
-template <int ROWS>
-__global__ __launch_bounds__(ROWS ? 64 * MID_WAVES : 256) void reduce_rms_kernel(ReduceArgs r, typename RedSecond<ROWS>::type a, const float *hyper, int64_t *ctl,
-                                                                                 int64_t batch_advance, int with_tail)
+__global__ __launch_bounds__(64 * MID_WAVES) void sums_fwd_kernel(ReduceArgs r, SumsFwdArgs p)
 {
-    if constexpr (ROWS != 0) {
-        extern __shared__ __attribute__((aligned(16))) float sums_fwd_smem[];
-        sums_fwd_body<ROWS>(r, a, sums_fwd_smem, (int)blockIdx.x);
-    } else {
-    // grid order: the tail's workgroups FIRST (theirs is the longer chain: 7.1 us on its own against the sums' 4.7), the sums behind them
-    const int n_tail = (int)gridDim.x - r.blocks;
-    if ((int)blockIdx.x >= n_tail) {
-        if (r.ctl_snap != nullptr && (int)blockIdx.x == n_tail && threadIdx.x == 0) *r.ctl_snap = r.ctl_src[0];
-        const int64_t i0 = (int64_t)((int)blockIdx.x - n_tail) * (256 * RED_U) + threadIdx.x;
-        float4 v[RED_U][l1p_dev::KSPLIT];
-#pragma unroll
-        for (int u = 0; u < RED_U; ++u) {
-            const int64_t i = i0 + 256 * u < r.slab4 ? i0 + 256 * u : r.slab4 - 1;     // clamped, not predicated
-#pragma unroll
-            for (int p = 0; p < l1p_dev::KSPLIT; ++p) v[u][p] = r.part[(int64_t)p * r.slab4 + i];
-        }
-#pragma unroll
-        for (int u = 0; u < RED_U; ++u) {
-            float4 acc = v[u][0];
-#pragma unroll
-            for (int p = 1; p < l1p_dev::KSPLIT; ++p) { acc.x += v[u][p].x; acc.y += v[u][p].y; acc.z += v[u][p].z; acc.w += v[u][p].w; }
-            if (i0 + 256 * u < r.slab4) r.part[i0 + 256 * u] = acc;
-        }
-        return;
-    }
-    // (the look-ahead form of the dW2 tiles -- every operand of a wave requested before its first product: one trip to memory instead of
-    //  three -- as behind the dW1 tiles of wgrad_rmsprop_kernel: here too the tail's chain is the launch's length, 9.3 us without)
-    if (with_tail) rmsprop_body<true>(a, hyper, ctl, batch_advance, 0, 0, idl_dev::GatherArgs{}, (int)blockIdx.x, (int)threadIdx.x);
-    }
+    extern __shared__ __attribute__((aligned(16))) float sums_fwd_smem[];
+    sums_fwd_body(r, p, sums_fwd_smem, (int)blockIdx.x);
 }
 
 // The dW1 tiles of the two-plane form (wgrad_planes_device.h) with THIS step's optimizer tail carried by their loader waves: a workgroup's four
@@ -1628,6 +1454,29 @@ int idl_mid_fwd(float *a1, const float *W2, const float *b2, const float *W3, co
     return IDL_OK;
 }
 
+// The batch-assembly riders of a middle launch (mid_fwd, mid_bwd, the sums launch): their arguments checked; the kernels' GatherArgs and the tiles [t0, t1)
+// -- shares [part, part_end) of `parts` of the next batch -- four to a rider workgroup.  feats == NULL: no riders in this launch.
+struct Riders {
+    idl_dev::GatherArgs g{}; int t0 = 0, t1 = 0;
+    unsigned wgs() const { return (unsigned)((t1 - t0 + 3) / 4); }
+};
+static int riders_of(const char *who, const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
+                     int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale, const double *inv_scale, float *y,
+                     uint16_t *yh, uint16_t *yl, int *over, int part, int part_end, int parts, Riders &out)
+{
+    const auto bad = [who](const char *what) { idl::set_error("bad argument: %s: %s", who, what); return IDL_ERR_ARG; };      // (IDL_REQUIRE's message, the caller named)
+    if (!(parts >= 1 && part >= 0 && part <= part_end && part_end <= parts)) return bad("need 0 <= part <= part_end <= parts");
+    if (!((yh != nullptr) == (yl != nullptr) && (yh == nullptr || (feats != nullptr && ((((uintptr_t)yh) | ((uintptr_t)yl)) & 7u) == 0))))
+        return bad("both planes of the next batch (8-byte aligned) or neither; planes need the batch assembly");
+    out = Riders{};
+    if (feats == nullptr) return IDL_OK;
+    if (!(pair_idx && mean && scale && (y || yh) && n >= 1 && fdim >= 4 && (fdim & 3) == 0 && batch >= 1 && n_pairs >= 0)) return bad("bad gather arguments (4 | f)");
+    out.g = idl_dev::GatherArgs{feats, n, fdim, view_stride, pair_idx, base, batch, n_pairs, mean, scale, inv_scale, y, base_add, yh, yl, over};
+    const int64_t ng = idl_dev::gather_tiles<MID_GATHER_ROWS>(fdim, batch);
+    out.t0 = (int)(ng * part / parts); out.t1 = (int)(ng * part_end / parts);
+    return IDL_OK;
+}
+
 static int mid_fwd_gather_impl(float *a1, const float *b1, int a1_transposed, const float *W2, const float *b2, const float *W3, const float *b3, int m,
                        int C, int train, uint64_t seed, const int64_t *ctl, float *f, float *inv, float *r2, float *z,
                        const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
@@ -1637,33 +1486,24 @@ static int mid_fwd_gather_impl(float *a1, const float *b1, int a1_transposed, co
     IDL_REQUIRE(a1 && W2 && b2 && W3 && b3 && ctl && f && inv && r2 && z, "NULL buffer");
     IDL_REQUIRE(m >= 16 && (m % 16) == 0 && C >= 1 && C <= 64 * MAX_CPL, "mid_fwd: m must be a multiple of 16, n_clusters in 1..256");
     IDL_REQUIRE((((uintptr_t)a1 | (uintptr_t)W2 | (uintptr_t)W3) & 15u) == 0, "a1 / W2 / W3 must be 16-byte aligned");
-    IDL_REQUIRE(parts >= 1 && part >= 0 && part <= part_end && part_end <= parts, "mid_fwd_gather: need 0 <= part <= part_end <= parts");
     IDL_REQUIRE(b1 == nullptr || (((uintptr_t)b1) & 15u) == 0, "mid_fwd_gather: b1 must be 16-byte aligned");
     IDL_REQUIRE(a1_transposed == 0 || a1_transposed == 1, "mid_fwd_gather: a1_transposed is 0 or 1");
-    IDL_REQUIRE((yh != nullptr) == (yl != nullptr) && (yh == nullptr || (feats != nullptr && ((((uintptr_t)yh) | ((uintptr_t)yl)) & 7u) == 0)),
-                "mid_fwd_gather: both planes of the next batch (8-byte aligned) or neither; planes need the batch assembly");
-    idl_dev::GatherArgs g{};
-    int64_t t0 = 0, t1 = 0;
-    if (feats != nullptr) {                  // (feats == NULL: no batch assembly in this launch)
-        IDL_REQUIRE(pair_idx && mean && scale && (y || yh) && n >= 1 && fdim >= 4 && (fdim & 3) == 0 && batch >= 1 && n_pairs >= 0,
-                    "mid_fwd_gather: bad gather arguments (4 | f)");
-        g = idl_dev::GatherArgs{feats, n, fdim, view_stride, pair_idx, base, batch, n_pairs, mean, scale, inv_scale, y, base_add, yh, yl, over};
-        const int64_t ng = idl_dev::gather_tiles<MID_GATHER_ROWS>(fdim, batch);
-        t0 = ng * part / parts; t1 = ng * part_end / parts;
-    }
-    const dim3 grid((unsigned)(m / 16 + (t1 - t0 + 3) / 4));
+    Riders rd;
+    if (const int rc = riders_of("mid_fwd_gather", feats, n, fdim, view_stride, pair_idx, base, base_add, n_pairs, batch, mean, scale, inv_scale, y, yh, yl, over,
+                                 part, part_end, parts, rd)) return rc;
+    const dim3 grid((unsigned)(m / 16) + rd.wgs());
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin)
         idl::PlanHead h{};
         h.kind = idl::PLAN_MID_FWD; h.variant = a1_transposed; /* 0 row-major, 1 transposed */ h.grid[0] = grid.x; h.grid[1] = 1; h.grid[2] = 1; h.block = 64 * MID_WAVES;
         memcpy(plan, &h, sizeof(h));
-        const MidFwdParams p{a1, b1, W2, b2, W3, b3, m, C, train, seed, ctl, f, inv, r2, z, m / 16, (int)t0, (int)t1, g};
+        const MidFwdParams p{a1, b1, W2, b2, W3, b3, m, C, train, seed, ctl, f, inv, r2, z, m / 16, rd.t0, rd.t1, rd.g};
         memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
         return IDL_OK;
     }
     if (a1_transposed) hipLaunchKernelGGL(mid_fwd_kernel<true>, grid, dim3(64 * MID_WAVES), 0, (hipStream_t)stream, a1, b1, W2, b2, W3, b3,
-                                          m, C, train, seed, ctl, f, inv, r2, z, m / 16, (int)t0, (int)t1, g);
+                                          m, C, train, seed, ctl, f, inv, r2, z, m / 16, rd.t0, rd.t1, rd.g);
     else hipLaunchKernelGGL(mid_fwd_kernel<false>, grid, dim3(64 * MID_WAVES), 0, (hipStream_t)stream, a1, b1, W2, b2, W3, b3,
-                            m, C, train, seed, ctl, f, inv, r2, z, m / 16, (int)t0, (int)t1, g);
+                            m, C, train, seed, ctl, f, inv, r2, z, m / 16, rd.t0, rd.t1, rd.g);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }
@@ -1818,9 +1658,6 @@ static int mid_bwd_gather_impl(const float *z, const float *r2, const float *f, 
 {
     IDL_REQUIRE((dr1h != nullptr) == (dr1l != nullptr) && (dr1h == nullptr || (dscale && over && ((((uintptr_t)dr1h) | ((uintptr_t)dr1l)) & 15u) == 0)),
                 "mid_bwd_gather: dr1's planes need both planes (16-byte aligned), the words of their scale and the flag");
-    IDL_REQUIRE((yh != nullptr) == (yl != nullptr) && (yh == nullptr || (feats != nullptr && ((((uintptr_t)yh) | ((uintptr_t)yl)) & 7u) == 0)),
-                "mid_bwd_gather: both planes of the next batch (8-byte aligned) or neither; planes need the batch assembly");
-    IDL_REQUIRE(parts >= 1 && part >= 0 && part <= part_end && part_end <= parts, "mid_bwd_gather: need 0 <= part <= part_end <= parts");
     IDL_REQUIRE(g_parts >= 1 && g_parts <= 16, "mid_bwd: g_parts outside 1..16");
     IDL_REQUIRE(z && r2 && f && inv && G && dP0 && W3 && W2 && act1 && dlogits && dlat && (dr1 || dr1h) && partial1 && partial2 && partial3, "NULL buffer");
     IDL_REQUIRE(m >= 2 && (m % 2) == 0 && C >= 1 && C <= 64 * MAX_CPL, "mid_bwd: even m, n_clusters in 1..256");
@@ -1832,32 +1669,24 @@ static int mid_bwd_gather_impl(const float *z, const float *r2, const float *f, 
     a.dlogits = dlogits; a.dlat = dlat; a.dr1 = dr1; a.partial1 = partial1; a.partial2 = partial2; a.partial3 = partial3;
     a.dW3_part = dW3_partial; a.ctl = nullptr; a.batch_advance = 0;
     a.g_parts = g_parts; a.m = m; a.C = C; a.train = train; a.nce_coef = nce_coef; a.act1_t = act1_transposed ? 1 : 0;
-    idl_dev::GatherArgs g{};
-    int64_t t0 = 0, t1 = 0;
-    if (feats != nullptr) {                  // (feats == NULL: no batch assembly in this launch)
-        IDL_REQUIRE(pair_idx && mean && scale && (y || yh) && n >= 1 && fdim >= 4 && (fdim & 3) == 0 && batch >= 1 && n_pairs >= 0,
-                    "mid_bwd_gather: bad gather arguments (4 | f)");
-        g = idl_dev::GatherArgs{feats, n, fdim, view_stride, pair_idx, base, batch, n_pairs, mean, scale, inv_scale, y, base_add, yh, yl, over};
-        const int64_t ng = idl_dev::gather_tiles<MID_GATHER_ROWS>(fdim, batch);
-        t0 = ng * part / parts; t1 = ng * part_end / parts;
-    }
+    Riders rd;
+    if (const int rc = riders_of("mid_bwd_gather", feats, n, fdim, view_stride, pair_idx, base, base_add, n_pairs, batch, mean, scale, inv_scale, y, yh, yl, over,
+                                 part, part_end, parts, rd)) return rc;
+    const unsigned grid = (unsigned)COL_PARTS + rd.wgs();
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin)
         IDL_REQUIRE(C <= 48 || (dr1h != nullptr && dzs != nullptr),
                     "mid_bwd_gather: beyond 48 classes only the form with dr1 as planes and z dP0 given can be recorded");
         idl::PlanHead h{};
         if (C > 48) { h.variant = 1; h.lds = (unsigned)(C * H2 * (int)sizeof(float)); }      // (the BIG body: W3 in dynamic LDS)
-        h.kind = idl::PLAN_MID_BWD; h.grid[0] = (unsigned)(COL_PARTS + (t1 - t0 + 3) / 4); h.grid[1] = 1; h.grid[2] = 1; h.block = 64 * MID_WAVES;
+        h.kind = idl::PLAN_MID_BWD; h.grid[0] = grid; h.grid[1] = 1; h.grid[2] = 1; h.block = 64 * MID_WAVES;
         memcpy(plan, &h, sizeof(h));
-        const MidBwdParams p{a, (int)t0, (int)t1, g};
+        const MidBwdParams p{a, rd.t0, rd.t1, rd.g};
         memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
         return IDL_OK;
     }
-    if (C > 48) return dr1h != nullptr ? launch_mid_bwd_big<true>(a, (unsigned)(COL_PARTS + (t1 - t0 + 3) / 4), (int)t0, (int)t1, g, stream)
-                                       : launch_mid_bwd_big<false>(a, (unsigned)(COL_PARTS + (t1 - t0 + 3) / 4), (int)t0, (int)t1, g, stream);
-    if (dr1h != nullptr) hipLaunchKernelGGL((mid_bwd_kernel<false, true>), dim3((unsigned)(COL_PARTS + (t1 - t0 + 3) / 4)), dim3(64 * MID_WAVES), 0, (hipStream_t)stream,
-                                            a, (int)t0, (int)t1, g);
-    else if (C <= 48) hipLaunchKernelGGL((mid_bwd_kernel<false, false>), dim3((unsigned)(COL_PARTS + (t1 - t0 + 3) / 4)), dim3(64 * MID_WAVES), 0, (hipStream_t)stream, a, (int)t0,
-                                    (int)t1, g);
+    if (C > 48) return dr1h != nullptr ? launch_mid_bwd_big<true>(a, grid, rd.t0, rd.t1, rd.g, stream) : launch_mid_bwd_big<false>(a, grid, rd.t0, rd.t1, rd.g, stream);
+    if (dr1h != nullptr) hipLaunchKernelGGL((mid_bwd_kernel<false, true>), dim3(grid), dim3(64 * MID_WAVES), 0, (hipStream_t)stream, a, rd.t0, rd.t1, rd.g);
+    else hipLaunchKernelGGL((mid_bwd_kernel<false, false>), dim3(grid), dim3(64 * MID_WAVES), 0, (hipStream_t)stream, a, rd.t0, rd.t1, rd.g);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }
@@ -2033,7 +1862,7 @@ static int rmsprop_launch(int count, float *const *params, const float *const *g
     }
     if (red != nullptr) {                   // ... beside the workgroups that add up the two-plane layer-1 tiles' partial sums (reduce_rms_kernel)
         IDL_REQUIRE(big == nullptr && l1 == nullptr && extra == 0 && idl::take_plan() == nullptr, "reduce_parts_rms: no tiles, no batch assembly, not recordable");
-        hipLaunchKernelGGL(reduce_rms_kernel<0>, dim3((unsigned)(red->blocks + nb_total + a.wg_tiles)), dim3(256), 0, (hipStream_t)stream, *red, a, hyper, ctl,
+        hipLaunchKernelGGL(reduce_rms_kernel, dim3((unsigned)(red->blocks + nb_total + a.wg_tiles)), dim3(256), 0, (hipStream_t)stream, *red, a, hyper, ctl,
                            batch_advance, 1);
         IDL_HIP_TRY(hipGetLastError());
         return IDL_OK;
@@ -2195,7 +2024,7 @@ int idl_reduce_parts_rms(float *part, int64_t slab_elems, const int64_t *step_co
             memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &r, sizeof(r));
             return IDL_OK;
         }
-        hipLaunchKernelGGL(reduce_rms_kernel<0>, dim3((unsigned)r.blocks), dim3(256), 0, (hipStream_t)stream, r, RmsArgs{}, (const float *)nullptr, (int64_t *)nullptr,
+        hipLaunchKernelGGL(reduce_rms_kernel, dim3((unsigned)r.blocks), dim3(256), 0, (hipStream_t)stream, r, RmsArgs{}, (const float *)nullptr, (int64_t *)nullptr,
                            (int64_t)0, 0);
         IDL_HIP_TRY(hipGetLastError());
         return IDL_OK;
@@ -2205,8 +2034,8 @@ int idl_reduce_parts_rms(float *part, int64_t slab_elems, const int64_t *step_co
                           stream, wg_index, wg_dy, wg_x, wg_m, wg_n_out, wg_n_in, wg_grad, wg_x_transposed, nullptr, -1, nullptr, w1_index, &r);
 }
 
-// The sums and the forward middle of the two-plane step in one launch (sums_fwd_body): part[8][m][512] from idl_l1_planes_rows, rows_per_wg = 4 or 8.
-int idl_reduce_mid_fwd_gather_planes(const float *part, const int64_t *step_counter, int64_t *step_snapshot, int rows_per_wg, float *r1_transposed,
+// The sums and the forward middle of the two-plane step in one launch (sums_fwd_kernel): part[8][m][512] from idl_l1_planes_rows.
+int idl_reduce_mid_fwd_gather_planes(const float *part, const int64_t *step_counter, int64_t *step_snapshot, float *r1_transposed,
                                      const float *b1, const float *W2, const float *b2, const float *W3, const float *b3, int m,
                                      int C, int train, uint64_t seed, float *f, float *inv, float *r2, float *z,
                                      const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
@@ -2215,31 +2044,16 @@ int idl_reduce_mid_fwd_gather_planes(const float *part, const int64_t *step_coun
                                      void *stream)
 {
     IDL_REQUIRE(part && step_counter && r1_transposed && b1 && W2 && b2 && W3 && b3 && f && inv && r2 && z, "reduce_mid_fwd: NULL buffer");
-    IDL_REQUIRE(rows_per_wg == 4 || rows_per_wg == 8, "reduce_mid_fwd: 4 or 8 rows a workgroup");
     IDL_REQUIRE(m >= 16 && (m % 16) == 0 && C >= 1 && C <= 64 * MAX_CPL && (int64_t)m * H1 < (1ll << 31), "reduce_mid_fwd: m must be a multiple of 16, n_clusters in 1..256");
     IDL_REQUIRE((((uintptr_t)part | (uintptr_t)b1 | (uintptr_t)W2 | (uintptr_t)W3) & 15u) == 0 && (((uintptr_t)r1_transposed) & 3u) == 0,
                 "reduce_mid_fwd: part / b1 / W2 / W3 must be 16-byte aligned");
-    IDL_REQUIRE(parts >= 1 && part_begin >= 0 && part_begin <= part_end && part_end <= parts, "reduce_mid_fwd: need 0 <= part_begin <= part_end <= parts");
-    IDL_REQUIRE((y_hi != nullptr) == (y_lo != nullptr) && (y_hi == nullptr || (feats != nullptr && ((((uintptr_t)y_hi) | ((uintptr_t)y_lo)) & 7u) == 0)),
-                "reduce_mid_fwd: both planes of the next batch (8-byte aligned) or neither; planes need the batch assembly");
     IDL_REQUIRE(idl::take_plan() == nullptr, "reduce_mid_fwd: the lone voter's launch, not recordable");
-    idl_dev::GatherArgs g{};
-    int64_t t0 = 0, t1 = 0;
-    if (feats != nullptr) {                  // (feats == NULL: no batch assembly in this launch)
-        IDL_REQUIRE(pair_idx && mean && scale && (y || y_hi) && n >= 1 && fdim >= 4 && (fdim & 3) == 0 && batch >= 1 && n_pairs >= 0,
-                    "reduce_mid_fwd: bad gather arguments (4 | f)");
-        g = idl_dev::GatherArgs{feats, n, fdim, view_stride, pair_idx, base, batch, n_pairs, mean, scale, inv_scale, y, base_add, (uint16_t *)y_hi, (uint16_t *)y_lo,
-                                overflow_flag};
-        const int64_t ng = idl_dev::gather_tiles<MID_GATHER_ROWS>(fdim, batch);
-        t0 = ng * part_begin / parts; t1 = ng * part_end / parts;
-    }
-    const ReduceArgs r{(float4 *)const_cast<float *>(part), (int64_t)m * H1 / 4, l1p_dev::KSPLIT, m / rows_per_wg, step_counter, step_snapshot};
-    const SumsFwdArgs p{b1, W2, b2, W3, b3, r1_transposed, m, C, train, seed, f, inv, r2, z, (int)t0, (int)t1, g};
-    const dim3 grid((unsigned)(r.blocks + (t1 - t0 + 3) / 4));
-    if (rows_per_wg == 4) hipLaunchKernelGGL(reduce_rms_kernel<4>, grid, dim3(64 * MID_WAVES), sums_fwd_lds<4>(), (hipStream_t)stream, r, p, (const float *)nullptr,
-                                             (int64_t *)nullptr, (int64_t)0, 0);
-    else hipLaunchKernelGGL(reduce_rms_kernel<8>, grid, dim3(64 * MID_WAVES), sums_fwd_lds<8>(), (hipStream_t)stream, r, p, (const float *)nullptr,
-                            (int64_t *)nullptr, (int64_t)0, 0);
+    Riders rd;
+    if (const int rc = riders_of("reduce_mid_fwd", feats, n, fdim, view_stride, pair_idx, base, base_add, n_pairs, batch, mean, scale, inv_scale, y,
+                                 (uint16_t *)y_hi, (uint16_t *)y_lo, overflow_flag, part_begin, part_end, parts, rd)) return rc;
+    const ReduceArgs r{(float4 *)const_cast<float *>(part), (int64_t)m * H1 / 4, l1p_dev::KSPLIT, m / SUMS_FWD_ROWS, step_counter, step_snapshot};
+    const SumsFwdArgs p{b1, W2, b2, W3, b3, r1_transposed, m, C, train, seed, f, inv, r2, z, rd.t0, rd.t1, rd.g};
+    hipLaunchKernelGGL(sums_fwd_kernel, dim3((unsigned)r.blocks + rd.wgs()), dim3(64 * MID_WAVES), SUMS_FWD_LDS, (hipStream_t)stream, r, p);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }

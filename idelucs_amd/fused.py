@@ -59,7 +59,6 @@ VARIANTS = {
     "planes_wgrad": "1",     # 0: dW1 on the fp32 tiles (writing W1's planes) beside the two-plane layer 1
     "planes_tail": "wgrad",  # reduce: the optimizer tail beside the next step's partial sums instead of on the dW1 tiles' loader waves
     "sums_fwd": "1",         # 0: the lone step's forward middle as a launch of its own behind the partial sums (seven launches a step instead of six)
-    "sums_fwd_rows": "8",    # 4: the merged launch's workgroups own 4 whole rows of the batch instead of 8 (measured slower: DESIGN 4.4)
     "fused": "1",            # 0: models.IID_model trains NetLinear + RMSprop through torch autograd instead of the fused explicit step
 }
 VARIANTS.update({k: v for k, v in _lib.DEV.items() if k in VARIANTS})
@@ -423,7 +422,7 @@ class FusedLinearTrainer(_LinearStepParts):
         # next step's partial sums instead, 9.4 us for that launch against 4.7)
         self._planes_tail_wgrad = _v("planes_tail") != "reduce"
         # ... and the forward middle inside the launch that adds the partial sums (lone voter, tail on the dW1 tiles: _step_planes)
-        self._sums_fwd = int(_v("sums_fwd_rows")) if _v("sums_fwd") == "1" else 0
+        self._sums_fwd = _v("sums_fwd") == "1"
         self._cus = torch.cuda.get_device_properties(self.dev).multi_processor_count if self.dev.type == "cuda" else 0
         self._ctl_snap = torch.zeros(1, dtype=torch.int64, device=self.dev)       # the step counter as the step's reduce launch saw it (idl_wgrad_xplanes_rms)
         self._w1_planes = None                   # (W1 hi, W1 lo, overflow flag)
@@ -590,7 +589,7 @@ class FusedLinearTrainer(_LinearStepParts):
         if merged:          # part[8][m][512] -> sums, ReLU / Dropout (r1), lat, head, softmax by workgroups of whole rows; the riders as in mid_fwd
             if cold:
                 self._evict()
-            _launch(_L.idl_reduce_mid_fwd_gather_planes, _p(part), _p(self.ctl), _p(self._ctl_snap), self._sums_fwd, _p(r1), _p(self.b1),
+            _launch(_L.idl_reduce_mid_fwd_gather_planes, _p(part), _p(self.ctl), _p(self._ctl_snap), _p(r1), _p(self.b1),
                     *self._mid_fwd_args(bf, tr)[:8], *self._mid_fwd_args(bf, tr)[9:], *self._next_batch(st, m), *nxt, 0, GATHER_SPLIT, 8, _stream())
         else:
             if self._pending is not None and not rec:       # (a recording looks at no pending tail: a lockstep voter never leaves one)

@@ -1,5 +1,5 @@
-"""The forward middle inside the launch that adds layer 1's K-slice partial sums (csrc/train_step.hip: sums_fwd_body, the ROWS = 4 / 8 instances of
-reduce_rms_kernel; fused.VARIANTS['sums_fwd']): six launches a step instead of seven, every result bit for bit what the two launches leave.
+"""The forward middle inside the launch that adds layer 1's K-slice partial sums (csrc/train_step.hip: sums_fwd_kernel; fused.VARIANTS['sums_fwd']): six
+launches a step instead of seven, every result bit for bit what the two launches leave.
 Reference: the step of idelucs/models.py:117-133 through Linear(F,512) .. Softmax of idelucs/PytorchUtils.py:38-50.
 
 Shapes: the smallest the plane kernels take -- F = 1024, H = 512, m = 128 (one tile of the batch) and 384 (three: not a power of two), 2 / 20 / 48 output
@@ -80,8 +80,8 @@ def _small_store(dev, n, F, seed, views=2):
 @pytest.mark.parametrize("C", [2, 20, 48])
 def test_merged_launch_leaves_what_the_two_launches_leave(dev, m, C):
     """On the same partial sums: idl_reduce_mid_fwd_gather_planes' r1, f, inv, r2, z (and the next batch's planes its riders assemble, and the step counter's
-    copy) against idl_reduce_parts_rms + idl_mid_fwd_gather_planes -- dropout on and off, riders on and off, 4 and 8 rows a workgroup; bit for bit.  The
-    partial sums are only read."""
+    copy) against idl_reduce_parts_rms + idl_mid_fwd_gather_planes -- dropout on and off, riders on and off; bit for bit.  With dropout on, r1 is also what
+    the unfused idl_relu_dropout_fwd (layer id 1) leaves on the summed, biased activations.  The partial sums are only read."""
     import torch
     from idelucs_amd import _lib
     from idelucs_amd.fused import _NO_TAIL
@@ -123,31 +123,37 @@ def test_merged_launch_leaves_what_the_two_launches_leave(dev, m, C):
             torch.cuda.synchronize()
             want = (part[0].clone(), f, inv, r2, z, xh, xl, snap)
             assert all(torch.isfinite(t).all() for t in want[:5])
-            for rows in (4, 8):
-                src = rows0.clone()
-                r1T = torch.full((H1, m), float("nan"), device=dev)
-                snap_n = torch.zeros(1, dtype=torch.int64, device=dev)
-                f_n, inv_n, r2_n, z_n = outs()
-                xh_n = torch.zeros((m, F), dtype=torch.int16, device=dev); xl_n = torch.zeros_like(xh_n)
-                _lib.check(L.idl_reduce_mid_fwd_gather_planes(_p(src), _p(ctl), _p(snap_n), rows, _p(r1T), _p(b1), _p(W2), _p(b2), _p(W3), _p(b3), m, C, train,
-                                                              seed, _p(f_n), _p(inv_n), _p(r2_n), _p(z_n), *gather_args(riders, xh_n, xl_n, flag), _stream()))
+            src = rows0.clone()
+            r1T = torch.full((H1, m), float("nan"), device=dev)
+            snap_n = torch.zeros(1, dtype=torch.int64, device=dev)
+            f_n, inv_n, r2_n, z_n = outs()
+            xh_n = torch.zeros((m, F), dtype=torch.int16, device=dev); xl_n = torch.zeros_like(xh_n)
+            _lib.check(L.idl_reduce_mid_fwd_gather_planes(_p(src), _p(ctl), _p(snap_n), _p(r1T), _p(b1), _p(W2), _p(b2), _p(W3), _p(b3), m, C, train,
+                                                          seed, _p(f_n), _p(inv_n), _p(r2_n), _p(z_n), *gather_args(riders, xh_n, xl_n, flag), _stream()))
+            torch.cuda.synchronize()
+            got = (r1T, f_n, inv_n, r2_n, z_n, xh_n, xl_n, snap_n)
+            for name, a_, b_ in zip(("r1", "f", "inv", "r2", "z", "x_hi", "x_lo", "step snapshot"), got, want):
+                assert torch.equal(a_, b_), (name, train, riders, (a_.double() - b_.double()).abs().max().item())
+            assert torch.equal(src, rows0)
+            assert snap_n.item() == ctl[0].item() and flag.item() == 0
+            if train:
+                assert (r1T == 0).float().mean().item() > 0.5 and (r1T > 0).any()
+                # ... and the unfused kernel's: the sums in ascending slab order, the bias, then idl_relu_dropout_fwd on the flat [m][512] array
+                acc = rows0[0].clone()
+                for p_ in range(1, parts):
+                    acc += rows0[p_]
+                acc += b1
+                _lib.check(L.idl_relu_dropout_fwd(_p(acc), acc.numel(), 1, seed, _p(ctl), 1, _stream()))
                 torch.cuda.synchronize()
-                got = (r1T, f_n, inv_n, r2_n, z_n, xh_n, xl_n, snap_n)
-                for name, a_, b_ in zip(("r1", "f", "inv", "r2", "z", "x_hi", "x_lo", "step snapshot"), got, want):
-                    assert torch.equal(a_, b_), (name, train, riders, rows, (a_.double() - b_.double()).abs().max().item())
-                assert torch.equal(src, rows0)
-                assert snap_n.item() == ctl[0].item() and flag.item() == 0
-                if train:
-                    assert (r1T == 0).float().mean().item() > 0.5 and (r1T > 0).any()
-                if riders:
-                    assert xh_n.ne(0).any()
+                assert torch.equal(r1T, acc.t()), (train, riders, (r1T.double() - acc.t().double()).abs().max().item())
+            if riders:
+                assert xh_n.ne(0).any()
 
 
-def _run_twenty(dev, store, net0, B, sums_fwd, rows, graph, cold, monkeypatch):
+def _run_twenty(dev, store, net0, B, sums_fwd, graph, cold, monkeypatch):
     import torch
     from idelucs_amd import fused
     monkeypatch.setitem(fused.VARIANTS, "sums_fwd", sums_fwd)
-    monkeypatch.setitem(fused.VARIANTS, "sums_fwd_rows", rows)
     monkeypatch.setitem(fused.VARIANTS, "test_cold", "1" if cold else "0")
     tr = fused.FusedLinearTrainer(copy.deepcopy(net0), lr=1e-3, weight=0.25, lamb=2.8, seed=11)
     tr.begin_voter(1)
@@ -163,7 +169,7 @@ def _run_twenty(dev, store, net0, B, sums_fwd, rows, graph, cold, monkeypatch):
 
 @pytest.mark.parametrize("F,m,C", [(1024, 128, 20), (1024, 384, 2), (2560, 384, 2), (2560, 384, 20), (2560, 384, 48)])
 def test_twenty_steps_are_the_seven_launch_steps(dev, monkeypatch, F, m, C):
-    """Twenty steps (an epoch of twenty full batches) from one state with sums_fwd = 0 and 1 (4 and 8 rows a workgroup), eager and graph-replayed, with warm
+    """Twenty steps (an epoch of twenty full batches) from one state with sums_fwd = 0 and 1, eager and graph-replayed, with warm
     caches and under test_cold = 1: every parameter, running average, the loss sums and the counters are equal bit for bit."""
     import torch
     from idelucs_amd import models
@@ -174,15 +180,15 @@ def test_twenty_steps_are_the_seven_launch_steps(dev, monkeypatch, F, m, C):
     assert store.n_pairs == 20 * B
     torch.manual_seed(C)
     net0 = NetLinear(F, C).to(dev); net0.apply(models.weights_init)
-    want, merged = _run_twenty(dev, store, net0, B, "0", "4", False, False, monkeypatch)
+    want, merged = _run_twenty(dev, store, net0, B, "0", False, False, monkeypatch)
     assert not merged
     assert all(torch.isfinite(t).all() for t in want[:13])
-    for sums_fwd, rows in (("0", "4"), ("1", "4"), ("1", "8")):
+    for sums_fwd in ("0", "1"):
         for graph in (False, True):
             for cold in (False, True):
                 if (sums_fwd, graph, cold) == ("0", False, False):
                     continue
-                got, merged = _run_twenty(dev, store, net0, B, sums_fwd, rows, graph, cold, monkeypatch)
+                got, merged = _run_twenty(dev, store, net0, B, sums_fwd, graph, cold, monkeypatch)
                 assert merged == (sums_fwd == "1" and F >= 2304 and m >= 192), (sums_fwd, F, m, merged)
                 for i, (a_, b_) in enumerate(zip(got, want)):
-                    assert torch.equal(a_, b_), (i, sums_fwd, rows, graph, cold)
+                    assert torch.equal(a_, b_), (i, sums_fwd, graph, cold)

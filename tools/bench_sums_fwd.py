@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """Times an epoch of the lone voter's two-plane step (NetLinear(4096, 20) + RMSprop, cfg2's shape) with the forward middle as a launch of its own
-(fused.VARIANTS['sums_fwd'] = 0: seven launches a step, the parent's sequence) and inside the launch that adds layer 1's partial sums (sums_fwd = 1 with 4 and
-with 8 rows a workgroup: six launches), on the same GPU, in the same process, alternating the legs.
+(fused.VARIANTS['sums_fwd'] = 0: seven launches a step) and inside the launch that adds layer 1's partial sums (sums_fwd = 1, 8 rows a workgroup: six
+launches), on the same GPU, in the same process, alternating the legs.
 
 Input: a seeded synthetic feature store of 100 000 rows x 4 views x 4096 features, batch 512 (m = 1024 rows a step; 585 full batches + a partial one an epoch:
-586 steps a leg).  Prints one JSON line: every round, the median ms of an epoch and the spread (max - min) of each leg, us per step, and for each merged leg
+586 steps a leg).  Prints one JSON line: every round, the median ms of an epoch and the spread (max - min) of each leg, us per step, and for the merged leg
 whether it clears the rule for the default -- its median below the seven-launch median by more than three times the larger of the two spreads.
 
 Usage:  python tools/bench_sums_fwd.py [--rounds R]
-        python tools/bench_sums_fwd.py --only 0        (one leg alone: "0", "4" or "8"; "0" also runs on a tree without the merged launch)
+        python tools/bench_sums_fwd.py --only 0        (one leg alone: "0" or "8"; "0" also runs on a tree without the merged launch)
 """
 import argparse
 import copy
@@ -41,7 +41,7 @@ def main():
     torch.manual_seed(0)
     net0 = NetLinear(F, C).to(dev)
     net0.apply(models.weights_init)
-    legs = [a.only] if a.only else ["0", "4", "8"]
+    legs = [a.only] if a.only else ["0", "8"]
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -55,7 +55,7 @@ def main():
     epochs = {}
     for leg in legs:
         if "sums_fwd" in fused.VARIANTS:
-            fused.VARIANTS["sums_fwd"], fused.VARIANTS["sums_fwd_rows"] = ("0", "4") if leg == "0" else ("1", leg)
+            fused.VARIANTS["sums_fwd"] = "0" if leg == "0" else "1"
         elif leg != "0":
             raise SystemExit("this tree has no merged launch: --only 0")
         tr = fused.FusedLinearTrainer(copy.deepcopy(net0), 1e-3, 0.25, 2.8, seed=0)
@@ -68,7 +68,7 @@ def main():
         epoch()                                             # warm-up: allocations, the captured graph
         torch.cuda.synchronize()
         assert tr._form(tr.buffers(2 * B), st) == "planes" and not tr.planes_overflowed()
-        assert getattr(tr, "_sums_fwd", 0) == (0 if leg == "0" else int(leg))
+        assert bool(getattr(tr, "_sums_fwd", False)) == (leg != "0")
         epochs[leg] = epoch
     t = {leg: [] for leg in legs}
     for _ in range(a.rounds):                               # alternating, same box, same process
