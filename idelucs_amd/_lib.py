@@ -23,6 +23,25 @@ _c = ctypes
 _vp, _i64, _i32, _int = _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int
 _pi64, _pu8 = _c.POINTER(_c.c_int64), _c.POINTER(_c.c_uint8)
 
+
+class idl_next_batch_t(_c.Structure):
+    """The next batch's assembly by spare workgroups of a launch (include/idelucs_hip.h); where an entry point takes one, None = no assembly."""
+    _fields_ = [("feats", _vp), ("n", _i64), ("f", _i64), ("view_stride", _i64), ("pair_idx", _vp), ("base", _vp), ("base_add", _i64),
+                ("n_pairs", _i64), ("batch", _i64), ("mean", _vp), ("scale", _vp), ("inv_scale", _vp), ("y", _vp), ("y_hi", _vp), ("y_lo", _vp),
+                ("overflow_flag", _vp), ("part", _int), ("part_end", _int), ("parts", _int)]
+
+
+class idl_opt_tail_t(_c.Structure):
+    """The RMSprop tail of a step (include/idelucs_hip.h): skip_index / wg_index = -1 for no tensor updated elsewhere / no in-launch dW2 tiles."""
+    _fields_ = [("count", _int), ("params", _c.POINTER(_vp)), ("grads", _c.POINTER(_vp)), ("grad_parts", _c.POINTER(_i32)), ("square_avg", _c.POINTER(_vp)),
+                ("sizes", _pi64), ("hyper", _vp),
+                ("ctl", _vp), ("loss_rows", _vp), ("loss_m", _int), ("w_nce", _c.c_float), ("w_iic", _c.c_float), ("out", _vp),
+                ("skip_index", _int), ("wg_index", _int), ("wg_dy", _vp), ("wg_x", _vp), ("wg_x_transposed", _int), ("wg_m", _int),
+                ("wg_n_out", _int), ("wg_n_in", _int), ("wg_grad", _vp), ("batch_advance", _i64)]
+
+
+_nb, _tail = _c.POINTER(idl_next_batch_t), _c.POINTER(idl_opt_tail_t)
+
 # name -> (restype, argtypes); kept in one table so tests can check every symbol the header declares
 SIGNATURES = {
     "idl_last_error": (_c.c_char_p, []),
@@ -85,49 +104,30 @@ SIGNATURES = {
     "idl_col_sum_parts": (_int, []),
     "idl_mid_bwd": (_int, [_vp] * 5 + [_int] + [_vp] * 4 + [_int, _int, _int, _c.c_float] + [_vp] * 8 + [_i64, _vp]),
     "idl_bias_grads": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _int, _vp, _int, _int, _vp, _i64, _vp, _vp, _vp]),
-    "idl_rmsprop_step_gather": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp,
-                                       _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "idl_wgrad_supported": (_int, [_int, _int, _int]),
     "idl_wgrad_rmsprop": (_int, [_vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "idl_l1_fwd_supported": (_int, [_int, _int, _int]),
     "idl_l1_fwd": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
     "idl_debug_wgrad_clock": (_int, [_vp, _vp, _int, _int, _int, _vp, _int, _vp, _vp]),
-    "idl_rmsprop_step_gather_wgrad": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp,
-                                             _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
-                                             _int, _vp, _vp, _int, _int, _int, _int, _vp, _i64, _vp]),
-    "idl_wgrad_rmsprop_step": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp,
-                                      _int, _vp, _vp, _int, _int, _int, _vp,
-                                      _int, _vp, _vp, _int, _int, _int, _int, _vp, _i64, _vp]),
-    "idl_l1_fwd_rms": (_int, [_vp, _vp, _int, _int, _vp,
-                              _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp, _int,
-                              _int, _vp, _vp, _int, _int, _int, _int, _vp, _i64, _vp]),
+    "idl_wgrad_rmsprop_step": (_int, [_vp, _vp, _int, _int, _int, _vp, _tail, _vp]),
+    "idl_l1_fwd_rms": (_int, [_vp, _vp, _int, _int, _vp, _tail, _vp]),
     "idl_mid_bwd_gather": (_int, [_vp] * 5 + [_int] + [_vp] * 4 + [_int, _int, _int, _c.c_float] + [_vp] * 7 +
-                           [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
-    "idl_mid_fwd_gather": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp, _vp] +
-                           [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
+                           [_int, _vp, _vp, _vp, _vp, _vp, _nb, _vp]),
+    "idl_mid_fwd_gather": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _nb, _vp]),
     "idl_planes_exponent": (_int, [_int]),
     "idl_split_planes": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "idl_l1_planes_parts": (_int, []),
     "idl_l1_planes_supported": (_int, [_int, _int, _int]),
     "idl_l1_planes": (_int, [_vp, _vp, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
     "idl_l1_planes_rows": (_int, [_vp, _vp, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
-    "idl_reduce_mid_fwd_gather_planes": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp] +
-                                         [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
-    "idl_reduce_parts_rms": (_int, [_vp, _i64, _vp, _vp,
-                                    _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp, _int,
-                                    _int, _vp, _vp, _int, _int, _int, _int, _vp, _i64, _vp]),
+    "idl_reduce_mid_fwd_gather_planes": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp,
+                                                _nb, _vp]),
+    "idl_reduce_parts_rms": (_int, [_vp, _i64, _vp, _vp, _tail, _vp]),
     "idl_wgrad_xplanes_supported": (_int, [_int, _int, _int]),
     "idl_wgrad_rmsprop_xplanes": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "idl_wgrad_xplanes_rms": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp,
-                                     _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp, _int,
-                                     _int, _vp, _vp, _int, _int, _int, _int, _vp, _i64, _vp]),
+    "idl_wgrad_xplanes_rms": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _tail, _vp]),
     "idl_wgrad_rmsprop_planes": (_int, [_vp, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "idl_mid_bwd_gather_planes": (_int, [_vp] * 5 + [_int] + [_vp] * 4 + [_int, _int, _int, _c.c_float] + [_vp] * 7 +
-                                  [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int,
-                                   _vp, _vp, _vp, _vp, _vp]),
     "idl_dr1_scale_words": (_int, []),
-    "idl_mid_fwd_gather_planes": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp, _vp] +
-                                  [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp]),
     "idl_mst_prim_workspace": (_i64, [_i64]),
     "idl_mst_prim": (_int, [_vp, _int, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "idl_mst_prim_local": (_int, [_vp, _int, _vp, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -159,7 +159,7 @@ SIGNATURES = {
     "idl_plan_begin": (_int, [_vp]),
     "idl_plan_end": (_int, []),
     "idl_plan_launch": (_int, [_vp, _vp, _int, _vp]),
-    "idl_rmsprop_step": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _int, _c.c_float, _c.c_float, _vp, _vp]),
+    "idl_rmsprop_step": (_int, [_tail, _nb, _vp]),
     "idl_small_l1_fwd": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
     "idl_small_mid_fwd": (_int, [_vp] * 8 + [_int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "idl_small_mid_bwd": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_float, _c.c_uint64,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "../../include/idelucs_hip.h"
 
@@ -35,6 +36,17 @@ struct PlanHead {
     uint32_t grid2[3];                 // second launch of the record (InfoNCE pass 2, idl_iic_core_dz's z dP0 tiles)
 };
 static_assert(sizeof(PlanHead) <= PLAN_PARAMS, "plan header does not fit");
+// Fill a plan record: the head (the shape of one voter's launch; grid2: the record's second launch, if it has one) and behind it the kernel's parameter struct.
+template <class P>
+inline void fill_plan(void *plan, int kind, int variant, dim3 grid, unsigned block, unsigned lds, const P &params, dim3 grid2 = dim3(0, 0, 0))
+{
+    static_assert(sizeof(P) + PLAN_PARAMS <= PLAN_BYTES, "the parameter struct does not fit a plan record");
+    PlanHead h{};
+    h.kind = kind; h.variant = variant; h.grid[0] = grid.x; h.grid[1] = grid.y; h.grid[2] = grid.z; h.block = block; h.lds = lds;
+    h.grid2[0] = grid2.x; h.grid2[1] = grid2.y; h.grid2[2] = grid2.z;
+    memcpy(plan, &h, sizeof(h));
+    memcpy((unsigned char *)plan + PLAN_PARAMS, &params, sizeof(params));
+}
 // the record the next supporting launcher on this thread fills instead of launching (and clears); NULL = launch normally
 void *take_plan();
 // the batched launches of the other translation units
@@ -60,3 +72,21 @@ int at_b_plan_launch(const PlanHead &h, const void *dev_plans, int n_voters, hip
             return IDL_ERR_ARG;                    \
         }                                          \
     } while (0)
+
+namespace idl {
+
+// Raise kernel K's dynamic-LDS limit to `bytes`, once per device (the flags are K's own: one instance of this function per kernel).
+template <auto K>
+inline int raise_dyn_lds(int bytes)
+{
+    static bool attr_set[64] = {};
+    int dev = 0;
+    IDL_HIP_TRY(hipGetDevice(&dev));
+    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
+        IDL_HIP_TRY(hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        attr_set[dev] = true;
+    }
+    return IDL_OK;
+}
+
+}  // namespace idl

@@ -35,18 +35,12 @@ __global__ __launch_bounds__(THREADS) void l1_fwd_kernel(L1Args a)
     l1_fwd_body<DBG>(a, (int)blockIdx.x, l1_smem);
 }
 
-static int raise_lds_limit()
+template <int DBG>
+static int launch_l1_fwd(const L1Args &a, void *stream)
 {
-    static bool attr_set[64] = {};
-    int dev = 0;
-    IDL_HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)l1_fwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)l1_fwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)l1_fwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)l1_fwd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_set[dev] = true;
-    }
+    if (const int rc = idl::raise_dyn_lds<l1_fwd_kernel<DBG>>(LDS_BYTES)) return rc;
+    hipLaunchKernelGGL(l1_fwd_kernel<DBG>, dim3((unsigned)a.n_tiles), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, a);
+    IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }
 
@@ -65,17 +59,11 @@ int idl_l1_fwd(const float *W1, const float *x, int m, int n_in, float *a1_t, vo
     IDL_REQUIRE(W1 && x && a1_t && idl_l1_fwd_supported(m, H1, n_in), "l1_fwd: Linear(n_in, 512), m % 32 == 0, n_in % 64 == 0, n_in >= 192");
     IDL_REQUIRE((((uintptr_t)W1 | (uintptr_t)x | (uintptr_t)a1_t) & 15u) == 0, "l1_fwd: buffers must be 16-byte aligned");
     IDL_REQUIRE(idl::take_plan() == nullptr, "l1_fwd: not a recordable launch");
-    if (const int rc = raise_lds_limit(); rc != IDL_OK) return rc;
     const int n_tiles = (H1 / TH) * (m / TR);
     const L1Args a{W1, x, a1_t, m, n_in, n_tiles, 0};
-    const dim3 grid((unsigned)n_tiles), block(THREADS);
     static const int dbg = [] { const char *e = idl::dev_env("l1_debug"); return e != nullptr ? atoi(e) : 0; }();
-    if (dbg == 1) hipLaunchKernelGGL((l1_fwd_kernel<1>), grid, block, LDS_BYTES, (hipStream_t)stream, a);
-    else if (dbg == 2) hipLaunchKernelGGL((l1_fwd_kernel<2>), grid, block, LDS_BYTES, (hipStream_t)stream, a);
-    else if (dbg == 3) hipLaunchKernelGGL((l1_fwd_kernel<3>), grid, block, LDS_BYTES, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(l1_fwd_kernel<0>, grid, block, LDS_BYTES, (hipStream_t)stream, a);
-    IDL_HIP_TRY(hipGetLastError());
-    return IDL_OK;
+    if (dbg < 1 || dbg > 3) return launch_l1_fwd<0>(a, stream);
+    return dbg == 1 ? launch_l1_fwd<1>(a, stream) : dbg == 2 ? launch_l1_fwd<2>(a, stream) : launch_l1_fwd<3>(a, stream);      // (diagnostic variants)
 }
 
 }  // extern "C"

@@ -333,11 +333,7 @@ int idl_at_b(const float *A, int lda, const float *B, int ldb, int K, int M, int
     IDL_REQUIRE(A && B && out && K >= 1 && M >= 1 && N >= 1 && lda >= M && ldb >= N && ldo >= N && M <= 65535 * 16 && N <= 65535 * 16, "at_b: NULL buffer or bad shape");
     const dim3 grid((unsigned)((M + 15) / 16), (unsigned)((N + 15) / 16));
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin)
-        idl::PlanHead h{};
-        h.kind = idl::PLAN_AT_B; h.grid[0] = grid.x; h.grid[1] = grid.y; h.grid[2] = 1; h.block = 256;
-        memcpy(plan, &h, sizeof(h));
-        const AtBParams p{A, lda, B, ldb, K, M, N, out, ldo};
-        memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
+        idl::fill_plan(plan, idl::PLAN_AT_B, 0, grid, 256, 0, AtBParams{A, lda, B, ldb, K, M, N, out, ldo});
         return IDL_OK;
     }
     hipLaunchKernelGGL(at_b_kernel, grid, dim3(256), 0, (hipStream_t)stream, A, lda, B, ldb, K, M, N, out, ldo);
@@ -374,13 +370,8 @@ static int nce_launch(const float *f, int m, float temperature, float *lse, floa
     const dim3 grid1((unsigned)(m / 16 + (iic.P0 != nullptr ? (iic.cols > 0 ? iic.cols : 1) : 0)), NCE_SPLIT);
     const bool core2 = iic.z != nullptr && iic.cols == 0;    // the core as the spare workgroup of pass 2 (n_clusters <= 48)
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin): both passes in one record
-        const dim3 g2 = core2 ? grid1 : grid;     // (n_clusters > 48: the joint's tiles ride in pass 1 alone, the core is idl_iic_core_dz's record)
-        idl::PlanHead h{};
-        h.kind = idl::PLAN_NCE; h.grid[0] = grid1.x; h.grid[1] = grid1.y; h.grid[2] = 1; h.block = 256;
-        h.grid2[0] = g2.x; h.grid2[1] = g2.y; h.grid2[2] = 1;
-        memcpy(plan, &h, sizeof(h));
-        const NceParams p{f, m, inv_t, rowsum_part, pos, lse, loss_rows, G_part, iic};
-        memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
+        // (n_clusters > 48: the joint's tiles ride in pass 1 alone, the core is idl_iic_core_dz's record)
+        idl::fill_plan(plan, idl::PLAN_NCE, 0, grid1, 256, 0, NceParams{f, m, inv_t, rowsum_part, pos, lse, loss_rows, G_part, iic}, core2 ? grid1 : grid);
         return IDL_OK;
     }
     hipLaunchKernelGGL(nce_pass1_kernel, grid1, dim3(256), 0, (hipStream_t)stream, f, m, inv_t, rowsum_part, pos, iic);

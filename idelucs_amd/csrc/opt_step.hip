@@ -1,6 +1,6 @@
 // opt_step.hip -- the last launch of a NetLinear training step whose optimizer is SGD with momentum, Adam (reference
 // idelucs/models.py:89-92, stepped at models.py:131-132) or RMSprop with the momentum buffer that CyclicLR's cycle_momentum gives it
-// (models.py:87-88 under models.py:99): idl_opt_step_gather_wgrad, the counterpart of idl_rmsprop_step_gather_wgrad
+// (models.py:87-88 under models.py:99): idl_opt_step_gather_wgrad, the counterpart of idl_rmsprop_step
 // (train_step.hip) with the optimizer generalised.  The forward, the backward and the loss launches in front of it do not know
 // which optimizer follows them; this file is where the two enter the step.
 //

@@ -67,20 +67,10 @@ static int l1_planes_impl(const void *w_hi, const void *w_lo, int ld_w, const vo
     l1p_dev::L1pArgs a{(const uint16_t *)w_hi, (const uint16_t *)w_lo, (const uint16_t *)x_hi, (const uint16_t *)x_lo, part, m, n_out, n_in,
                        (n_out / l1p_dev::TM) * (m / l1p_dev::TN) * l1p_dev::KSPLIT, ld_w, ld_x, l1p_dbg, rows};
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin): several voters in one launch, train_step.hip
-        static_assert(sizeof(l1p_dev::L1pArgs) + idl::PLAN_PARAMS <= idl::PLAN_BYTES, "L1pArgs does not fit a plan record");
-        idl::PlanHead h{};
-        h.kind = idl::PLAN_L1_PLANES; h.grid[0] = (unsigned)a.n_tiles; h.grid[1] = 1; h.grid[2] = 1; h.block = l1p_dev::THREADS; h.lds = l1p_dev::LDS_BYTES;
-        memcpy(plan, &h, sizeof(h));
-        memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &a, sizeof(a));
+        idl::fill_plan(plan, idl::PLAN_L1_PLANES, 0, dim3((unsigned)a.n_tiles), l1p_dev::THREADS, l1p_dev::LDS_BYTES, a);
         return IDL_OK;
     }
-    static bool attr_set[64] = {};
-    int dev = 0;
-    IDL_HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)l1_planes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l1p_dev::LDS_BYTES));
-        attr_set[dev] = true;
-    }
+    if (const int rc = idl::raise_dyn_lds<l1_planes_kernel>(l1p_dev::LDS_BYTES)) return rc;
     hipLaunchKernelGGL(l1_planes_kernel, dim3((unsigned)a.n_tiles), dim3(l1p_dev::THREADS), l1p_dev::LDS_BYTES, (hipStream_t)stream, a);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;

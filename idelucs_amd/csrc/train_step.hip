@@ -1405,13 +1405,7 @@ template <bool DP>
 static int launch_mid_bwd_big(const MidBwdArgs &a, unsigned grid, int t0, int t1, const idl_dev::GatherArgs &g, void *stream)
 {
     const int lds = a.C * H2 * (int)sizeof(float);
-    static bool attr_set[64] = {};
-    int dev = 0;
-    IDL_HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)mid_bwd_kernel<true, DP>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * MAX_CPL * H2 * (int)sizeof(float)));
-        attr_set[dev] = true;
-    }
+    if (const int rc = idl::raise_dyn_lds<mid_bwd_kernel<true, DP>>(64 * MAX_CPL * H2 * (int)sizeof(float))) return rc;
     hipLaunchKernelGGL((mid_bwd_kernel<true, DP>), dim3(grid), dim3(64 * MID_WAVES), lds, (hipStream_t)stream, a, t0, t1, g);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
@@ -1455,33 +1449,33 @@ int idl_mid_fwd(float *a1, const float *W2, const float *b2, const float *W3, co
 }
 
 // The batch-assembly riders of a middle launch (mid_fwd, mid_bwd, the sums launch): their arguments checked; the kernels' GatherArgs and the tiles [t0, t1)
-// -- shares [part, part_end) of `parts` of the next batch -- four to a rider workgroup.  feats == NULL: no riders in this launch.
+// -- shares [part, part_end) of `parts` of the next batch -- four to a rider workgroup.  nb == NULL (or nb->feats == NULL): no riders in this launch.
 struct Riders {
     idl_dev::GatherArgs g{}; int t0 = 0, t1 = 0;
     unsigned wgs() const { return (unsigned)((t1 - t0 + 3) / 4); }
 };
-static int riders_of(const char *who, const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
-                     int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale, const double *inv_scale, float *y,
-                     uint16_t *yh, uint16_t *yl, int *over, int part, int part_end, int parts, Riders &out)
+static int riders_of(const char *who, const idl_next_batch_t *nb, Riders &out)
 {
     const auto bad = [who](const char *what) { idl::set_error("bad argument: %s: %s", who, what); return IDL_ERR_ARG; };      // (IDL_REQUIRE's message, the caller named)
-    if (!(parts >= 1 && part >= 0 && part <= part_end && part_end <= parts)) return bad("need 0 <= part <= part_end <= parts");
-    if (!((yh != nullptr) == (yl != nullptr) && (yh == nullptr || (feats != nullptr && ((((uintptr_t)yh) | ((uintptr_t)yl)) & 7u) == 0))))
-        return bad("both planes of the next batch (8-byte aligned) or neither; planes need the batch assembly");
     out = Riders{};
-    if (feats == nullptr) return IDL_OK;
-    if (!(pair_idx && mean && scale && (y || yh) && n >= 1 && fdim >= 4 && (fdim & 3) == 0 && batch >= 1 && n_pairs >= 0)) return bad("bad gather arguments (4 | f)");
-    out.g = idl_dev::GatherArgs{feats, n, fdim, view_stride, pair_idx, base, batch, n_pairs, mean, scale, inv_scale, y, base_add, yh, yl, over};
-    const int64_t ng = idl_dev::gather_tiles<MID_GATHER_ROWS>(fdim, batch);
-    out.t0 = (int)(ng * part / parts); out.t1 = (int)(ng * part_end / parts);
+    if (nb == nullptr) return IDL_OK;
+    uint16_t *yh = (uint16_t *)nb->y_hi, *yl = (uint16_t *)nb->y_lo;
+    if (!(nb->parts >= 1 && nb->part >= 0 && nb->part <= nb->part_end && nb->part_end <= nb->parts)) return bad("need 0 <= part <= part_end <= parts");
+    if (!((yh != nullptr) == (yl != nullptr) && (yh == nullptr || (nb->feats != nullptr && ((((uintptr_t)yh) | ((uintptr_t)yl)) & 7u) == 0))))
+        return bad("both planes of the next batch (8-byte aligned) or neither; planes need the batch assembly");
+    if (nb->feats == nullptr) return IDL_OK;
+    if (!(nb->pair_idx && nb->mean && nb->scale && (nb->y || yh) && nb->n >= 1 && nb->f >= 4 && (nb->f & 3) == 0 && nb->batch >= 1 && nb->n_pairs >= 0))
+        return bad("bad gather arguments (4 | f)");
+    out.g = idl_dev::GatherArgs{nb->feats, nb->n, nb->f, nb->view_stride, nb->pair_idx, nb->base, nb->batch, nb->n_pairs, nb->mean, nb->scale, nb->inv_scale, nb->y,
+                                nb->base_add, yh, yl, nb->overflow_flag};
+    const int64_t ng = idl_dev::gather_tiles<MID_GATHER_ROWS>(nb->f, nb->batch);
+    out.t0 = (int)(ng * nb->part / nb->parts); out.t1 = (int)(ng * nb->part_end / nb->parts);
     return IDL_OK;
 }
 
-static int mid_fwd_gather_impl(float *a1, const float *b1, int a1_transposed, const float *W2, const float *b2, const float *W3, const float *b3, int m,
+int idl_mid_fwd_gather(float *a1, const float *b1, int a1_transposed, const float *W2, const float *b2, const float *W3, const float *b3, int m,
                        int C, int train, uint64_t seed, const int64_t *ctl, float *f, float *inv, float *r2, float *z,
-                       const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
-                       int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale,
-                       const double *inv_scale, float *y, int part, int part_end, int parts, void *stream, uint16_t *yh, uint16_t *yl, int *over = nullptr)
+                       const idl_next_batch_t *next_batch, void *stream)
 {
     IDL_REQUIRE(a1 && W2 && b2 && W3 && b3 && ctl && f && inv && r2 && z, "NULL buffer");
     IDL_REQUIRE(m >= 16 && (m % 16) == 0 && C >= 1 && C <= 64 * MAX_CPL, "mid_fwd: m must be a multiple of 16, n_clusters in 1..256");
@@ -1489,15 +1483,11 @@ static int mid_fwd_gather_impl(float *a1, const float *b1, int a1_transposed, co
     IDL_REQUIRE(b1 == nullptr || (((uintptr_t)b1) & 15u) == 0, "mid_fwd_gather: b1 must be 16-byte aligned");
     IDL_REQUIRE(a1_transposed == 0 || a1_transposed == 1, "mid_fwd_gather: a1_transposed is 0 or 1");
     Riders rd;
-    if (const int rc = riders_of("mid_fwd_gather", feats, n, fdim, view_stride, pair_idx, base, base_add, n_pairs, batch, mean, scale, inv_scale, y, yh, yl, over,
-                                 part, part_end, parts, rd)) return rc;
+    if (const int rc = riders_of("mid_fwd_gather", next_batch, rd)) return rc;
     const dim3 grid((unsigned)(m / 16) + rd.wgs());
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin)
-        idl::PlanHead h{};
-        h.kind = idl::PLAN_MID_FWD; h.variant = a1_transposed; /* 0 row-major, 1 transposed */ h.grid[0] = grid.x; h.grid[1] = 1; h.grid[2] = 1; h.block = 64 * MID_WAVES;
-        memcpy(plan, &h, sizeof(h));
-        const MidFwdParams p{a1, b1, W2, b2, W3, b3, m, C, train, seed, ctl, f, inv, r2, z, m / 16, rd.t0, rd.t1, rd.g};
-        memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
+        idl::fill_plan(plan, idl::PLAN_MID_FWD, a1_transposed /* 0 row-major, 1 transposed */, grid, 64 * MID_WAVES, 0,
+                       MidFwdParams{a1, b1, W2, b2, W3, b3, m, C, train, seed, ctl, f, inv, r2, z, m / 16, rd.t0, rd.t1, rd.g});
         return IDL_OK;
     }
     if (a1_transposed) hipLaunchKernelGGL(mid_fwd_kernel<true>, grid, dim3(64 * MID_WAVES), 0, (hipStream_t)stream, a1, b1, W2, b2, W3, b3,
@@ -1506,29 +1496,6 @@ static int mid_fwd_gather_impl(float *a1, const float *b1, int a1_transposed, co
                             m, C, train, seed, ctl, f, inv, r2, z, m / 16, rd.t0, rd.t1, rd.g);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
-}
-
-int idl_mid_fwd_gather(float *a1, const float *b1, int a1_transposed, const float *W2, const float *b2, const float *W3, const float *b3, int m,
-                       int C, int train, uint64_t seed, const int64_t *ctl, float *f, float *inv, float *r2, float *z,
-                       const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
-                       int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale,
-                       const double *inv_scale, float *y, int part, int part_end, int parts, void *stream)
-{
-    return mid_fwd_gather_impl(a1, b1, a1_transposed, W2, b2, W3, b3, m, C, train, seed, ctl, f, inv, r2, z, feats, n, fdim, view_stride, pair_idx, base,
-                               base_add, n_pairs, batch, mean, scale, inv_scale, y, part, part_end, parts, stream, nullptr, nullptr);
-}
-
-// ... the same launch with the next batch ALSO written as two fp16 planes (planes.h) by the assembling workgroups
-int idl_mid_fwd_gather_planes(float *a1, const float *b1, int a1_transposed, const float *W2, const float *b2, const float *W3, const float *b3, int m,
-                              int C, int train, uint64_t seed, const int64_t *ctl, float *f, float *inv, float *r2, float *z,
-                              const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
-                              int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale,
-                              const double *inv_scale, float *y, void *y_hi, void *y_lo, int *overflow_flag, int part, int part_end, int parts,
-                              void *stream)
-{
-    return mid_fwd_gather_impl(a1, b1, a1_transposed, W2, b2, W3, b3, m, C, train, seed, ctl, f, inv, r2, z, feats, n, fdim, view_stride, pair_idx, base,
-                               base_add, n_pairs, batch, mean, scale, inv_scale, y, part, part_end, parts, stream, (uint16_t *)y_hi, (uint16_t *)y_lo,
-                               overflow_flag);
 }
 
 int idl_nce_rows(float *S, int m, float temperature, float *lse, float *loss_rows, void *stream)
@@ -1550,13 +1517,7 @@ int idl_iic_core(float *P0, int C, float lamb, float eps, float w_iic, float *sc
     if (C <= 48) hipLaunchKernelGGL(iic_core_kernel<256>, dim3(1), dim3(256), 0, (hipStream_t)stream, P0, C, lamb, eps, w_iic, scratch, out);
     else if (C <= 200) {                     // the joint fits LDS (rows padded to an odd stride: C * (C | 1) * 4 + 1.9 KB <= 160 KB)
         const int lds = C * (C | 1) * 4;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        IDL_HIP_TRY(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)iic_core_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 200 * 201 * 4));
-            attr_set[dev] = true;
-        }
+        if (const int rc = idl::raise_dyn_lds<iic_core_rows_kernel>(200 * 201 * 4)) return rc;
         // scratch: [0, C*C) the unshifted gradient; then (16-byte aligned) 2 doubles per workgroup of the first launch + the total
         const int G = (C + IIC_RPW - 1) / IIC_RPW;
         IDL_REQUIRE((((uintptr_t)scratch) & 15u) == 0, "iic_core: scratch must be 16-byte aligned");
@@ -1570,29 +1531,19 @@ int idl_iic_core(float *P0, int C, float lamb, float eps, float w_iic, float *sc
 }
 
 // idl_iic_core for 48 < n_clusters <= 200 WITHOUT its second launch, and z dP0 instead: dzs[r][c] = sum_k z[r][k] dP0[k][c] for all m rows (what
-// idl_mid_bwd_gather_planes takes as z_dP0); P0 keeps the joint, out[3] the IIC loss.  scratch as idl_iic_core's.
+// idl_mid_bwd_gather takes as z_dP0); P0 keeps the joint, out[3] the IIC loss.  scratch as idl_iic_core's.
 int idl_iic_core_dz(const float *P0, int C, float lamb, float eps, float w_iic, float *scratch, float *out, const float *z, int m, float *dzs, void *stream)
 {
     IDL_REQUIRE(P0 && scratch && out && z && dzs && C > 48 && C <= 200 && m >= 1, "iic_core_dz: NULL buffer, or n_clusters outside 49..200");
     IDL_REQUIRE((((uintptr_t)scratch) & 15u) == 0, "iic_core_dz: scratch must be 16-byte aligned");
     const int lds = C * (C | 1) * 4;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    IDL_HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)iic_core_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 200 * 201 * 4));
-        attr_set[dev] = true;
-    }
+    if (const int rc = idl::raise_dyn_lds<iic_core_rows_kernel>(200 * 201 * 4)) return rc;
     const int G = (C + IIC_RPW - 1) / IIC_RPW;
     double *part = (double *)(scratch + ((C * C + 3) & ~3));
     const int groups = ((C + 15) / 16 + 3) / 4;              // (a workgroup: 16 rows x 4 column tiles)
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin): both launches in one record
-        idl::PlanHead h{};
-        h.kind = idl::PLAN_IIC_CORE_DZ; h.grid[0] = (unsigned)G; h.grid[1] = 1; h.grid[2] = 1; h.block = 1024; h.lds = (unsigned)lds;
-        h.grid2[0] = (unsigned)(((m + 15) / 16) * groups); h.grid2[1] = 1; h.grid2[2] = 1;
-        memcpy(plan, &h, sizeof(h));
-        const IicDzParams p{P0, C, lamb, eps, w_iic, scratch, part, G, z, m, dzs, out};
-        memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
+        idl::fill_plan(plan, idl::PLAN_IIC_CORE_DZ, 0, dim3((unsigned)G), 1024, (unsigned)lds, IicDzParams{P0, C, lamb, eps, w_iic, scratch, part, G, z, m, dzs, out},
+                       dim3((unsigned)(((m + 15) / 16) * groups)));
         return IDL_OK;
     }
     hipLaunchKernelGGL(iic_core_rows_kernel, dim3(G), dim3(1024), lds, (hipStream_t)stream, P0, C, lamb, eps, scratch, part);
@@ -1647,41 +1598,36 @@ int idl_mid_bwd(const float *z, const float *r2, const float *f, const float *in
 }
 
 
-static int mid_bwd_gather_impl(const float *z, const float *r2, const float *f, const float *inv, const float *G, int g_parts, const float *dP0,
+// idl_mid_bwd whose spare workgroups assemble a share of the next batch (next_batch; its planes too, where given), dr1 also or only as two fp16 planes
+// (dr1_hi / dr1_lo) and, beyond 48 classes, z dP0 as an input
+int idl_mid_bwd_gather(const float *z, const float *r2, const float *f, const float *inv, const float *G, int g_parts, const float *dP0,
                        const float *W3, const float *W2, const float *act1, int m, int C, int train, float nce_coef, float *dlogits,
-                       float *dlat, float *dr1, float *partial1, float *partial2, float *partial3, float *dW3_partial,
-                       const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
-                       int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale,
-                       const double *inv_scale, float *y, int part, int part_end, int parts, int act1_transposed, void *stream,
-                       uint16_t *yh, uint16_t *yl, int *over = nullptr, uint16_t *dr1h = nullptr, uint16_t *dr1l = nullptr, int *dscale = nullptr,
-                       const float *dzs = nullptr)
+                       float *dlat, float *dr1, float *partial1, float *partial2, float *partial3, float *dW3_partial, int act1_transposed,
+                       void *dr1_hi, void *dr1_lo, int *dr1_scale, int *dr1_overflow_flag, const float *z_dP0, const idl_next_batch_t *next_batch, void *stream)
 {
-    IDL_REQUIRE((dr1h != nullptr) == (dr1l != nullptr) && (dr1h == nullptr || (dscale && over && ((((uintptr_t)dr1h) | ((uintptr_t)dr1l)) & 15u) == 0)),
+    uint16_t *dr1h = (uint16_t *)dr1_hi, *dr1l = (uint16_t *)dr1_lo;
+    IDL_REQUIRE((dr1h != nullptr) == (dr1l != nullptr) && (dr1h == nullptr || (dr1_scale && dr1_overflow_flag && ((((uintptr_t)dr1h) | ((uintptr_t)dr1l)) & 15u) == 0)),
                 "mid_bwd_gather: dr1's planes need both planes (16-byte aligned), the words of their scale and the flag");
     IDL_REQUIRE(g_parts >= 1 && g_parts <= 16, "mid_bwd: g_parts outside 1..16");
     IDL_REQUIRE(z && r2 && f && inv && G && dP0 && W3 && W2 && act1 && dlogits && dlat && (dr1 || dr1h) && partial1 && partial2 && partial3, "NULL buffer");
     IDL_REQUIRE(m >= 2 && (m % 2) == 0 && C >= 1 && C <= 64 * MAX_CPL, "mid_bwd: even m, n_clusters in 1..256");
     IDL_REQUIRE(dW3_partial == nullptr || C <= 48, "mid_bwd: dW3 partials need n_clusters <= 48");
     MidBwdArgs a{};
-    a.dr1h = dr1h; a.dr1l = dr1l; a.dscale = dscale; a.dover = over; a.dzs = dzs;
-    IDL_REQUIRE(dzs == nullptr || C > 48, "mid_bwd_gather: z dP0 as an input is the n_clusters > 48 form");
+    a.dr1h = dr1h; a.dr1l = dr1l; a.dscale = dr1_scale; a.dover = dr1_overflow_flag; a.dzs = z_dP0;
+    IDL_REQUIRE(z_dP0 == nullptr || C > 48, "mid_bwd_gather: z dP0 as an input is the n_clusters > 48 form");
     a.z = z; a.r2 = r2; a.f = f; a.inv = inv; a.G = G; a.dP0 = dP0; a.W3 = W3; a.W2 = W2; a.act1 = act1;
     a.dlogits = dlogits; a.dlat = dlat; a.dr1 = dr1; a.partial1 = partial1; a.partial2 = partial2; a.partial3 = partial3;
     a.dW3_part = dW3_partial; a.ctl = nullptr; a.batch_advance = 0;
     a.g_parts = g_parts; a.m = m; a.C = C; a.train = train; a.nce_coef = nce_coef; a.act1_t = act1_transposed ? 1 : 0;
     Riders rd;
-    if (const int rc = riders_of("mid_bwd_gather", feats, n, fdim, view_stride, pair_idx, base, base_add, n_pairs, batch, mean, scale, inv_scale, y, yh, yl, over,
-                                 part, part_end, parts, rd)) return rc;
+    if (const int rc = riders_of("mid_bwd_gather", next_batch, rd)) return rc;
     const unsigned grid = (unsigned)COL_PARTS + rd.wgs();
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin)
-        IDL_REQUIRE(C <= 48 || (dr1h != nullptr && dzs != nullptr),
+        IDL_REQUIRE(C <= 48 || (dr1h != nullptr && z_dP0 != nullptr),
                     "mid_bwd_gather: beyond 48 classes only the form with dr1 as planes and z dP0 given can be recorded");
-        idl::PlanHead h{};
-        if (C > 48) { h.variant = 1; h.lds = (unsigned)(C * H2 * (int)sizeof(float)); }      // (the BIG body: W3 in dynamic LDS)
-        h.kind = idl::PLAN_MID_BWD; h.grid[0] = grid; h.grid[1] = 1; h.grid[2] = 1; h.block = 64 * MID_WAVES;
-        memcpy(plan, &h, sizeof(h));
-        const MidBwdParams p{a, rd.t0, rd.t1, rd.g};
-        memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
+        // (variant 1: the BIG body beyond 48 classes, W3 in dynamic LDS)
+        idl::fill_plan(plan, idl::PLAN_MID_BWD, C > 48 ? 1 : 0, dim3(grid), 64 * MID_WAVES, C > 48 ? (unsigned)(C * H2 * (int)sizeof(float)) : 0u,
+                       MidBwdParams{a, rd.t0, rd.t1, rd.g});
         return IDL_OK;
     }
     if (C > 48) return dr1h != nullptr ? launch_mid_bwd_big<true>(a, grid, rd.t0, rd.t1, rd.g, stream) : launch_mid_bwd_big<false>(a, grid, rd.t0, rd.t1, rd.g, stream);
@@ -1689,33 +1635,6 @@ static int mid_bwd_gather_impl(const float *z, const float *r2, const float *f, 
     else hipLaunchKernelGGL((mid_bwd_kernel<false, false>), dim3(grid), dim3(64 * MID_WAVES), 0, (hipStream_t)stream, a, rd.t0, rd.t1, rd.g);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
-}
-
-int idl_mid_bwd_gather(const float *z, const float *r2, const float *f, const float *inv, const float *G, int g_parts, const float *dP0,
-                       const float *W3, const float *W2, const float *act1, int m, int C, int train, float nce_coef, float *dlogits,
-                       float *dlat, float *dr1, float *partial1, float *partial2, float *partial3, float *dW3_partial,
-                       const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
-                       int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale,
-                       const double *inv_scale, float *y, int part, int part_end, int parts, int act1_transposed, void *stream)
-{
-    return mid_bwd_gather_impl(z, r2, f, inv, G, g_parts, dP0, W3, W2, act1, m, C, train, nce_coef, dlogits, dlat, dr1, partial1, partial2, partial3,
-                               dW3_partial, feats, n, fdim, view_stride, pair_idx, base, base_add, n_pairs, batch, mean, scale, inv_scale, y, part,
-                               part_end, parts, act1_transposed, stream, nullptr, nullptr);
-}
-
-// ... the same launch with the next batch ALSO written as two fp16 planes (planes.h) by the assembling workgroups
-int idl_mid_bwd_gather_planes(const float *z, const float *r2, const float *f, const float *inv, const float *G, int g_parts, const float *dP0,
-                              const float *W3, const float *W2, const float *act1, int m, int C, int train, float nce_coef, float *dlogits,
-                              float *dlat, float *dr1, float *partial1, float *partial2, float *partial3, float *dW3_partial,
-                              const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
-                              int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale,
-                              const double *inv_scale, float *y, void *y_hi, void *y_lo, int *overflow_flag, int part, int part_end, int parts,
-                              int act1_transposed, void *dr1_hi, void *dr1_lo, int *dr1_scale, const float *z_dP0, void *stream)
-{
-    return mid_bwd_gather_impl(z, r2, f, inv, G, g_parts, dP0, W3, W2, act1, m, C, train, nce_coef, dlogits, dlat, dr1, partial1, partial2, partial3,
-                               dW3_partial, feats, n, fdim, view_stride, pair_idx, base, base_add, n_pairs, batch, mean, scale, inv_scale, y, part,
-                               part_end, parts, act1_transposed, stream, (uint16_t *)y_hi, (uint16_t *)y_lo, overflow_flag, (uint16_t *)dr1_hi,
-                               (uint16_t *)dr1_lo, dr1_scale, z_dP0);
 }
 
 int idl_col_sum_parts(void) { return COL_PARTS; }
@@ -1785,45 +1704,41 @@ static uint64_t *stamp_buffer()
 
 static int g_phase_mode_host = 0;     // idl_debug_phase_stamps: while armed, the optimizer launch leaves the stamp buffer alone
 
-static int rmsprop_launch(int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
-                          float *const *square_avg, const int64_t *sizes, const float *hyper, int64_t *ctl, int64_t batch_advance,
-                          const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out, const idl_dev::GatherArgs &g,
-                          void *stream, int wg_index = -1, const float *wg_dy = nullptr, const float *wg_x = nullptr, int wg_m = 0,
-                          int wg_n_out = 0, int wg_n_in = 0, float *wg_grad = nullptr, int wg_x_transposed = 0,
-                          const wg_dev::WgArgs *big = nullptr, int big_index = -1, const l1_dev::L1Args *l1 = nullptr, int skip_index = -1,
-                          const ReduceArgs *red = nullptr, const wgp_dev::XpArgs *xp = nullptr)
+// What carries the optimizer's blocks besides a launch of their own -- at most one of these
+struct TailCarrier {
+    const wg_dev::WgArgs *big = nullptr;       // the dW1 tiles at the head of the launch: they update tensor skip_index (wgrad_rmsprop_kernel)
+    const l1_dev::L1Args *l1 = nullptr;        // the layer-1 forward tiles of the next step (l1_rms_kernel)
+    const ReduceArgs *red = nullptr;           // the workgroups that add up the two-plane layer-1 tiles' partial sums (reduce_rms_kernel)
+    const wgp_dev::XpArgs *xp = nullptr;       // the loader waves of the two-plane dW1 tiles (wgrad_dplanes_rms_kernel)
+};
+
+static int rmsprop_launch(const idl_opt_tail_t &t, const idl_dev::GatherArgs &g, void *stream, const TailCarrier &by)
 {
-    IDL_REQUIRE(count >= 1 && count <= 8 && params && grads && square_avg && sizes && hyper && ctl, "rmsprop_step: 1..8 tensors");
+    const int count = t.count, wg_index = t.wg_index, skip_index = t.skip_index;
+    IDL_REQUIRE(count >= 1 && count <= 8 && t.params && t.grads && t.square_avg && t.sizes && t.hyper && t.ctl, "rmsprop_step: 1..8 tensors");
     RmsArgs a{};
     a.count = count;
-    a.loss_rows = loss_rows; a.out = (loss_rows != nullptr && loss_m > 0) ? out : nullptr; a.loss_m = loss_m; a.w_nce = w_nce; a.w_iic = w_iic;
-    int64_t mx = 0;
+    a.loss_rows = t.loss_rows; a.out = (t.loss_rows != nullptr && t.loss_m > 0) ? t.out : nullptr; a.loss_m = t.loss_m; a.w_nce = t.w_nce; a.w_iic = t.w_iic;
     for (int i = 0; i < count; ++i) {
-        a.p[i] = params[i]; a.g[i] = grads[i]; a.v[i] = square_avg[i]; a.n[i] = sizes[i];
-        a.parts[i] = grad_parts ? grad_parts[i] : 1;
+        a.p[i] = t.params[i]; a.g[i] = t.grads[i]; a.v[i] = t.square_avg[i]; a.n[i] = t.sizes[i];
+        a.parts[i] = t.grad_parts ? t.grad_parts[i] : 1;
         IDL_REQUIRE(a.parts[i] >= 1, "rmsprop_step: grad_parts must be >= 1");
-        if (sizes[i] > mx) mx = sizes[i];
     }
     if (wg_index >= 0) {
-        IDL_REQUIRE(wg_index < count && wg_dy && wg_x && wg_m >= 1 && wg_n_out >= 16 && (wg_n_out % 16) == 0 && wg_n_in >= 16 &&
-                    (wg_n_in % 16) == 0 && sizes[wg_index] == (int64_t)wg_n_out * wg_n_in && (int64_t)wg_m * wg_n_in < (1ll << 31),
+        IDL_REQUIRE(wg_index < count && t.wg_dy && t.wg_x && t.wg_m >= 1 && t.wg_n_out >= 16 && (t.wg_n_out % 16) == 0 && t.wg_n_in >= 16 &&
+                    (t.wg_n_in % 16) == 0 && t.sizes[wg_index] == (int64_t)t.wg_n_out * t.wg_n_in && (int64_t)t.wg_m * t.wg_n_in < (1ll << 31),
                     "rmsprop_step: in-launch weight gradient needs n_out, n_in multiples of 16 and sizes[wg_index] == n_out * n_in");
-        a.wg_t = wg_index; a.wg_dy = wg_dy; a.wg_x = wg_x; a.wg_grad = wg_grad; a.wg_m = wg_m; a.wg_n_out = wg_n_out; a.wg_n_in = wg_n_in;
-        a.wg_tiles = (wg_n_out / 16) * (wg_n_in / 16);
-        a.wg_xt = wg_x_transposed ? 1 : 0;
-        IDL_REQUIRE(!wg_x_transposed || ((wg_m & 3) == 0 && (((uintptr_t)wg_x) & 15u) == 0), "rmsprop_step: transposed wg_x needs 4 | m and 16-byte alignment");
+        a.wg_t = wg_index; a.wg_dy = t.wg_dy; a.wg_x = t.wg_x; a.wg_grad = t.wg_grad; a.wg_m = t.wg_m; a.wg_n_out = t.wg_n_out; a.wg_n_in = t.wg_n_in;
+        a.wg_tiles = (t.wg_n_out / 16) * (t.wg_n_in / 16);
+        a.wg_xt = t.wg_x_transposed ? 1 : 0;
+        IDL_REQUIRE(!t.wg_x_transposed || ((t.wg_m & 3) == 0 && (((uintptr_t)t.wg_x) & 15u) == 0), "rmsprop_step: transposed wg_x needs 4 | m and 16-byte alignment");
         a.n[wg_index] = 0;                  // its optimizer blocks have nothing to do: the tile workgroups update it
-        mx = 0;
-        for (int i = 0; i < count; ++i) if (a.n[i] > mx) mx = a.n[i];
     }
-    (void)mx;
-    if (skip_index >= 0 && skip_index < count) a.n[skip_index] = 0;     // (updated elsewhere: the dW1 tiles' own launch)
-    if (big != nullptr) {                   // tensor big_index is updated by the tile workgroups at the head of the launch
-        IDL_REQUIRE(big_index >= 0 && big_index < count && big_index != wg_index &&
-                    sizes[big_index] == (int64_t)big->p.n_out * big->p.n_in && big->p.W == params[big_index] && big->p.V == square_avg[big_index],
-                    "wgrad_rmsprop_step: w1_index must name the tensor the tiles update");
-        a.n[big_index] = 0;
-    }
+    if (skip_index >= 0 && skip_index < count) a.n[skip_index] = 0;     // (updated elsewhere: by the dW1 tiles, of this launch or of their own)
+    if (by.big != nullptr)                  // ... by the tile workgroups at the head of this launch
+        IDL_REQUIRE(skip_index >= 0 && skip_index < count && skip_index != wg_index &&
+                    t.sizes[skip_index] == (int64_t)by.big->p.n_out * by.big->p.n_in && by.big->p.W == t.params[skip_index] && by.big->p.V == t.square_avg[skip_index],
+                    "wgrad_rmsprop_step: skip_index must name the tensor the tiles update");
     int nb_total = 0;
     for (int i = 0; i < count; ++i) {
         const bool vec = a.parts[i] == 1 && (a.n[i] & 3) == 0 && ((((uintptr_t)a.p[i]) | ((uintptr_t)a.g[i]) | ((uintptr_t)a.v[i])) & 15u) == 0;
@@ -1835,83 +1750,60 @@ static int rmsprop_launch(int count, float *const *params, const float *const *g
     if (nb_total == 0) nb_total = 1;        // (step counter / loss assembly still need a block)
     for (int i = count; i <= 8; ++i) a.first[i] = nb_total;
     const int64_t extra = g.y != nullptr ? idl_dev::gather_blocks(g.f, g.batch) : 0;
-    if (xp != nullptr) {                    // ... carried by the loader waves of the two-plane dW1 tiles (wgrad_xplanes_rms_kernel)
-        IDL_REQUIRE(big == nullptr && l1 == nullptr && red == nullptr && extra == 0, "wgrad_xplanes_rms: no other tiles, no batch assembly");
+    const float *hyper = t.hyper;
+    int64_t *ctl = t.ctl;
+    const int64_t batch_advance = t.batch_advance;
+    if (by.xp != nullptr) {                 // ... carried by the loader waves of the two-plane dW1 tiles (wgrad_xplanes_rms_kernel)
+        const wgp_dev::XpArgs *xp = by.xp;
+        IDL_REQUIRE(by.big == nullptr && by.l1 == nullptr && by.red == nullptr && extra == 0, "wgrad_xplanes_rms: no other tiles, no batch assembly");
         idl::DeviceInfo di;
         if (const int rc = idl::device_info(&di); rc != IDL_OK) return rc;
         IDL_REQUIRE(nb_total + a.wg_tiles <= xp->tiles && xp->tiles <= di.cus, "wgrad_xplanes_rms: the tail's blocks need a tile each, and every tile its own CU");
         if (void *plan = idl::take_plan()) {      // recorded, not launched (idl_plan_begin)
-            idl::PlanHead h{};
-            h.kind = idl::PLAN_WGRAD_XPLANES; h.grid[0] = (unsigned)xp->tiles; h.grid[1] = 1; h.grid[2] = 1; h.block = wgp_dev::NT; h.lds = wgp_dev::LDS_BYTES + 16;
-            memcpy(plan, &h, sizeof(h));
-            const XpRmsParams xr{*xp, a, hyper, ctl, batch_advance, nb_total + a.wg_tiles};
-            memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &xr, sizeof(xr));
+            idl::fill_plan(plan, idl::PLAN_WGRAD_XPLANES, 0, dim3((unsigned)xp->tiles), wgp_dev::NT, wgp_dev::LDS_BYTES + 16,
+                           XpRmsParams{*xp, a, hyper, ctl, batch_advance, nb_total + a.wg_tiles});
             return IDL_OK;
         }
-        static bool attr_set[64] = {};
-        int dev = 0;
-        IDL_HIP_TRY(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_dplanes_rms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wgp_dev::LDS_BYTES + 16));
-            attr_set[dev] = true;
-        }
+        if (const int rc = idl::raise_dyn_lds<wgrad_dplanes_rms_kernel>(wgp_dev::LDS_BYTES + 16)) return rc;
         hipLaunchKernelGGL(wgrad_dplanes_rms_kernel, dim3((unsigned)xp->tiles), dim3(wgp_dev::NT), wgp_dev::LDS_BYTES + 16, (hipStream_t)stream, *xp, a, hyper,
                            ctl, batch_advance, nb_total + a.wg_tiles);
         IDL_HIP_TRY(hipGetLastError());
         return IDL_OK;
     }
-    if (red != nullptr) {                   // ... beside the workgroups that add up the two-plane layer-1 tiles' partial sums (reduce_rms_kernel)
-        IDL_REQUIRE(big == nullptr && l1 == nullptr && extra == 0 && idl::take_plan() == nullptr, "reduce_parts_rms: no tiles, no batch assembly, not recordable");
-        hipLaunchKernelGGL(reduce_rms_kernel, dim3((unsigned)(red->blocks + nb_total + a.wg_tiles)), dim3(256), 0, (hipStream_t)stream, *red, a, hyper, ctl,
+    if (by.red != nullptr) {                // ... beside the workgroups that add up the two-plane layer-1 tiles' partial sums (reduce_rms_kernel)
+        IDL_REQUIRE(by.big == nullptr && by.l1 == nullptr && extra == 0 && idl::take_plan() == nullptr, "reduce_parts_rms: no tiles, no batch assembly, not recordable");
+        hipLaunchKernelGGL(reduce_rms_kernel, dim3((unsigned)(by.red->blocks + nb_total + a.wg_tiles)), dim3(256), 0, (hipStream_t)stream, *by.red, a, hyper, ctl,
                            batch_advance, 1);
         IDL_HIP_TRY(hipGetLastError());
         return IDL_OK;
     }
-    if (l1 != nullptr) {                    // the optimizer blocks ride behind the layer-1 forward tiles of the next step (l1_rms_kernel)
-        IDL_REQUIRE(big == nullptr && extra == 0 && idl::take_plan() == nullptr, "l1_fwd_rms: no dW1 tiles, no batch assembly, not recordable");
-        static bool attr_set[64] = {};
-        int dev = 0;
-        IDL_HIP_TRY(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)l1_rms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l1_dev::LDS_BYTES));
-            attr_set[dev] = true;
-        }
-        hipLaunchKernelGGL(l1_rms_kernel, dim3((unsigned)(l1->n_tiles + nb_total + a.wg_tiles)), dim3(l1_dev::THREADS), l1_dev::LDS_BYTES,
-                           (hipStream_t)stream, *l1, a, hyper, ctl, batch_advance);
+    if (by.l1 != nullptr) {                 // the optimizer blocks ride behind the layer-1 forward tiles of the next step (l1_rms_kernel)
+        IDL_REQUIRE(by.big == nullptr && extra == 0 && idl::take_plan() == nullptr, "l1_fwd_rms: no dW1 tiles, no batch assembly, not recordable");
+        if (const int rc = idl::raise_dyn_lds<l1_rms_kernel>(l1_dev::LDS_BYTES)) return rc;
+        hipLaunchKernelGGL(l1_rms_kernel, dim3((unsigned)(by.l1->n_tiles + nb_total + a.wg_tiles)), dim3(l1_dev::THREADS), l1_dev::LDS_BYTES,
+                           (hipStream_t)stream, *by.l1, a, hyper, ctl, batch_advance);
         IDL_HIP_TRY(hipGetLastError());
         return IDL_OK;
     }
+    const wg_dev::WgArgs *big = by.big;
+    const dim3 grid((unsigned)((big != nullptr ? big->tiles : 0) + nb_total + extra + a.wg_tiles));
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin)
-        idl::PlanHead h{};
         const RmsParams p{a, hyper, ctl, batch_advance, (int)extra, g};
-        if (big != nullptr) {                       // the dW1 tiles ride at the head of every voter's share of the launch
-            h.kind = idl::PLAN_WGRAD_RMSPROP; h.grid[0] = (unsigned)(big->tiles + nb_total + extra + a.wg_tiles); h.grid[1] = 1; h.grid[2] = 1;
-            h.block = wg_dev::THREADS;
-            memcpy(plan, &h, sizeof(h));
-            const WgRmsParams wp{*big, p};
-            memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &wp, sizeof(wp));
-            return IDL_OK;
-        }
-        h.kind = idl::PLAN_RMSPROP; h.grid[0] = (unsigned)(nb_total + extra + a.wg_tiles); h.grid[1] = 1; h.grid[2] = 1; h.block = 256;
-        memcpy(plan, &h, sizeof(h));
-        memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &p, sizeof(p));
+        if (big != nullptr) idl::fill_plan(plan, idl::PLAN_WGRAD_RMSPROP, 0, grid, wg_dev::THREADS, 0, WgRmsParams{*big, p});     // the dW1 tiles ride at the head of every voter's share of the launch
+        else idl::fill_plan(plan, idl::PLAN_RMSPROP, 0, grid, 256, 0, p);
         return IDL_OK;
     }
     if (big != nullptr) {
-        const dim3 grid((unsigned)(big->tiles + nb_total + extra + a.wg_tiles));
         static const bool skip = [] { const char *e = idl::dev_env("stamps_skip_tiles"); return e != nullptr && e[0] == '1'; }();
-        static bool attr_set[64] = {};
-        int dev = 0;
-        IDL_HIP_TRY(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_rmsprop_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_dev::IMG_BYTES));
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_rmsprop_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_dev::IMG_BYTES));
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_rmsprop_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_dev::IMG_BYTES));
-            attr_set[dev] = true;
-        }
+        if (const int rc = idl::raise_dyn_lds<wgrad_rmsprop_kernel<false, false>>(wg_dev::IMG_BYTES)) return rc;
         const dim3 block(wg_dev::THREADS);
         const hipStream_t st_ = (hipStream_t)stream;
-        if (uint64_t *st = g_phase_mode_host ? nullptr : stamp_buffer(); st != nullptr && skip)
+        uint64_t *st = g_phase_mode_host ? nullptr : stamp_buffer();
+        if (st != nullptr) {                      // (the diagnostic instances)
+            if (const int rc = idl::raise_dyn_lds<wgrad_rmsprop_kernel<true, false>>(wg_dev::IMG_BYTES)) return rc;
+            if (const int rc = idl::raise_dyn_lds<wgrad_rmsprop_kernel<true, true>>(wg_dev::IMG_BYTES)) return rc;
+        }
+        if (st != nullptr && skip)
             hipLaunchKernelGGL((wgrad_rmsprop_kernel<true, true>), grid, block, wg_dev::IMG_BYTES, st_, *big, a, hyper, ctl, batch_advance, (int)extra, g, st);
         else if (st != nullptr)
             hipLaunchKernelGGL(wgrad_rmsprop_kernel<true>, grid, block, wg_dev::IMG_BYTES, st_, *big, a, hyper, ctl, batch_advance, (int)extra, g, st);
@@ -1920,108 +1812,73 @@ static int rmsprop_launch(int count, float *const *params, const float *const *g
                                (uint64_t *)nullptr);
     }
     else
-        hipLaunchKernelGGL(rmsprop_kernel, dim3((unsigned)(nb_total + extra + a.wg_tiles)), dim3(256), 0, (hipStream_t)stream, a, hyper, ctl,
-                           batch_advance, 0, (int)extra, g);
+        hipLaunchKernelGGL(rmsprop_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, hyper, ctl, batch_advance, 0, (int)extra, g);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }
 
-int idl_rmsprop_step(int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
-                     float *const *square_avg, const int64_t *sizes, const float *hyper, int64_t *ctl, int64_t batch_advance,
-                     const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out, void *stream)
+// The optimizer launch.  next_batch (or NULL): it also assembles the whole next batch, at the offset ctl[1] that an earlier launch of the step advanced.
+int idl_rmsprop_step(const idl_opt_tail_t *tail, const idl_next_batch_t *next_batch, void *stream)
 {
+    IDL_REQUIRE(tail != nullptr, "rmsprop_step: NULL tail");
     idl_dev::GatherArgs g{};
-    return rmsprop_launch(count, params, grads, grad_parts, square_avg, sizes, hyper, ctl, batch_advance, loss_rows, loss_m, w_nce, w_iic,
-                          out, g, stream);
-}
-
-int idl_rmsprop_step_gather(int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
-                            float *const *square_avg, const int64_t *sizes, const float *hyper, int64_t *ctl,
-                            const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out,
-                            const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx, int64_t n_pairs,
-                            int64_t batch, const double *mean, const double *scale, const double *inv_scale, float *y, void *stream)
-{
-    IDL_REQUIRE(feats && pair_idx && mean && scale && y && n >= 1 && f >= 1 && batch >= 1 && n_pairs >= 0, "rmsprop_step_gather: bad gather arguments");
-    idl_dev::GatherArgs g{feats, n, f, view_stride, pair_idx, ctl + 1, batch, n_pairs, mean, scale, inv_scale, y};
-    return rmsprop_launch(count, params, grads, grad_parts, square_avg, sizes, hyper, ctl, 0, loss_rows, loss_m, w_nce, w_iic, out, g, stream);
-}
-
-int idl_rmsprop_step_gather_wgrad(int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
-                                  float *const *square_avg, const int64_t *sizes, const float *hyper, int64_t *ctl,
-                                  const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out,
-                                  const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx, int64_t n_pairs,
-                                  int64_t batch, const double *mean, const double *scale, const double *inv_scale, float *y,
-                                  int wg_index, const float *wg_dy, const float *wg_x, int wg_x_transposed, int wg_m, int wg_n_out, int wg_n_in,
-                                  float *wg_grad, int64_t batch_advance, void *stream)
-{
-    idl_dev::GatherArgs g{};
-    if (feats != nullptr) {
-        IDL_REQUIRE(pair_idx && mean && scale && y && n >= 1 && f >= 1 && batch >= 1 && n_pairs >= 0, "rmsprop_step_gather_wgrad: bad gather arguments");
-        g = idl_dev::GatherArgs{feats, n, f, view_stride, pair_idx, ctl + 1, batch, n_pairs, mean, scale, inv_scale, y};
+    if (const idl_next_batch_t *nb = next_batch; nb != nullptr && nb->feats != nullptr) {
+        IDL_REQUIRE(tail->ctl != nullptr && nb->base == tail->ctl + 1, "rmsprop_step: the optimizer launch assembles the batch at ctl[1]: next_batch->base must be ctl + 1");
+        IDL_REQUIRE(nb->y_hi == nullptr && nb->y_lo == nullptr, "rmsprop_step: the optimizer launch writes no planes of the next batch");
+        IDL_REQUIRE(nb->base_add == 0, "rmsprop_step: the optimizer launch takes no base_add");
+        IDL_REQUIRE(nb->part == 0 && nb->part_end == nb->parts, "rmsprop_step: the optimizer launch assembles the whole batch, not a share");
+        IDL_REQUIRE(nb->pair_idx && nb->mean && nb->scale && nb->y && nb->n >= 1 && nb->f >= 1 && nb->batch >= 1 && nb->n_pairs >= 0, "rmsprop_step: bad gather arguments");
+        g = idl_dev::GatherArgs{nb->feats, nb->n, nb->f, nb->view_stride, nb->pair_idx, tail->ctl + 1, nb->batch, nb->n_pairs, nb->mean, nb->scale, nb->inv_scale, nb->y};
     }
-    return rmsprop_launch(count, params, grads, grad_parts, square_avg, sizes, hyper, ctl, batch_advance, loss_rows, loss_m, w_nce, w_iic, out, g,
-                          stream, wg_index, wg_dy, wg_x, wg_m, wg_n_out, wg_n_in, wg_grad, wg_x_transposed);
+    return rmsprop_launch(*tail, g, stream, TailCarrier{});
 }
 
-int idl_wgrad_rmsprop_step(int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
-                           float *const *square_avg, const int64_t *sizes, const float *hyper, int64_t *ctl,
-                           const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out,
-                           int w1_index, const float *w1_dy, const float *w1_x, int w1_m, int w1_n_out, int w1_n_in, float *w1_grad,
-                           int wg_index, const float *wg_dy, const float *wg_x, int wg_x_transposed, int wg_m, int wg_n_out, int wg_n_in,
-                           float *wg_grad, int64_t batch_advance, void *stream)
+// The optimizer launch with the dW1 = w1_dy^T w1_x tiles (and RMSprop on tensor tail->skip_index from their registers) at its head.
+int idl_wgrad_rmsprop_step(const float *w1_dy, const float *w1_x, int w1_m, int w1_n_out, int w1_n_in, float *w1_grad, const idl_opt_tail_t *tail, void *stream)
 {
-    IDL_REQUIRE(count >= 1 && count <= 8 && params && square_avg && w1_index >= 0 && w1_index < count, "wgrad_rmsprop_step: w1_index outside the tensors");
+    IDL_REQUIRE(tail != nullptr, "wgrad_rmsprop_step: NULL tail");
+    const int w1_index = tail->skip_index;
+    IDL_REQUIRE(tail->count >= 1 && tail->count <= 8 && tail->params && tail->square_avg && w1_index >= 0 && w1_index < tail->count,
+                "wgrad_rmsprop_step: skip_index outside the tensors");
     IDL_REQUIRE(w1_dy && w1_x && wg_dev::supported(w1_m, w1_n_out, w1_n_in), "wgrad_rmsprop_step: m % 32 == 0, n_out % 64 == 0, n_in % 128 == 0");
-    IDL_REQUIRE((((uintptr_t)w1_dy | (uintptr_t)w1_x | (uintptr_t)w1_grad | (uintptr_t)params[w1_index] | (uintptr_t)square_avg[w1_index]) & 15u) == 0,
+    IDL_REQUIRE((((uintptr_t)w1_dy | (uintptr_t)w1_x | (uintptr_t)w1_grad | (uintptr_t)tail->params[w1_index] | (uintptr_t)tail->square_avg[w1_index]) & 15u) == 0,
                 "wgrad_rmsprop_step: buffers must be 16-byte aligned");
     IDL_REQUIRE((int64_t)w1_m * w1_n_in < (1ll << 29) && (int64_t)w1_n_out * w1_n_in < (1ll << 29), "wgrad_rmsprop_step: operands beyond 2^31 bytes");
     wg_dev::WgArgs w{};
-    w.p = wg_dev::WgProblem{w1_dy, w1_x, w1_grad, params[w1_index], square_avg[w1_index], w1_n_out, w1_n_in};
-    w.hyper = hyper; w.m = w1_m;
+    w.p = wg_dev::WgProblem{w1_dy, w1_x, w1_grad, tail->params[w1_index], tail->square_avg[w1_index], w1_n_out, w1_n_in};
+    w.hyper = tail->hyper; w.m = w1_m;
     w.tiles_m = w1_n_out / wg_dev::TM;
     w.tiles = w.tiles_m * (w1_n_in / wg_dev::TN);
-    idl_dev::GatherArgs g{};
-    return rmsprop_launch(count, params, grads, grad_parts, square_avg, sizes, hyper, ctl, batch_advance, loss_rows, loss_m, w_nce, w_iic, out, g,
-                          stream, wg_index, wg_dy, wg_x, wg_m, wg_n_out, wg_n_in, wg_grad, wg_x_transposed, &w, w1_index);
+    TailCarrier by;
+    by.big = &w;
+    return rmsprop_launch(*tail, idl_dev::GatherArgs{}, stream, by);
 }
 
-int idl_l1_fwd_rms(const float *W1, const float *x, int m, int n_in, float *r1_transposed,
-                   int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
-                   float *const *square_avg, const int64_t *sizes, const float *hyper, int64_t *ctl,
-                   const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out, int w1_index,
-                   int wg_index, const float *wg_dy, const float *wg_x, int wg_x_transposed, int wg_m, int wg_n_out, int wg_n_in,
-                   float *wg_grad, int64_t batch_advance, void *stream)
+int idl_l1_fwd_rms(const float *W1, const float *x, int m, int n_in, float *r1_transposed, const idl_opt_tail_t *tail, void *stream)
 {
+    IDL_REQUIRE(tail != nullptr, "l1_fwd_rms: NULL tail");
     IDL_REQUIRE(W1 && x && r1_transposed && idl_l1_fwd_supported(m, l1_dev::H1, n_in), "l1_fwd_rms: Linear(n_in, 512), m % 32 == 0, n_in % 64 == 0, n_in >= 192");
     IDL_REQUIRE((((uintptr_t)W1 | (uintptr_t)x | (uintptr_t)r1_transposed) & 15u) == 0, "l1_fwd_rms: buffers must be 16-byte aligned");
     const int n_tiles = (l1_dev::H1 / l1_dev::TH) * (m / l1_dev::TR);
     static const int prio = [] { const char *e = idl::dev_env("l1_prio"); return e ? atoi(e) : 0; }();     // (A/B knob: measured)
     const l1_dev::L1Args l{W1, x, r1_transposed, m, n_in, n_tiles, prio};
-    idl_dev::GatherArgs g{};
-    return rmsprop_launch(count, params, grads, grad_parts, square_avg, sizes, hyper, ctl, batch_advance, loss_rows, loss_m, w_nce, w_iic, out, g,
-                          stream, wg_index, wg_dy, wg_x, wg_m, wg_n_out, wg_n_in, wg_grad, wg_x_transposed, nullptr, -1, &l, w1_index);
+    TailCarrier by;
+    by.l1 = &l;
+    return rmsprop_launch(*tail, idl_dev::GatherArgs{}, stream, by);
 }
 
 
 // part[p][i], p < idl_l1_planes_parts(), i < slab_elems (4 | slab_elems): part[0][i] = ((part[0][i] + part[1][i]) + ...) in ascending p.
-// With count >= 1: the previous step's optimizer tail in the same launch (arguments as idl_l1_fwd_rms); count == 0: the sums alone.
-int idl_reduce_parts_rms(float *part, int64_t slab_elems, const int64_t *step_counter, int64_t *step_snapshot,
-                         int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
-                         float *const *square_avg, const int64_t *sizes, const float *hyper, int64_t *ctl,
-                         const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out, int w1_index,
-                         int wg_index, const float *wg_dy, const float *wg_x, int wg_x_transposed, int wg_m, int wg_n_out, int wg_n_in,
-                         float *wg_grad, int64_t batch_advance, void *stream)
+// With a tail: the previous step's optimizer tail in the same launch; tail == NULL: the sums alone.
+int idl_reduce_parts_rms(float *part, int64_t slab_elems, const int64_t *step_counter, int64_t *step_snapshot, const idl_opt_tail_t *tail, void *stream)
 {
     IDL_REQUIRE(part && slab_elems >= 4 && (slab_elems & 3) == 0 && (((uintptr_t)part) & 15u) == 0 && slab_elems < (1ll << 31), "reduce_parts_rms: 4 | slab_elems, 16-byte aligned");
-    IDL_REQUIRE((step_counter != nullptr) == (step_snapshot != nullptr) && (step_snapshot == nullptr || count == 0),
+    IDL_REQUIRE((step_counter != nullptr) == (step_snapshot != nullptr) && (step_snapshot == nullptr || tail == nullptr),
                 "reduce_parts_rms: the step counter's snapshot needs both pointers and a launch without the tail (which moves the counter)");
-    ReduceArgs r{(float4 *)part, slab_elems / 4, l1p_dev::KSPLIT, (int)((slab_elems / 4 + 256 * RED_U - 1) / (256 * RED_U)), step_counter, step_snapshot};
-    if (count == 0) {
+    const ReduceArgs r{(float4 *)part, slab_elems / 4, l1p_dev::KSPLIT, (int)((slab_elems / 4 + 256 * RED_U - 1) / (256 * RED_U)), step_counter, step_snapshot};
+    if (tail == nullptr) {
         if (void *plan = idl::take_plan()) {      // recorded, not launched (idl_plan_begin)
-            idl::PlanHead h{};
-            h.kind = idl::PLAN_REDUCE; h.grid[0] = (unsigned)r.blocks; h.grid[1] = 1; h.grid[2] = 1; h.block = 256;
-            memcpy(plan, &h, sizeof(h));
-            memcpy((unsigned char *)plan + idl::PLAN_PARAMS, &r, sizeof(r));
+            idl::fill_plan(plan, idl::PLAN_REDUCE, 0, dim3((unsigned)r.blocks), 256, 0, r);
             return IDL_OK;
         }
         hipLaunchKernelGGL(reduce_rms_kernel, dim3((unsigned)r.blocks), dim3(256), 0, (hipStream_t)stream, r, RmsArgs{}, (const float *)nullptr, (int64_t *)nullptr,
@@ -2029,19 +1886,16 @@ int idl_reduce_parts_rms(float *part, int64_t slab_elems, const int64_t *step_co
         IDL_HIP_TRY(hipGetLastError());
         return IDL_OK;
     }
-    idl_dev::GatherArgs g{};
-    return rmsprop_launch(count, params, grads, grad_parts, square_avg, sizes, hyper, ctl, batch_advance, loss_rows, loss_m, w_nce, w_iic, out, g,
-                          stream, wg_index, wg_dy, wg_x, wg_m, wg_n_out, wg_n_in, wg_grad, wg_x_transposed, nullptr, -1, nullptr, w1_index, &r);
+    TailCarrier by;
+    by.red = &r;
+    return rmsprop_launch(*tail, idl_dev::GatherArgs{}, stream, by);
 }
 
 // The sums and the forward middle of the two-plane step in one launch (sums_fwd_kernel): part[8][m][512] from idl_l1_planes_rows.
 int idl_reduce_mid_fwd_gather_planes(const float *part, const int64_t *step_counter, int64_t *step_snapshot, float *r1_transposed,
                                      const float *b1, const float *W2, const float *b2, const float *W3, const float *b3, int m,
                                      int C, int train, uint64_t seed, float *f, float *inv, float *r2, float *z,
-                                     const float *feats, int64_t n, int64_t fdim, int64_t view_stride, const int64_t *pair_idx, const int64_t *base,
-                                     int64_t base_add, int64_t n_pairs, int64_t batch, const double *mean, const double *scale,
-                                     const double *inv_scale, float *y, void *y_hi, void *y_lo, int *overflow_flag, int part_begin, int part_end, int parts,
-                                     void *stream)
+                                     const idl_next_batch_t *next_batch, void *stream)
 {
     IDL_REQUIRE(part && step_counter && r1_transposed && b1 && W2 && b2 && W3 && b3 && f && inv && r2 && z, "reduce_mid_fwd: NULL buffer");
     IDL_REQUIRE(m >= 16 && (m % 16) == 0 && C >= 1 && C <= 64 * MAX_CPL && (int64_t)m * H1 < (1ll << 31), "reduce_mid_fwd: m must be a multiple of 16, n_clusters in 1..256");
@@ -2049,8 +1903,7 @@ int idl_reduce_mid_fwd_gather_planes(const float *part, const int64_t *step_coun
                 "reduce_mid_fwd: part / b1 / W2 / W3 must be 16-byte aligned");
     IDL_REQUIRE(idl::take_plan() == nullptr, "reduce_mid_fwd: the lone voter's launch, not recordable");
     Riders rd;
-    if (const int rc = riders_of("reduce_mid_fwd", feats, n, fdim, view_stride, pair_idx, base, base_add, n_pairs, batch, mean, scale, inv_scale, y,
-                                 (uint16_t *)y_hi, (uint16_t *)y_lo, overflow_flag, part_begin, part_end, parts, rd)) return rc;
+    if (const int rc = riders_of("reduce_mid_fwd", next_batch, rd)) return rc;
     const ReduceArgs r{(float4 *)const_cast<float *>(part), (int64_t)m * H1 / 4, l1p_dev::KSPLIT, m / SUMS_FWD_ROWS, step_counter, step_snapshot};
     const SumsFwdArgs p{b1, W2, b2, W3, b3, r1_transposed, m, C, train, seed, f, inv, r2, z, rd.t0, rd.t1, rd.g};
     hipLaunchKernelGGL(sums_fwd_kernel, dim3((unsigned)r.blocks + rd.wgs()), dim3(64 * MID_WAVES), SUMS_FWD_LDS, (hipStream_t)stream, r, p);
@@ -2058,17 +1911,14 @@ int idl_reduce_mid_fwd_gather_planes(const float *part, const int64_t *step_coun
     return IDL_OK;
 }
 
-// idl_wgrad_rmsprop_xplanes (W updated, its planes written) with THIS step's optimizer tail carried by the tiles' loader waves (tail arguments as
-// idl_l1_fwd_rms; w1_index: the tensor the tiles update, left out of the tail).  Needs a CU per tile and no more tail blocks than tiles.
+// idl_wgrad_rmsprop_xplanes (W updated, its planes written) with THIS step's optimizer tail carried by the tiles' loader waves (tail->skip_index: the
+// tensor the tiles update, left out of the tail).  Needs a CU per tile and no more tail blocks than tiles.
 int idl_wgrad_xplanes_rms(const void *dy_hi, const void *dy_lo, int *dy_scale, const void *x_hi, const void *x_lo, int ld_x, int m, int n_out, int n_in, float *grad, float *W,
-                          float *square_avg, void *w_hi, void *w_lo, int *overflow_flag,
-                          int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
-                          float *const *square_avg_all, const int64_t *sizes, const float *hyper, int64_t *ctl,
-                          const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out, int w1_index,
-                          int wg_index, const float *wg_dy, const float *wg_x, int wg_x_transposed, int wg_m, int wg_n_out, int wg_n_in,
-                          float *wg_grad, int64_t batch_advance, void *stream)
+                          float *square_avg, void *w_hi, void *w_lo, int *overflow_flag, const idl_opt_tail_t *tail, void *stream)
 {
-    IDL_REQUIRE(dy_hi && dy_lo && dy_scale && x_hi && x_lo && W && square_avg && hyper && ctl && w_hi && w_lo && overflow_flag, "wgrad_xplanes_rms: NULL buffer");
+    IDL_REQUIRE(tail != nullptr, "wgrad_xplanes_rms: NULL tail");
+    const float *hyper = tail->hyper;
+    IDL_REQUIRE(dy_hi && dy_lo && dy_scale && x_hi && x_lo && W && square_avg && hyper && tail->ctl && w_hi && w_lo && overflow_flag, "wgrad_xplanes_rms: NULL buffer");
     IDL_REQUIRE(idl_wgrad_xplanes_supported(m, n_out, n_in), "wgrad_xplanes_rms: m % 64 == 0, m >= 192, n_out % 64 == 0, n_in % 128 == 0");
     IDL_REQUIRE(ld_x >= n_in && ld_x <= n_in + 1024 && (ld_x & 7) == 0, "wgrad_xplanes_rms: n_in <= ld_x <= n_in + 1024, 8 | ld_x");
     IDL_REQUIRE((((uintptr_t)dy_hi | (uintptr_t)dy_lo | (uintptr_t)x_hi | (uintptr_t)x_lo | (uintptr_t)grad | (uintptr_t)W | (uintptr_t)square_avg) & 15u) == 0 &&
@@ -2081,9 +1931,9 @@ int idl_wgrad_xplanes_rms(const void *dy_hi, const void *dy_lo, int *dy_scale, c
     x.tiles_m = n_out / wgp_dev::TM; x.tiles = x.tiles_m * (n_in / wgp_dev::TN);
     static const int wgp_dbg = idl::dev_env("wgp_dbg") ? atoi(idl::dev_env("wgp_dbg")) : 0;      // (timing ablations; wgrad_planes_device.h)
     x.dbg = wgp_dbg;
-    idl_dev::GatherArgs g{};
-    return rmsprop_launch(count, params, grads, grad_parts, square_avg_all, sizes, hyper, ctl, batch_advance, loss_rows, loss_m, w_nce, w_iic, out, g,
-                          stream, wg_index, wg_dy, wg_x, wg_m, wg_n_out, wg_n_in, wg_grad, wg_x_transposed, nullptr, -1, nullptr, w1_index, nullptr, &x);
+    TailCarrier by;
+    by.xp = &x;
+    return rmsprop_launch(*tail, idl_dev::GatherArgs{}, stream, by);
 }
 
 #ifdef IDL_PHASE_STAMPS
@@ -2135,27 +1985,15 @@ int idl_plan_launch(const void *host_plans, const void *dev_plans, int n_voters,
         break;
     case idl::PLAN_MID_BWD:
         if (h.variant) {                         // n_clusters > 48: W3 in dynamic LDS beside the static arrays, the limit raised once per device
-            static bool attr_set[64] = {};
-            int dev = 0;
-            IDL_HIP_TRY(hipGetDevice(&dev));
             IDL_REQUIRE(h.lds >= 49u * H2 * sizeof(float) && h.lds <= 64u * MAX_CPL * H2 * sizeof(float), "plan_launch: not the record of a middle backward beyond 48 classes");
-            if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-                IDL_HIP_TRY(hipFuncSetAttribute((const void *)mid_bwd_big_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * MAX_CPL * H2 * (int)sizeof(float)));
-                attr_set[dev] = true;
-            }
+            if (const int rc = idl::raise_dyn_lds<mid_bwd_big_batched_kernel>(64 * MAX_CPL * H2 * (int)sizeof(float))) return rc;
             hipLaunchKernelGGL(mid_bwd_big_batched_kernel, dim3((unsigned)n_voters, h.grid[0]), dim3(h.block), h.lds, st, dp);
         }
         else hipLaunchKernelGGL(mid_bwd_batched_kernel, dim3((unsigned)n_voters, h.grid[0]), dim3(h.block), 0, st, dp);
         break;
     case idl::PLAN_IIC_CORE_DZ: {                // the rows launch (every workgroup keeps the joint in dynamic LDS), then the z dP0 tiles
-        static bool attr_set[64] = {};
-        int dev = 0;
-        IDL_HIP_TRY(hipGetDevice(&dev));
         IDL_REQUIRE(h.lds <= 200u * 201u * 4u && h.block == 1024u, "plan_launch: not the record of idl_iic_core_dz");
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)iic_core_rows_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 200 * 201 * 4));
-            attr_set[dev] = true;
-        }
+        if (const int rc = idl::raise_dyn_lds<iic_core_rows_batched_kernel>(200 * 201 * 4)) return rc;
         hipLaunchKernelGGL(iic_core_rows_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), h.lds, st, dp);
         hipLaunchKernelGGL(iic_dz_batched_kernel, dim3(h.grid2[0], (unsigned)n_voters), dim3(256), 0, st, dp);
         break;
@@ -2165,33 +2003,18 @@ int idl_plan_launch(const void *host_plans, const void *dev_plans, int n_voters,
     case idl::PLAN_RMSPROP:
         hipLaunchKernelGGL(rmsprop_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), 0, st, dp);
         break;
-    case idl::PLAN_WGRAD_RMSPROP: {
-        static bool attr_set[64] = {};
-        int dev = 0;
-        IDL_HIP_TRY(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_rmsprop_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wg_dev::IMG_BYTES));
-            attr_set[dev] = true;
-        }
+    case idl::PLAN_WGRAD_RMSPROP:
+        if (const int rc = idl::raise_dyn_lds<wgrad_rmsprop_batched_kernel>(wg_dev::IMG_BYTES)) return rc;
         hipLaunchKernelGGL(wgrad_rmsprop_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), wg_dev::IMG_BYTES, st, dp);
         break;
-    }
     case idl::PLAN_L1_PLANES:
-    case idl::PLAN_WGRAD_XPLANES: {
-        static bool attr_set[64] = {};
-        int dev = 0;
-        IDL_HIP_TRY(hipGetDevice(&dev));
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)l1_planes_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l1p_dev::LDS_BYTES));
-            IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_xplanes_rms_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wgp_dev::LDS_BYTES + 16));
-            attr_set[dev] = true;
-        }
-        if (h.kind == idl::PLAN_L1_PLANES)
-            hipLaunchKernelGGL(l1_planes_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), l1p_dev::LDS_BYTES, st, dp);
-        else
-            hipLaunchKernelGGL(wgrad_xplanes_rms_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), wgp_dev::LDS_BYTES + 16, st, dp);
+        if (const int rc = idl::raise_dyn_lds<l1_planes_batched_kernel>(l1p_dev::LDS_BYTES)) return rc;
+        hipLaunchKernelGGL(l1_planes_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), l1p_dev::LDS_BYTES, st, dp);
         break;
-    }
+    case idl::PLAN_WGRAD_XPLANES:
+        if (const int rc = idl::raise_dyn_lds<wgrad_xplanes_rms_batched_kernel>(wgp_dev::LDS_BYTES + 16)) return rc;
+        hipLaunchKernelGGL(wgrad_xplanes_rms_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), wgp_dev::LDS_BYTES + 16, st, dp);
+        break;
     case idl::PLAN_REDUCE:
         hipLaunchKernelGGL(reduce_batched_kernel, dim3(h.grid[0], (unsigned)n_voters), dim3(h.block), 0, st, dp);
         break;

@@ -28,19 +28,13 @@ __global__ __launch_bounds__(wg_dev::THREADS) void wgrad_q16_clock_kernel(wg_dev
 
 }  // namespace
 
-// the tiles' LDS image is 64 KB of dynamic shared memory: raised once per device for every instantiation
-static int raise_lds_limit()
+// the tiles' LDS image is 64 KB of dynamic shared memory: the launched instantiation's limit is raised once per device
+template <auto K, class... Extra>
+static int launch_tiles(const wg_dev::WgArgs &a, void *stream, Extra... extra)
 {
-    static bool attr_set[64] = {};
-    int dev = 0;
-    IDL_HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_q16_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_dev::IMG_BYTES));
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_q16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_dev::IMG_BYTES));
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_q16_clock_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_dev::IMG_BYTES));
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_q16_clock_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_dev::IMG_BYTES));
-        attr_set[dev] = true;
-    }
+    if (const int rc = idl::raise_dyn_lds<K>(wg_dev::IMG_BYTES)) return rc;
+    hipLaunchKernelGGL(K, dim3((unsigned)a.tiles), dim3(wg_dev::THREADS), wg_dev::IMG_BYTES, (hipStream_t)stream, a, extra...);
+    IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
 }
 
@@ -65,12 +59,7 @@ static int wgrad_launch(const float *dy, const float *x, int m, int n_out, int n
     a.tiles_m = n_out / wg_dev::TM;
     a.tiles = a.tiles_m * (n_in / wg_dev::TN);
     static const bool noload = [] { const char *e = idl::dev_env("wgrad_kernel"); return e != nullptr && strcmp(e, "noload") == 0; }();
-    if (const int rc = raise_lds_limit(); rc != IDL_OK) return rc;
-    const dim3 grid((unsigned)a.tiles), block(wg_dev::THREADS);
-    if (noload) hipLaunchKernelGGL((wgrad_q16_kernel<1>), grid, block, wg_dev::IMG_BYTES, (hipStream_t)stream, a);   // diagnostic
-    else hipLaunchKernelGGL((wgrad_q16_kernel<0>), grid, block, wg_dev::IMG_BYTES, (hipStream_t)stream, a);
-    IDL_HIP_TRY(hipGetLastError());
-    return IDL_OK;
+    return !noload ? launch_tiles<wgrad_q16_kernel<0>>(a, stream) : launch_tiles<wgrad_q16_kernel<1>>(a, stream) /* diagnostic */;
 }
 
 int idl_wgrad_rmsprop(const float *dy, const float *x, int m, int n_out, int n_in, float *grad, float *W, float *square_avg,
@@ -98,12 +87,7 @@ int idl_debug_wgrad_clock(const float *dy, const float *x, int m, int n_out, int
     a.m = m;
     a.tiles_m = n_out / wg_dev::TM;
     a.tiles = a.tiles_m * (n_in / wg_dev::TN);
-    if (const int rc = raise_lds_limit(); rc != IDL_OK) return rc;
-    const dim3 grid((unsigned)a.tiles), block(wg_dev::THREADS);
-    if (variant == 2) hipLaunchKernelGGL((wgrad_q16_clock_kernel<2>), grid, block, wg_dev::IMG_BYTES, (hipStream_t)stream, a, stamps);
-    else hipLaunchKernelGGL((wgrad_q16_clock_kernel<0>), grid, block, wg_dev::IMG_BYTES, (hipStream_t)stream, a, stamps);
-    IDL_HIP_TRY(hipGetLastError());
-    return IDL_OK;
+    return variant == 0 ? launch_tiles<wgrad_q16_clock_kernel<0>>(a, stream, stamps) : launch_tiles<wgrad_q16_clock_kernel<2>>(a, stream, stamps);
 }
 
 }  // extern "C"

@@ -43,13 +43,7 @@ extern "C" int idl_wgrad_rmsprop_xplanes(const void *dy_hi, const void *dy_lo, i
     a.tiles_m = n_out / TM; a.tiles = a.tiles_m * (n_in / TN);
     static const int wgp_dbg = idl::dev_env("wgp_dbg") ? atoi(idl::dev_env("wgp_dbg")) : 0;      // (timing ablations; wgrad_planes_device.h)
     a.dbg = wgp_dbg;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    IDL_HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        IDL_HIP_TRY(hipFuncSetAttribute((const void *)wgrad_dplanes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES + 16));
-        attr_set[dev] = true;
-    }
+    if (const int rc = idl::raise_dyn_lds<wgrad_dplanes_kernel>(LDS_BYTES + 16)) return rc;
     hipLaunchKernelGGL(wgrad_dplanes_kernel, dim3((unsigned)a.tiles), dim3(NT), LDS_BYTES + 16, (hipStream_t)stream, a);      // (+ 16: the tail's words)
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;

@@ -4,8 +4,8 @@
 One step of reference idelucs/models.py:117-133 takes one of five launch sequences (FusedLinearTrainer._form picks it once per step):
     planes       (default, n_clusters <= 48) the two big products on the fp16 matrix cores from two-plane operands:
                  idl_l1_planes_rows -> idl_reduce_mid_fwd_gather_planes (the partial sums and the forward middle in one launch) -> idl_nce_fused_iic_z
-                 -> idl_mid_bwd_gather_planes -> idl_wgrad_xplanes_rms (dW1 with RMSprop in the tiles' epilogue, the optimizer's tail on their loader
-                 waves); recorded, or with another ending: idl_l1_planes -> idl_reduce_parts_rms -> idl_mid_fwd_gather_planes -> ...
+                 -> idl_mid_bwd_gather -> idl_wgrad_xplanes_rms (dW1 with RMSprop in the tiles' epilogue, the optimizer's tail on their loader
+                 waves); recorded, or with another ending: idl_l1_planes -> idl_reduce_parts_rms -> idl_mid_fwd_gather -> ...
     planes_rows  the same for n_clusters > 48 (the fine-grained mode's 200 output units: joint + IIC core with z dP0, dW3 on idl_at_b)
     tiles        IDELUCS_PLANES=0 (or shapes the planes do not take): own fp32 tiles, idl_l1_fwd -> idl_mid_fwd_gather -> InfoNCE + IIC ->
                  idl_mid_bwd_gather -> idl_wgrad_rmsprop; the optimizer's tail rides in the NEXT step's layer-1 launch (idl_l1_fwd_rms)
@@ -81,10 +81,8 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-# the arguments of a launch that can assemble the next batch into bf.x (the store, the pair list, the destination) when it assembles none
-_NO_GATHER = (None, 0, 0, 0, None, 0, 0, None, None, None, None)
-# idl_reduce_parts_rms with no optimizer tail beside the sum: the 23 arguments _tail / _wg would fill (FusedLinearTrainer._reduce)
-_NO_TAIL = (0, None, None, None, None, None, None, None, None, 0, 0.0, 0.0, None, 0, -1, None, None, 0, 0, 0, 0, None, 0)
+# idl_mid_bwd_gather's dr1_hi, dr1_lo, dr1_scale, dr1_overflow_flag and z_dP0 when dr1 is the fp32 tensor alone and the kernel forms z dP0 itself
+_DR1_FP32 = (None,) * 5
 
 
 def _tile_per_cu(H1, F, cus):
@@ -279,14 +277,21 @@ class _LinearStepParts:
             self._bufs[m] = _Buffers(m, self.F, self.H1, self.H2, self.C, self.dev, shared=(self._shared_buffers or {}).get(m))
         return self._bufs[m]
 
-    def _next_batch(self, st, m):
-        """The arguments with which a middle launch assembles its share of the next batch: the store, the pair list and the offset."""
-        return (_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2, st.n_pairs, m // 2,
-                _p(st.mean), _p(st.scale), _p(st.inv_scale))
+    def _next_batch(self, st, m, *, y=None, planes=(None, None), flag=None, part=0, part_end=8, parts=8, base_add=None):
+        """The next batch's assembly by a launch (idl_next_batch_t): the store, the pair list and the offset -- ctl[1], which a middle launch
+        reads before the step has advanced it (base_add: m // 2 rows on) --, the destination y and / or the two planes with their overflow flag,
+        and the share [part, part_end) of `parts` this launch takes."""
+        return _lib.idl_next_batch_t(_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2 if base_add is None else base_add,
+                                     st.n_pairs, m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(y), _p(planes[0]), _p(planes[1]), _p(flag),
+                                     part, part_end, parts)
+
+    def _mid_fwd_tensors(self, bf, tr):
+        """The forward middle's weights, shape and dropout seed, and its outputs (the step counter goes between the two)."""
+        return (_p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3), bf.m, self.C, tr, self.seed), (_p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z))
 
     def _mid_fwd_args(self, bf, tr):
-        return (_p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3), bf.m, self.C, tr, self.seed, _p(self.ctl),
-                _p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z))
+        head, outs = self._mid_fwd_tensors(bf, tr)
+        return (*head, _p(self.ctl), *outs)
 
     def _mid_bwd_args(self, bf, tr, r1, gW3):
         _, gb1, _, gb2, _, gb3 = self.grads
@@ -304,10 +309,10 @@ class _LinearStepParts:
         mid_fwd + its share of the next batch (into bf.xs[1 - xi]), InfoNCE + IIC, mid_bwd + the rest of the next batch -- each through the
         launcher k."""
         m = bf.m
-        nxt = (*self._next_batch(st, m), _p(bf.xs[1 - xi]))
-        k(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *nxt, 0, GATHER_SPLIT, 8, _stream())
+        y = bf.xs[1 - xi]
+        k(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), self._next_batch(st, m, y=y, part_end=GATHER_SPLIT), _stream())
         launch_losses(k, bf, self.lamb, self.weight, self.out)
-        k(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *nxt, GATHER_SPLIT, 8, 8, 1, _stream())
+        k(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), 1, *_DR1_FP32, self._next_batch(st, m, y=y, part=GATHER_SPLIT), _stream())
 
     def _early(self, bf, st):
         """Whether the middle launches of a general step on bf assemble the next batch from st (else the step's last launch does, or nobody)."""
@@ -343,7 +348,7 @@ class _LinearStepParts:
             self._tiles_middle(k, bf, tr, st, xi, r1)
             return
         if early:       # (n_clusters > 48: ALL of the next batch's tiles ride in the mid-forward launch)
-            k(_L.idl_mid_fwd_gather, _p(r1), None, 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), _p(bf.xs[1 - xi]), 0, 8, 8, _stream())
+            k(_L.idl_mid_fwd_gather, _p(r1), None, 0, *self._mid_fwd_args(bf, tr), self._next_batch(st, m, y=bf.xs[1 - xi]), _stream())
         elif m % 16 == 0:   # ReLU/Dropout + Linear(512,64) + head in one MFMA kernel
             k(_L.idl_mid_fwd, _p(r1), *self._mid_fwd_args(bf, tr), _stream())
         else:
@@ -439,7 +444,6 @@ class FusedLinearTrainer(_LinearStepParts):
         self._pending = None                     # (buffers, parity) of the step whose tail has not run yet
         n = len(self.params)
         self._vp = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.square_avg])
-        self._sz_no_w1 = (ctypes.c_int64 * n)(*([0] + [p.numel() for p in self.params[1:]]))     # W1 updated by idl_wgrad_rmsprop
 
     def begin_voter(self, voter, keep_state=False):
         """Dropout stream of voter v: the Philox counter word the kernels take from ctl[0] (its low 32 bits) starts at
@@ -516,22 +520,24 @@ class FusedLinearTrainer(_LinearStepParts):
         else:
             self._step_general(bf, tr, batch_advance, st, xi)
 
-    def _tail(self, bf, sizes=None):
-        """The leading arguments of an optimizer launch: every tensor's RMSprop (sizes: self._sz, or without W1), the step loss."""
-        return (len(self.params), self._pp, self._gp, self._parts, self._vp, self._sz if sizes is None else sizes, _p(self.hyper),
-                _p(self.ctl), _p(bf.loss_rows), bf.m, 1.0 - self.weight, self.weight, _p(self.out))
+    def _tail(self, bf, *, skip=-1, advance=0, **wg):
+        """The optimizer's tail of the step on bf (idl_opt_tail_t): every tensor's RMSprop but tensor `skip`'s (0: W1, which dW1 tiles update), the
+        step loss, the batch offset's advance, and the in-launch dW2 tiles where the caller adds them (**self._wg(...))."""
+        return _lib.idl_opt_tail_t(count=len(self.params), params=self._pp, grads=self._gp, grad_parts=self._parts, square_avg=self._vp, sizes=self._sz,
+                                   hyper=_p(self.hyper), ctl=_p(self.ctl), loss_rows=_p(bf.loss_rows), loss_m=bf.m, w_nce=1.0 - self.weight,
+                                   w_iic=self.weight, out=_p(self.out), skip_index=skip, batch_advance=advance, **(wg or {"wg_index": -1}))
 
-    def _wg(self, bf, r1, transposed, advance):
-        """The trailing arguments of an optimizer launch: the dW2 = dlat^T r1 tiles, the batch offset's advance, the stream."""
-        m = bf.m
-        return (2, _p(bf.dlat), _p(r1), transposed, m, self.H2, self.H1, _p(self.grads[2]), advance, _stream())
+    def _wg(self, bf, r1, transposed):
+        """The dW2 = dlat^T r1 tiles of an optimizer launch: idl_opt_tail_t's wg_* fields."""
+        return dict(wg_index=2, wg_dy=_p(bf.dlat), wg_x=_p(r1), wg_x_transposed=transposed, wg_m=bf.m, wg_n_out=self.H2, wg_n_in=self.H1,
+                    wg_grad=_p(self.grads[2]))
 
     def _gw1(self):
         return _p(self.grads[0]) if self._keep_w1_grad else None
 
     def _reduce(self, part, m):
         """The sum of idl_l1_planes' eight K-slice partial sums, with no optimizer tail beside it."""
-        self._k(_L.idl_reduce_parts_rms, _p(part), self.H1 * m, _p(self.ctl), _p(self._ctl_snap), *_NO_TAIL, _stream())
+        self._k(_L.idl_reduce_parts_rms, _p(part), self.H1 * m, _p(self.ctl), _p(self._ctl_snap), None, _stream())
 
     def _check_x32(self, bf, xi):
         if getattr(bf, "_planes", None) is not None and not bf._planes["x32"][xi]:
@@ -585,12 +591,13 @@ class FusedLinearTrainer(_LinearStepParts):
         if cold:
             self._evict()
         self._k(_L.idl_l1_planes_rows if merged else _L.idl_l1_planes, _p(wh), _p(wl), F, _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, _p(part), _stream())
-        nxt = (None if plw else _p(bf.xs[1 - xi]), _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
+        nxt = dict(y=None if plw else bf.xs[1 - xi], planes=(pb["xh"][1 - xi], pb["xl"][1 - xi]), flag=flag)
         if merged:          # part[8][m][512] -> sums, ReLU / Dropout (r1), lat, head, softmax by workgroups of whole rows; the riders as in mid_fwd
             if cold:
                 self._evict()
-            _launch(_L.idl_reduce_mid_fwd_gather_planes, _p(part), _p(self.ctl), _p(self._ctl_snap), _p(r1), _p(self.b1),
-                    *self._mid_fwd_args(bf, tr)[:8], *self._mid_fwd_args(bf, tr)[9:], *self._next_batch(st, m), *nxt, 0, GATHER_SPLIT, 8, _stream())
+            head, outs = self._mid_fwd_tensors(bf, tr)
+            _launch(_L.idl_reduce_mid_fwd_gather_planes, _p(part), _p(self.ctl), _p(self._ctl_snap), _p(r1), _p(self.b1), *head, *outs,
+                    self._next_batch(st, m, part_end=GATHER_SPLIT, **nxt), _stream())
         else:
             if self._pending is not None and not rec:       # (a recording looks at no pending tail: a lockstep voter never leaves one)
                 self._tail_launch(*self._pending, red=(part, H1 * m))
@@ -598,11 +605,10 @@ class FusedLinearTrainer(_LinearStepParts):
                 self._reduce(part, m)
             if cold:
                 self._evict()
-            self._k(_L.idl_mid_fwd_gather_planes, _p(part), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
-                    0, GATHER_SPLIT, 8, _stream())
+            self._k(_L.idl_mid_fwd_gather, _p(part), _p(self.b1), 1, *self._mid_fwd_args(bf, tr), self._next_batch(st, m, part_end=GATHER_SPLIT, **nxt), _stream())
         launch_losses(self._k, bf, self.lamb, self.weight, self.out)
-        self._k(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), *self._next_batch(st, m), *nxt,
-                GATHER_SPLIT, 8, 8, 1, *self._dr1_planes_args(pb, plw), _stream())
+        self._k(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, self.grads[4]), 1, *self._dr1_planes_args(pb, plw, flag),
+                self._next_batch(st, m, part=GATHER_SPLIT, **nxt), _stream())
         if not rec:     # a recording assembled nothing: run_epoch records both parities between _gather (which clears valid[0]) and the split of
             #             batch 0, so a recording at parity 1 that set valid[0] would let the first step run on stale planes
             pb["valid"][1 - xi] = True
@@ -613,7 +619,7 @@ class FusedLinearTrainer(_LinearStepParts):
             if cold:
                 self._evict()
             self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, *w1, _p(wh), _p(wl), _p(flag),
-                    *self._tail(bf), 0, *self._wg(bf, r1, 1, m // 2))
+                    self._tail(bf, skip=0, advance=m // 2, **self._wg(bf, r1, 1)), _stream())
             return
         if plw:
             _launch(_L.idl_wgrad_rmsprop_xplanes, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, *w1, _p(self.hyper),
@@ -642,18 +648,17 @@ class FusedLinearTrainer(_LinearStepParts):
         self._reduce(part, m)
         if cold:
             self._evict()
-        nxt = (None, _p(pb["xh"][1 - xi]), _p(pb["xl"][1 - xi]), _p(flag))
+        nxt = dict(planes=(pb["xh"][1 - xi], pb["xl"][1 - xi]), flag=flag)
         # (the bias of Linear(F,512) is added here)
-        self._k(_L.idl_mid_fwd_gather_planes, _p(r1), _p(self.b1), 0, *self._mid_fwd_args(bf, tr), *self._next_batch(st, m), *nxt,
-                0, GATHER_SPLIT, 8, _stream())
+        self._k(_L.idl_mid_fwd_gather, _p(r1), _p(self.b1), 0, *self._mid_fwd_args(bf, tr), self._next_batch(st, m, part_end=GATHER_SPLIT, **nxt), _stream())
         # the core writes z dP0 up to 200 output units, a library product beyond them (lone only: _form records no wider head, and a
         # recording takes no library product)
         dz = rec or 48 < C <= 200
         launch_losses(self._k, bf, self.lamb, self.weight, self.out, dz=dz)
         if not dz:
             torch.mm(bf.z, bf.P0, out=bf.dzs)
-        self._k(_L.idl_mid_bwd_gather_planes, *self._mid_bwd_args(bf, tr, r1, None), *self._next_batch(st, m), *nxt,
-                GATHER_SPLIT, 8, 8, 0, *self._dr1_planes_args(pb, True, bf.dzs), _stream())
+        self._k(_L.idl_mid_bwd_gather, *self._mid_bwd_args(bf, tr, r1, None), 0, *self._dr1_planes_args(pb, True, flag, bf.dzs),
+                self._next_batch(st, m, part=GATHER_SPLIT, **nxt), _stream())
         if not rec:     # (a recording assembled nothing: _step_planes)
             pb["valid"][1 - xi] = True
             pb["x32"][1 - xi] = False
@@ -661,7 +666,7 @@ class FusedLinearTrainer(_LinearStepParts):
         if cold:
             self._evict()
         self._k(_L.idl_wgrad_xplanes_rms, *self._dy_planes_args(pb), _p(pb["xh"][xi]), _p(pb["xl"][xi]), F, m, H1, F, None if rec else self._gw1(),
-                _p(self.W1), _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), *self._tail(bf), 0, *self._wg(bf, r1, 0, m // 2))
+                _p(self.W1), _p(self.square_avg[0]), _p(wh), _p(wl), _p(flag), self._tail(bf, skip=0, advance=m // 2, **self._wg(bf, r1, 0)), _stream())
 
     def _step_tiles(self, bf, tr, st, xi, defer_tail):
         """n_clusters <= 48 on the fp32 tiles: a1^T = W1 x^T on own tiles (the previous step's optimizer tail rides in the same launch),
@@ -693,23 +698,21 @@ class FusedLinearTrainer(_LinearStepParts):
         # ---- dW1 on own MFMA tiles with RMSprop in their epilogue: at the head of the optimizer launch of a pipelined step, else a
         # launch of its own (a recorded step takes the tiles only inside its optimizer launch); dW1 as a GEMM where the tiles do not apply
         w1_tiles = bool(_L.idl_wgrad_supported(m, H1, F))
-        sizes = self._sz
+        skip = -1                               # the tensor the optimizer launch leaves out: W1 (0) once tiles have updated it
         if w1_tiles and not early and self._rec is None:
             _launch(_L.idl_wgrad_rmsprop, _p(bf.dr1), _p(x), m, H1, F, self._gw1(), _p(self.W1), _p(self.square_avg[0]), _p(self.hyper), _stream())
-            sizes = self._sz_no_w1
+            skip = 0
         elif not (w1_tiles and early):
             self._mm(bf.dr1.t(), x, self.grads[0])
         # ---- RMSprop (and advance the device-side step counter / batch offset)
         if w1_tiles and early:
-            k(_L.idl_wgrad_rmsprop_step, *self._tail(bf, sizes), 0, _p(bf.dr1), _p(x), m, H1, F, self._gw1(), *self._wg(bf, r1, int(both), m // 2))
+            k(_L.idl_wgrad_rmsprop_step, _p(bf.dr1), _p(x), m, H1, F, self._gw1(), self._tail(bf, skip=0, advance=m // 2, **self._wg(bf, r1, int(both))), _stream())
         elif early:     # no batch assembly here; the offset moves on at the end of the step
-            k(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, sizes), *_NO_GATHER, *self._wg(bf, r1, int(both), m // 2))
-        elif st is not None:
-            _launch(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, sizes), _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs,
-                    m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.x), *self._wg(bf, r1, 0, 0))
+            k(_L.idl_rmsprop_step, self._tail(bf, skip=skip, advance=m // 2, **self._wg(bf, r1, int(both))), None, _stream())
+        elif st is not None:    # the whole next batch into bf.x, at the offset the middle of the step has advanced
+            _launch(_L.idl_rmsprop_step, self._tail(bf, skip=skip, **self._wg(bf, r1, 0)), self._next_batch(st, m, y=bf.x, base_add=0), _stream())
         else:
-            _launch(_L.idl_rmsprop_step, len(self.params), self._pp, self._gp, self._parts, self._vp, sizes, _p(self.hyper), _p(self.ctl),
-                    batch_advance, _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out), _stream())
+            _launch(_L.idl_rmsprop_step, self._tail(bf, skip=skip, advance=batch_advance), None, _stream())
 
     def _w1_planes_of(self):
         """W1's planes and the planes' overflow flag, made on first use."""
@@ -718,11 +721,11 @@ class FusedLinearTrainer(_LinearStepParts):
                                torch.zeros(1, dtype=torch.int32, device=self.dev))
         return self._w1_planes
 
-    def _dr1_planes_args(self, pb, on, dzs=None):
-        """idl_mid_bwd_gather_planes' last arguments: dr1's planes and the words of their scale (or none of them: dr1 in fp32), and z dP0 as an
-        input (the step of n_clusters > 48)."""
+    def _dr1_planes_args(self, pb, on, flag, dzs=None):
+        """idl_mid_bwd_gather's arguments behind act1_transposed: dr1's planes and the words of their scale (or none of them: dr1 in fp32), the
+        overflow flag they raise (the word the next batch's planes raise too) and z dP0 as an input (the step of n_clusters > 48)."""
         pb["dr1_as_planes"] = bool(on)
-        return ((_p(pb["dh"]), _p(pb["dl"]), _p(self._dr1_scale)) if on else (None, None, None)) + (_p(dzs),)
+        return ((_p(pb["dh"]), _p(pb["dl"]), _p(self._dr1_scale)) if on else (None, None, None)) + (_p(flag), _p(dzs))
 
     def dr1_of(self, bf):
         """dr1 of the last step on these buffers as an fp32 tensor (tests): the step's own tensor, or -- where mid_bwd wrote it as planes only --
@@ -739,15 +742,15 @@ class FusedLinearTrainer(_LinearStepParts):
         """The optimizer's tail of the step that ran on (bf, xi) with the activations r1: dW2 tiles + RMSprop on every tensor but W1 + step
         loss + step counter -- behind the layer-1 tiles of the next step (l1 = (x, m, r1T) of THAT step), beside the workgroups that add up the next
         step's layer-1 partial sums (red), or as a launch of its own."""
-        wg = self._wg(bf, r1, 1, bf.m // 2)
+        tail = self._tail(bf, skip=0, advance=bf.m // 2, **self._wg(bf, r1, 1))       # (without W1: the tiles' own launch updated it)
         if red is not None:       # beside the workgroups that add up the next step's layer-1 partial sums (red = (part, elements of a slab))
             part, slab = red
-            _launch(_L.idl_reduce_parts_rms, _p(part), slab, None, None, *self._tail(bf), 0, *wg)
+            _launch(_L.idl_reduce_parts_rms, _p(part), slab, None, None, tail, _stream())
         elif l1 is not None:
             x, m1, r1T = l1
-            _launch(_L.idl_l1_fwd_rms, _p(self.W1), _p(x), m1, self.F, _p(r1T), *self._tail(bf), 0, *wg)
-        else:       # (sizes without W1: the tiles' own launch updated it)
-            _launch(_L.idl_rmsprop_step_gather_wgrad, *self._tail(bf, self._sz_no_w1), *_NO_GATHER, *wg)
+            _launch(_L.idl_l1_fwd_rms, _p(self.W1), _p(x), m1, self.F, _p(r1T), tail, _stream())
+        else:
+            _launch(_L.idl_rmsprop_step, tail, None, _stream())
         self._pending = None
 
     def flush_tail(self):

@@ -19,7 +19,7 @@ import ctypes
 import torch
 
 from ._lib import lib as _L
-from .fused import STEPS_PER_GRAPH, _LinearStepParts, _NO_GATHER, _launch, _mm_now, _p, _stream
+from .fused import STEPS_PER_GRAPH, _LinearStepParts, _launch, _mm_now, _p, _stream
 
 KIND_SGD, KIND_ADAM, KIND_RMSPROP = 1, 2, 3
 
@@ -93,9 +93,12 @@ class FusedLinearOptTrainer(_LinearStepParts):
         return bf.r1.view(self.H1, bf.m).t() if getattr(bf, "_r1_transposed", False) else bf.r1
 
     # ------------------------------------------------------------------ one step on a filled bf.xs[xi]
-    def _opt(self, bf, r1, transposed, advance, gather=_NO_GATHER):
-        """The step's last launch: dW2 = dlat^T r1 tiles + the optimizer on every tensor + step loss + counters (+ the next batch)."""
+    def _opt(self, bf, r1, transposed, advance, st=None):
+        """The step's last launch: dW2 = dlat^T r1 tiles + the optimizer on every tensor + step loss + counters (+ with st, the next batch from
+        that store into bf.x).  idl_opt_step_gather_wgrad takes the batch assembly as eleven positional arguments: all empty for none."""
         m = bf.m
+        gather = (None, 0, 0, 0, None, 0, 0, None, None, None, None) if st is None else (
+            _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs, m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.x))
         _launch(_L.idl_opt_step_gather_wgrad, self.kind, len(self.params), self._pp, self._gp, self._parts, self._s1p, self._s2p, self._sz,
                 _p(self.hyper64), _p(self.steps[self._tpar:]), _p(self.steps[1 - self._tpar:]), _p(self.ctl),
                 _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out), *gather,
@@ -133,8 +136,7 @@ class FusedLinearOptTrainer(_LinearStepParts):
         if early:
             self._opt(bf, r1, int(both), m // 2)
         elif st is not None:        # the offset moved mid-step: the last launch assembles the next batch into bf.x
-            self._opt(bf, r1, 0, 0, gather=(_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs, m // 2, _p(st.mean), _p(st.scale),
-                                            _p(st.inv_scale), _p(bf.x)))
+            self._opt(bf, r1, 0, 0, st=st)
         else:
             self._opt(bf, r1, 0, batch_advance)
 

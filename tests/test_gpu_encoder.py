@@ -239,8 +239,9 @@ def test_fused_rmsprop_kernel_exact(dev):
             gr.copy_(ref)
     from idelucs_amd import _lib
     from idelucs_amd.fused import _p, _stream
-    _lib.check(_lib.lib.idl_rmsprop_step(6, tr._pp, tr._gp, tr._parts, tr._vp, tr._sz, _p(tr.hyper), _p(tr.ctl), 7, None, 0, 0.0, 0.0, None,
-                                         _stream()))
+    tail = _lib.idl_opt_tail_t(count=6, params=tr._pp, grads=tr._gp, grad_parts=tr._parts, square_avg=tr._vp, sizes=tr._sz, hyper=_p(tr.hyper),
+                               ctl=_p(tr.ctl), skip_index=-1, wg_index=-1, batch_advance=7)
+    _lib.check(_lib.lib.idl_rmsprop_step(tail, None, _stream()))
     for n_, p in zip(names, tr.params):
         np.testing.assert_allclose(p.detach().cpu().numpy(), g[f"linear.step0.p.{n_}"], rtol=1e-5, atol=1e-7, err_msg=n_)
     assert tr.ctl.tolist() == [1, 7]
@@ -722,7 +723,7 @@ def test_transposed_layer1_activations(dev, m, C, train):
     on the row-major one, and leave the transposed image of the same masked activations behind."""
     import torch
     from idelucs_amd import _lib
-    from idelucs_amd.fused import _p, _stream
+    from idelucs_amd.fused import _p, _stream, _DR1_FP32
     L = _lib.lib
     torch.manual_seed(3 * m + C)
     a1 = torch.randn(m, 512, device=dev); b1 = torch.randn(512, device=dev) * 0.1
@@ -735,7 +736,7 @@ def test_transposed_layer1_activations(dev, m, C, train):
         f = torch.empty(m, 64, device=dev); inv = torch.empty(m, device=dev); r2 = torch.empty(m, 64, device=dev); z = torch.empty(m, C, device=dev)
         if tr_:
             _lib.check(L.idl_mid_fwd_gather(_p(buf), _p(b1), 1, _p(W2), _p(b2), _p(W3), _p(b3), m, C, train, 9, _p(ctl), _p(f), _p(inv), _p(r2), _p(z),
-                                            None, 0, 0, 0, None, None, 0, 0, 0, None, None, None, None, 0, 1, 1, _stream()))
+                                            None, _stream()))
         else:
             _lib.check(L.idl_mid_fwd(_p(buf), _p(W2), _p(b2), _p(W3), _p(b3), m, C, train, 9, _p(ctl), _p(f), _p(inv), _p(r2), _p(z), _stream()))
         torch.cuda.synchronize()
@@ -755,8 +756,7 @@ def test_transposed_layer1_activations(dev, m, C, train):
         w3 = torch.empty(parts, C, 64, device=dev)
         if tr_:
             _lib.check(L.idl_mid_bwd_gather(_p(z), _p(r2), _p(f), _p(inv), _p(G), gp, _p(dP0), _p(W3), _p(W2), _p(act), m, C, train, 1e-3,
-                                            _p(dlg), _p(dlat), _p(dr1), _p(p1), _p(p2), _p(p3), _p(w3),
-                                            None, 0, 0, 0, None, None, 0, 0, 0, None, None, None, None, 0, 1, 1, 1, _stream()))
+                                            _p(dlg), _p(dlat), _p(dr1), _p(p1), _p(p2), _p(p3), _p(w3), 1, *_DR1_FP32, None, _stream()))
         else:
             _lib.check(L.idl_mid_bwd(_p(z), _p(r2), _p(f), _p(inv), _p(G), gp, _p(dP0), _p(W3), _p(W2), _p(act), m, C, train, 1e-3,
                                      _p(dlg), _p(dlat), _p(dr1), _p(p1), _p(p2), _p(p3), _p(w3), None, 0, _stream()))
@@ -791,7 +791,7 @@ def test_own_layer1_forward_tiles(dev, m, F):
 
 @pytest.mark.parametrize("m,xt", [(1024, 0), (960, 0), (70, 0), (1024, 1), (960, 1), (72, 1)])
 def test_dw2_inside_the_optimizer_launch(dev, m, xt):
-    """idl_rmsprop_step_gather_wgrad: the gradient of one tensor computed in the launch as dy^T x (MFMA tiles) and applied
+    """idl_rmsprop_step: the gradient of one tensor computed in the launch as dy^T x (MFMA tiles) and applied
     there equals torch's product followed by the RMSprop formula; the other tensors are updated as by idl_rmsprop_step."""
     import ctypes
     import torch
@@ -810,10 +810,10 @@ def test_dw2_inside_the_optimizer_launch(dev, m, xt):
     ctl = torch.zeros(2, dtype=torch.int64, device=dev)
     gout = torch.empty(64, 512, device=dev)
     arr = lambda ts: (ctypes.c_void_p * 2)(*[t_.data_ptr() for t_ in ts])
-    _lib.check(L.idl_rmsprop_step_gather_wgrad(2, arr(W), arr(grads), (ctypes.c_int32 * 2)(1, 1), arr(V), (ctypes.c_int64 * 2)(64 * 512, 512),
-                                               _p(hyper), _p(ctl), None, 0, 0.0, 0.0, None,
-                                               None, 0, 0, 0, None, 0, 0, None, None, None, None,
-                                               0, _p(dy), _p(xarg), xt, m, 64, 512, _p(gout), 5, _stream()))
+    tail = _lib.idl_opt_tail_t(count=2, params=arr(W), grads=arr(grads), grad_parts=(ctypes.c_int32 * 2)(1, 1), square_avg=arr(V),
+                               sizes=(ctypes.c_int64 * 2)(64 * 512, 512), hyper=_p(hyper), ctl=_p(ctl), skip_index=-1, wg_index=0, wg_dy=_p(dy),
+                               wg_x=_p(xarg), wg_x_transposed=xt, wg_m=m, wg_n_out=64, wg_n_in=512, wg_grad=_p(gout), batch_advance=5)
+    _lib.check(L.idl_rmsprop_step(tail, None, _stream()))
     torch.cuda.synchronize()
     g64 = (dy.double().t() @ x.double())
     assert (gout.double() - g64).abs().max().item() <= 2e-6 * g64.abs().max().item() + 1e-5
@@ -974,7 +974,7 @@ def test_batch_assembly_riding_in_the_middle_launches_is_the_gather(dev):
     rows past the end of the pair list, which are left alone."""
     import torch
     from idelucs_amd import _lib, utils as U
-    from idelucs_amd.fused import _p, _stream
+    from idelucs_amd.fused import _p, _stream, _DR1_FP32
     L = _lib.lib
     torch.manual_seed(9)
     P, n, F, B, C, m = 4, 300, 1024, 512, 20, 1024
@@ -992,15 +992,17 @@ def test_batch_assembly_riding_in_the_middle_launches_is_the_gather(dev):
     a1 = torch.randn(m, 512, device=dev); W2 = torch.randn(64, 512, device=dev) * 0.06; b2 = torch.zeros(64, device=dev)
     W3 = torch.randn(C, 64, device=dev) * 0.2; b3 = torch.zeros(C, device=dev)
     f = torch.empty(m, 64, device=dev); inv = torch.empty(m, device=dev); r2 = torch.empty(m, 64, device=dev); z = torch.empty(m, C, device=dev)
-    g_args = lambda p0, p1: (_p(feats), n, F, n * F, _p(perm), _p(ctl[1:]), 512, n_pairs, B, _p(mean), _p(scale), _p(inv_scale), _p(got), p0, p1, 8)
+    next_batch = lambda p0, p1: _lib.idl_next_batch_t(feats=_p(feats), n=n, f=F, view_stride=n * F, pair_idx=_p(perm), base=_p(ctl[1:]), base_add=512,
+                                                      n_pairs=n_pairs, batch=B, mean=_p(mean), scale=_p(scale), inv_scale=_p(inv_scale), y=_p(got),
+                                                      part=p0, part_end=p1, parts=8)
     _lib.check(L.idl_mid_fwd_gather(_p(a1), None, 0, _p(W2), _p(b2), _p(W3), _p(b3), m, C, 1, 3, _p(ctl), _p(f), _p(inv), _p(r2), _p(z),
-                                    *g_args(0, 3), _stream()))
+                                    next_batch(0, 3), _stream()))
     parts = L.idl_col_sum_parts(); gp = L.idl_nce_fused_parts()
     G = torch.randn(gp, m, 64, device=dev); dP0 = torch.randn(C, C, device=dev); dP0 = dP0 + dP0.t()
     dlg = torch.empty(m, C, device=dev); dlat = torch.empty(m, 64, device=dev); dr1 = torch.empty(m, 512, device=dev)
     p1 = torch.empty(parts, 512, device=dev); p2 = torch.empty(parts, 64, device=dev); p3 = torch.empty(parts, C, device=dev)
     _lib.check(L.idl_mid_bwd_gather(_p(z), _p(r2), _p(f), _p(inv), _p(G), gp, _p(dP0), _p(W3), _p(W2), _p(a1), m, C, 1, 1e-3, _p(dlg), _p(dlat),
-                                    _p(dr1), _p(p1), _p(p2), _p(p3), None, *g_args(3, 8), 0, _stream()))
+                                    _p(dr1), _p(p1), _p(p2), _p(p3), None, 0, *_DR1_FP32, next_batch(3, 8), _stream()))
     torch.cuda.synchronize()
     live = n_pairs - (88 + 512)                               # rows of each half that exist in the pair list
     assert 0 < live < B

@@ -69,7 +69,7 @@ def test_riding_batch_assembly_is_the_gather_at_k8_width(dev):
     """test_batch_assembly_riding_in_the_middle_launches_is_the_gather at F = 65 536 (a batch of 2 x 64 rows): bit for bit."""
     import torch
     from idelucs_amd import _lib, utils as U
-    from idelucs_amd.fused import _p, _stream
+    from idelucs_amd.fused import _p, _stream, _DR1_FP32
     L = _lib.lib
     torch.manual_seed(9)
     P, n, F, B, C, m = 4, 40, F8, 64, 20, 128
@@ -85,15 +85,17 @@ def test_riding_batch_assembly_is_the_gather_at_k8_width(dev):
     a1 = torch.randn(m, 512, device=dev); W2 = torch.randn(64, 512, device=dev) * 0.06; b2 = torch.zeros(64, device=dev)
     W3 = torch.randn(C, 64, device=dev) * 0.2; b3 = torch.zeros(C, device=dev)
     f = torch.empty(m, 64, device=dev); inv = torch.empty(m, device=dev); r2 = torch.empty(m, 64, device=dev); z = torch.empty(m, C, device=dev)
-    g_args = lambda p0, p1: (_p(feats), n, F, n * F, _p(perm), _p(ctl[1:]), B, n_pairs, B, _p(mean), _p(scale), _p(inv_scale), _p(got), p0, p1, 8)
+    next_batch = lambda p0, p1: _lib.idl_next_batch_t(feats=_p(feats), n=n, f=F, view_stride=n * F, pair_idx=_p(perm), base=_p(ctl[1:]), base_add=B,
+                                                      n_pairs=n_pairs, batch=B, mean=_p(mean), scale=_p(scale), inv_scale=_p(inv_scale), y=_p(got),
+                                                      part=p0, part_end=p1, parts=8)
     _lib.check(L.idl_mid_fwd_gather(_p(a1), None, 0, _p(W2), _p(b2), _p(W3), _p(b3), m, C, 1, 3, _p(ctl), _p(f), _p(inv), _p(r2), _p(z),
-                                    *g_args(0, 3), _stream()))
+                                    next_batch(0, 3), _stream()))
     parts = L.idl_col_sum_parts(); gp = L.idl_nce_fused_parts()
     G = torch.randn(gp, m, 64, device=dev); dP0 = torch.randn(C, C, device=dev); dP0 = dP0 + dP0.t()
     dlg = torch.empty(m, C, device=dev); dlat = torch.empty(m, 64, device=dev); dr1 = torch.empty(m, 512, device=dev)
     p1 = torch.empty(parts, 512, device=dev); p2 = torch.empty(parts, 64, device=dev); p3 = torch.empty(parts, C, device=dev)
     _lib.check(L.idl_mid_bwd_gather(_p(z), _p(r2), _p(f), _p(inv), _p(G), gp, _p(dP0), _p(W3), _p(W2), _p(a1), m, C, 1, 1e-3, _p(dlg), _p(dlat),
-                                    _p(dr1), _p(p1), _p(p2), _p(p3), None, *g_args(3, 8), 0, _stream()))
+                                    _p(dr1), _p(p1), _p(p2), _p(p3), None, 0, *_DR1_FP32, next_batch(3, 8), _stream()))
     torch.cuda.synchronize()
     live = n_pairs - (8 + B)                                  # rows of each half that exist in the pair list
     assert 0 < live < B

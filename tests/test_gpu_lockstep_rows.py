@@ -207,7 +207,7 @@ def test_recorded_iic_core_dz_equals_three_launches(dev, C):
 
 @pytest.mark.parametrize("C", [49, 200])
 def test_recorded_mid_bwd_beyond_48_classes_equals_three_launches(dev, C):
-    """idl_mid_bwd_gather_planes recorded at C > 48 (the BIG body: W3 in dynamic LDS, dr1 as planes, z dP0 given), its spare workgroups assembling the
+    """idl_mid_bwd_gather recorded at C > 48 (the BIG body: W3 in dynamic LDS, dr1 as planes, z dP0 given), its spare workgroups assembling the
     second half of the next batch as planes: mid_bwd_big_batched_kernel against mid_bwd_kernel<true, true>.  Another form beyond 48 classes is refused."""
     import torch
     import test_gpu_encoder as E
@@ -232,17 +232,18 @@ def test_recorded_mid_bwd_beyond_48_classes_equals_three_launches(dev, C):
                     perm=torch.randperm(store.n_pairs, generator=g).to(dev), base=torch.zeros(1, dtype=torch.int64, device=dev))
 
     def args_of(b, dr1_planes=True):
-        nxt = (_p(store.feats), store.n, store.f, store.n * store.f, _p(b["perm"]), _p(b["base"]), m // 2, store.n_pairs, m // 2,
-               _p(store.mean), _p(store.scale), _p(store.inv_scale), None, _p(b["yh"]), _p(b["yl"]), _p(b["flag"]))
+        nxt = _lib.idl_next_batch_t(feats=_p(store.feats), n=store.n, f=store.f, view_stride=store.n * store.f, pair_idx=_p(b["perm"]), base=_p(b["base"]),
+                                    base_add=m // 2, n_pairs=store.n_pairs, batch=m // 2, mean=_p(store.mean), scale=_p(store.scale),
+                                    inv_scale=_p(store.inv_scale), y_hi=_p(b["yh"]), y_lo=_p(b["yl"]), overflow_flag=_p(b["flag"]), part=4, part_end=8, parts=8)
         dr1 = (None, _p(b["dh"]), _p(b["dl"]), _p(b["scale"])) if dr1_planes else (_p(b["act1"].new_empty(m, H1)), None, None, None)
         return (_p(b["z"]), _p(b["r2"]), _p(b["f"]), _p(b["inv"]), _p(b["G"]), parts, _p(b["P0"]), _p(b["W3"]), _p(b["W2"]), _p(b["act1"]), m, C, 1,
-                0.75 / (m * 0.85), _p(b["dlogits"]), _p(b["dlat"]), dr1[0], _p(b["gb1"]), _p(b["gb2"]), _p(b["gb3"]), None, *nxt, 4, 8, 8, 0,
-                *dr1[1:], _p(b["dzs"]), _stream())
+                0.75 / (m * 0.85), _p(b["dlogits"]), _p(b["dlat"]), dr1[0], _p(b["gb1"]), _p(b["gb2"]), _p(b["gb3"]), None, 0,
+                *dr1[1:], _p(b["flag"]), _p(b["dzs"]), nxt, _stream())
 
-    _recorded_equals_launched(dev, L.idl_mid_bwd_gather_planes, make, args_of, ["dlogits", "dlat", "dh", "dl", "scale", "gb1", "gb2", "gb3", "yh", "yl", "flag"])
+    _recorded_equals_launched(dev, L.idl_mid_bwd_gather, make, args_of, ["dlogits", "dlat", "dh", "dl", "scale", "gb1", "gb2", "gb3", "yh", "yl", "flag"])
     blob = torch.zeros(int(L.idl_plan_bytes()), dtype=torch.uint8)          # dr1 in fp32 beyond 48 classes: not a recordable form
     _lib.check(L.idl_plan_begin(ctypes.c_void_p(blob.data_ptr())))
-    rc = L.idl_mid_bwd_gather_planes(*args_of(make(0), dr1_planes=False))
+    rc = L.idl_mid_bwd_gather(*args_of(make(0), dr1_planes=False))
     L.idl_plan_end()
     assert rc != 0 and "beyond 48 classes" in _lib.last_error()
 

@@ -87,7 +87,7 @@ def test_layer1_product_from_planes_is_closer_to_float64_than_the_fp32_gemm(dev,
 
 def test_producers_write_the_planes_of_what_they_write(dev):
     """The dW1 tiles' epilogue (idl_wgrad_rmsprop_planes) leaves W1 exactly as idl_wgrad_rmsprop does, with planes that are idl_split_planes of
-    it; the batch-assembling workgroups of idl_mid_*_gather_planes leave the batch idl_gather_pairs_at assembles, with its planes."""
+    it; the batch-assembling workgroups of idl_mid_*_gather leave the batch idl_gather_pairs_at assembles, with its planes."""
     import torch
     from idelucs_amd import _lib
     L = _lib.lib
@@ -123,17 +123,20 @@ def test_producers_write_the_planes_of_what_they_write(dev):
     W3 = (torch.randn(C, H2, generator=g) / 8).to(dev); b3 = torch.zeros(C, device=dev)
     ctl = torch.zeros(2, dtype=torch.int64, device=dev)
     f = torch.empty(mm, H2, device=dev); inv = torch.empty(mm, device=dev); r2 = torch.empty(mm, H2, device=dev); z = torch.empty(mm, C, device=dev)
-    _lib.check(L.idl_mid_fwd_gather_planes(_p(a1), _p(b1), 1, _p(W2), _p(b2), _p(W3), _p(b3), mm, C, 1, ctypes.c_uint64(3), _p(ctl), _p(f), _p(inv), _p(r2), _p(z),
-                                           _p(feats), n, F, n * F, _p(perm), _p(base), 0, 2 * n, B, _p(mean), _p(scale), _p(inv_scale),
-                                           _p(y), _p(yh), _p(yl), _p(xflag), 0, 3, 8, _stream()))
+    def next_batch(p0, p1, **over):        # shares [p0, p1) of 8 of the batch at *base, as fp32 rows and as planes
+        fields = dict(feats=_p(feats), n=n, f=F, view_stride=n * F, pair_idx=_p(perm), base=_p(base), base_add=0, n_pairs=2 * n, batch=B, mean=_p(mean),
+                      scale=_p(scale), inv_scale=_p(inv_scale), y=_p(y), y_hi=_p(yh), y_lo=_p(yl), overflow_flag=_p(xflag), part=p0, part_end=p1, parts=8)
+        fields.update(over)
+        return _lib.idl_next_batch_t(**fields)
+
+    _lib.check(L.idl_mid_fwd_gather(_p(a1), _p(b1), 1, _p(W2), _p(b2), _p(W3), _p(b3), mm, C, 1, ctypes.c_uint64(3), _p(ctl), _p(f), _p(inv), _p(r2), _p(z),
+                                    next_batch(0, 3), _stream()))
     G = torch.randn(1, mm, H2, generator=g).to(dev) * 1e-2; dP0 = torch.randn(C, C, generator=g).to(dev) * 1e-2
     dlg = torch.empty(mm, C, device=dev); dlat = torch.empty(mm, H2, device=dev); dr1 = torch.empty(mm, 512, device=dev)
     parts = int(L.idl_col_sum_parts())
     p1 = torch.empty(parts, 512, device=dev); p2 = torch.empty(parts, H2, device=dev); p3 = torch.empty(parts, C, device=dev); pw3 = torch.empty(parts, C, H2, device=dev)
-    _lib.check(L.idl_mid_bwd_gather_planes(_p(z), _p(r2), _p(f), _p(inv), _p(G), 1, _p(dP0), _p(W3), _p(W2), _p(a1), mm, C, 1, 1e-3, _p(dlg), _p(dlat),
-                                           _p(dr1), _p(p1), _p(p2), _p(p3), _p(pw3),
-                                           _p(feats), n, F, n * F, _p(perm), _p(base), 0, 2 * n, B, _p(mean), _p(scale), _p(inv_scale),
-                                           _p(y), _p(yh), _p(yl), None, 3, 8, 8, 1, None, None, None, None, _stream()))
+    _lib.check(L.idl_mid_bwd_gather(_p(z), _p(r2), _p(f), _p(inv), _p(G), 1, _p(dP0), _p(W3), _p(W2), _p(a1), mm, C, 1, 1e-3, _p(dlg), _p(dlat),
+                                    _p(dr1), _p(p1), _p(p2), _p(p3), _p(pw3), 1, None, None, None, None, None, next_batch(3, 8, overflow_flag=None), _stream()))
     torch.cuda.synchronize()
     assert torch.equal(y, want) and xflag.item() == 0
     hi, lo, _, _ = _split(y, 0)
@@ -147,10 +150,9 @@ def test_producers_write_the_planes_of_what_they_write(dev):
 
     def bwd(G_, dP0_, planes):
         out = None if planes else torch.empty(mm, 512, device=dev)
-        tail = (_p(dh), _p(dl), _p(sc), None) if planes else (None, None, None, None)
-        _lib.check(L.idl_mid_bwd_gather_planes(_p(z), _p(r2), _p(f), _p(inv), _p(G_), 1, _p(dP0_), _p(W3), _p(W2), _p(a1), mm, C, 1, 1e-3, _p(dlg), _p(dlat),
-                                               _p(out), _p(p1), _p(p2), _p(p3), _p(pw3), None, 0, 0, 0, None, None, 0, 0, 0, None, None, None,
-                                               None, None, None, _p(dflag), 0, 0, 1, 1, *tail, _stream()))
+        dr1_planes = (_p(dh), _p(dl), _p(sc)) if planes else (None, None, None)
+        _lib.check(L.idl_mid_bwd_gather(_p(z), _p(r2), _p(f), _p(inv), _p(G_), 1, _p(dP0_), _p(W3), _p(W2), _p(a1), mm, C, 1, 1e-3, _p(dlg), _p(dlat),
+                                        _p(out), _p(p1), _p(p2), _p(p3), _p(pw3), 1, *dr1_planes, _p(dflag), None, None, _stream()))
         torch.cuda.synchronize()
         return out
 
@@ -190,9 +192,8 @@ def test_producers_write_the_planes_of_what_they_write(dev):
     # a column whose originals barely vary: the standardised entries leave the planes' range, are clamped there, and the flag says so
     scale2 = scale.clone(); scale2[7] = 1e-9
     inv2 = 1.0 / scale2
-    _lib.check(L.idl_mid_fwd_gather_planes(_p(a1), _p(b1), 1, _p(W2), _p(b2), _p(W3), _p(b3), mm, C, 1, ctypes.c_uint64(3), _p(ctl), _p(f), _p(inv), _p(r2), _p(z),
-                                           _p(feats), n, F, n * F, _p(perm), _p(base), 0, 2 * n, B, _p(mean), _p(scale2), _p(inv2),
-                                           None, _p(yh), _p(yl), _p(xflag), 0, 8, 8, _stream()))
+    _lib.check(L.idl_mid_fwd_gather(_p(a1), _p(b1), 1, _p(W2), _p(b2), _p(W3), _p(b3), mm, C, 1, ctypes.c_uint64(3), _p(ctl), _p(f), _p(inv), _p(r2), _p(z),
+                                    next_batch(0, 8, scale=_p(scale2), inv_scale=_p(inv2), y=None), _stream()))
     torch.cuda.synchronize()
     assert xflag.item() == 1
     col = yh.view(torch.float16)[:, 7].float()

@@ -80,11 +80,10 @@ def _small_store(dev, n, F, seed, views=2):
 @pytest.mark.parametrize("C", [2, 20, 48])
 def test_merged_launch_leaves_what_the_two_launches_leave(dev, m, C):
     """On the same partial sums: idl_reduce_mid_fwd_gather_planes' r1, f, inv, r2, z (and the next batch's planes its riders assemble, and the step counter's
-    copy) against idl_reduce_parts_rms + idl_mid_fwd_gather_planes -- dropout on and off, riders on and off; bit for bit.  With dropout on, r1 is also what
+    copy) against idl_reduce_parts_rms + idl_mid_fwd_gather -- dropout on and off, riders on and off; bit for bit.  With dropout on, r1 is also what
     the unfused idl_relu_dropout_fwd (layer id 1) leaves on the summed, biased activations.  The partial sums are only read."""
     import torch
     from idelucs_amd import _lib
-    from idelucs_amd.fused import _NO_TAIL
     L = _lib.lib
     F = 1024
     g = torch.Generator(device=dev); g.manual_seed(m + C)
@@ -104,11 +103,12 @@ def test_merged_launch_leaves_what_the_two_launches_leave(dev, m, C):
     def outs():
         return [torch.full(s, float("nan"), device=dev) for s in ((m, H2), (m,), (m, H2), (m, C))]
 
-    def gather_args(riders, xh, xl, flag):
+    def next_batch(riders, xh, xl, flag):
         if not riders:
-            return (None, 0, 0, 0, None, None, 0, 0, 0, None, None, None, None, None, None, None, 0, 0, 8)
-        return (_p(st.feats), st.n, st.f, st.n * st.f, _p(perm), _p(ctl[1:]), m // 2, st.n_pairs, m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale),
-                None, _p(xh), _p(xl), _p(flag), 0, 8, 8)
+            return None
+        return _lib.idl_next_batch_t(feats=_p(st.feats), n=st.n, f=st.f, view_stride=st.n * st.f, pair_idx=_p(perm), base=_p(ctl[1:]), base_add=m // 2,
+                                     n_pairs=st.n_pairs, batch=m // 2, mean=_p(st.mean), scale=_p(st.scale), inv_scale=_p(st.inv_scale),
+                                     y_hi=_p(xh), y_lo=_p(xl), overflow_flag=_p(flag), part=0, part_end=8, parts=8)
 
     for train in (0, 1):
         for riders in (0, 1):
@@ -117,9 +117,9 @@ def test_merged_launch_leaves_what_the_two_launches_leave(dev, m, C):
             f, inv, r2, z = outs()
             xh = torch.zeros((m, F), dtype=torch.int16, device=dev); xl = torch.zeros_like(xh)
             flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            _lib.check(L.idl_reduce_parts_rms(_p(part), H1 * m, _p(ctl), _p(snap), *_NO_TAIL, _stream()))
-            _lib.check(L.idl_mid_fwd_gather_planes(_p(part), _p(b1), 1, _p(W2), _p(b2), _p(W3), _p(b3), m, C, train, seed, _p(ctl), _p(f), _p(inv), _p(r2),
-                                                   _p(z), *gather_args(riders, xh, xl, flag), _stream()))
+            _lib.check(L.idl_reduce_parts_rms(_p(part), H1 * m, _p(ctl), _p(snap), None, _stream()))
+            _lib.check(L.idl_mid_fwd_gather(_p(part), _p(b1), 1, _p(W2), _p(b2), _p(W3), _p(b3), m, C, train, seed, _p(ctl), _p(f), _p(inv), _p(r2),
+                                            _p(z), next_batch(riders, xh, xl, flag), _stream()))
             torch.cuda.synchronize()
             want = (part[0].clone(), f, inv, r2, z, xh, xl, snap)
             assert all(torch.isfinite(t).all() for t in want[:5])
@@ -129,7 +129,7 @@ def test_merged_launch_leaves_what_the_two_launches_leave(dev, m, C):
             f_n, inv_n, r2_n, z_n = outs()
             xh_n = torch.zeros((m, F), dtype=torch.int16, device=dev); xl_n = torch.zeros_like(xh_n)
             _lib.check(L.idl_reduce_mid_fwd_gather_planes(_p(src), _p(ctl), _p(snap_n), _p(r1T), _p(b1), _p(W2), _p(b2), _p(W3), _p(b3), m, C, train,
-                                                          seed, _p(f_n), _p(inv_n), _p(r2_n), _p(z_n), *gather_args(riders, xh_n, xl_n, flag), _stream()))
+                                                          seed, _p(f_n), _p(inv_n), _p(r2_n), _p(z_n), next_batch(riders, xh_n, xl_n, flag), _stream()))
             torch.cuda.synchronize()
             got = (r1T, f_n, inv_n, r2_n, z_n, xh_n, xl_n, snap_n)
             for name, a_, b_ in zip(("r1", "f", "inv", "r2", "z", "x_hi", "x_lo", "step snapshot"), got, want):

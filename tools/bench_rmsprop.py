@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic: the optimizer launch of the fused step (idl_rmsprop_step_gather_wgrad with the in-launch dW2 tiles) timed alone,
+"""Diagnostic: the optimizer launch of the fused step (idl_rmsprop_step with the in-launch dW2 tiles) timed alone,
 back to back inside a HIP graph, at the cfg2 shapes -- with its operands cache-hot (same buffers every launch) and cache-cold
 (cycling through enough copies of W1 / v / g to exceed the 256 MB Infinity Cache)."""
 import os, sys, ctypes
@@ -20,12 +20,9 @@ def make():
 def launch(tr, bf, tiles=True):
     m = 1024
     if tiles:
-        _lib.check(L.idl_rmsprop_step_gather_wgrad(len(tr.params), tr._pp, tr._gp, tr._parts, tr._vp, tr._sz, _p(tr.hyper), _p(tr.ctl), _p(bf.loss_rows), m,
-                                                   0.75, 0.25, _p(tr.out), None, 0, 0, 0, None, 0, 0, None, None, None, None,
-                                                   2, _p(bf.dlat), _p(bf.r1), 1, m, 64, 512, _p(tr.grads[2]), m // 2, _stream()))
+        _lib.check(L.idl_rmsprop_step(tr._tail(bf, advance=m // 2, **tr._wg(bf, bf.r1, 1)), None, _stream()))
     else:
-        _lib.check(L.idl_rmsprop_step(len(tr.params), tr._pp, tr._gp, tr._parts, tr._vp, tr._sz, _p(tr.hyper), _p(tr.ctl), m // 2, _p(bf.loss_rows), m, 0.75, 0.25,
-                                      _p(tr.out), _stream()))
+        _lib.check(L.idl_rmsprop_step(tr._tail(bf, advance=m // 2), None, _stream()))
 def timeit(fn, n=200):
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
