@@ -245,6 +245,8 @@ def build_parser():
     # (no default: without the flag the namespace, the printed parameters and the results table have no such key)
     p.add_argument("--linear_step", action="store", type=str, default=argparse.SUPPRESS, choices=["autograd", "native"],
                    help="model_size='linear' with --optimizer SGD or Adam: train on torch autograd (the default) or on the native HIP step")
+    p.add_argument("--small_opt_step", action="store", type=str, default=argparse.SUPPRESS, choices=["autograd", "native"],
+                   help="model_size='small' with --optimizer SGD or Adam: train on torch autograd (the default) or on the native HIP step")
     p.add_argument("--rmsprop_momentum", action="store", type=str, default=argparse.SUPPRESS, choices=["ignore", "follow"],
                    help="--optimizer RMSprop with --scheduler Triangle: the native steps ignore the momentum CyclicLR writes into the "
                         "optimizer (the default) or follow it, as torch and the reference do")

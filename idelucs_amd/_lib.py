@@ -168,6 +168,9 @@ SIGNATURES = {
                                    _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "idl_small_wgrad_rms_momentum": (_int, [_vp] * 6 + [_vp] * 8 + [_int, _int, _int, _vp, _c.c_float, _c.c_float, _vp,
                                             _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    # (kind, params, grads, state1, state2, hyper, step_in, step_out, ctl, then idl_small_wgrad_rms's arguments from x on)
+    "idl_small_wgrad_opt": (_int, [_int] + [_vp] * 8 + [_vp] * 8 + [_int, _int, _int, _vp, _c.c_float, _c.c_float, _vp,
+                                   _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "idl_opt_step_gather_wgrad": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp,
                                          _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
                                          _int, _vp, _vp, _int, _int, _int, _int, _vp, _i64, _vp]),

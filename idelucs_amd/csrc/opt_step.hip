@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "opt_update_device.h"
 #include "scaler_device.h"
 #include "wave_ops.h"
 
@@ -34,7 +35,9 @@ constexpr int OPT_THREADS = 256;
 constexpr int OPT_UNROLL = 4;          // 16-byte elements per thread of the streaming update
 constexpr int OPT_MAX_BLOCKS = 1024;   // optimizer blocks of one tensor (beyond: a block walks on)
 constexpr int PART_CHUNK = 16;         // stacked partial gradients requested together
-constexpr int KIND_SGD = 1, KIND_ADAM = 2, KIND_RMSPROP = 3;
+// (Coef, make_coef and opt_update -- the arithmetic of the three optimizers -- are opt_update_device.h's: small_step.hip's last launch shares them)
+using idl_dev::Coef; using idl_dev::make_coef; using idl_dev::opt_update;
+using idl_dev::KIND_SGD; using idl_dev::KIND_ADAM; using idl_dev::KIND_RMSPROP;
 
 struct OptArgs {
     const float *loss_rows;   // optional step-loss assembly (models.py:128), as idl_rmsprop_step
@@ -57,68 +60,6 @@ struct OptArgs {
     int64_t *ctl;
     int64_t batch_advance;
 };
-
-// What one step's update needs, in the precision torch's kernels see it: the host-side Python floats rounded to fp32.
-template <int KIND>
-struct Coef {
-    float lr, mu, wd;                             // SGD; RMSprop: these and eps, b2 = alpha, b2w = 1 - alpha
-    float step, bc2s, eps, b1w, b2, b2w;          // Adam: lr / bc1, sqrt(bc2), eps, 1 - beta1, beta2, 1 - beta2
-};
-
-__device__ __forceinline__ double pow_int(double b, int64_t e)      // b^e, e >= 0 (wave-uniform: no divergence)
-{
-    double r = 1.0;
-    while (e > 0) {
-        if (e & 1) r *= b;
-        b *= b;
-        e >>= 1;
-    }
-    return r;
-}
-
-template <int KIND>
-__device__ __forceinline__ Coef<KIND> make_coef(const OptArgs &a)
-{
-    Coef<KIND> c{};
-    const double lr = a.hyper[0], h1 = a.hyper[1], h2 = a.hyper[2], eps = a.hyper[3], wd = a.hyper[4];
-    c.wd = (float)wd;
-    if constexpr (KIND == KIND_SGD) {
-        c.lr = (float)lr; c.mu = (float)h1;
-    } else if constexpr (KIND == KIND_RMSPROP) {
-        c.lr = (float)lr; c.mu = (float)h1; c.eps = (float)eps; c.b2 = (float)h2; c.b2w = (float)(1.0 - h2);
-    } else {
-        const int64_t t = *a.step_in + 1;
-        const double bc1 = 1.0 - pow_int(h1, t), bc2 = 1.0 - pow_int(h2, t);
-        c.step = (float)(lr / bc1); c.bc2s = (float)sqrt(bc2); c.eps = (float)eps;
-        c.b1w = (float)(1.0 - h1); c.b2 = (float)h2; c.b2w = (float)(1.0 - h2);
-    }
-    return c;
-}
-
-// torch.optim.SGD (momentum, weight decay; dampening 0, no nesterov): g' = g + wd p; buf = mu buf + g'; p -= lr buf -- a zero buf
-// makes the first step buf = g', torch's clone.  torch.optim.Adam (no amsgrad): m.lerp_(g, 1 - b1); v = b2 v + (1 - b2) g g;
-// p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).  torch.optim.RMSprop (not centered) with a momentum buffer: v = alpha v + (1 - alpha) g' g';
-// avg = sqrt(v) + eps; buf = mu buf + g' / avg; p -= lr buf (s1 = v, s2 = buf) -- mu = 0 makes buf = g' / avg, torch's addcdiv_ form.
-template <int KIND>
-__device__ __forceinline__ void opt_update(float g, float &p, float &s1, float &s2, const Coef<KIND> &c)
-{
-    g = fmaf(c.wd, p, g);
-    if constexpr (KIND == KIND_SGD) {
-        s1 = fmaf(c.mu, s1, g);
-        p = fmaf(-c.lr, s1, p);
-    } else if constexpr (KIND == KIND_RMSPROP) {
-        s1 = fmaf(c.b2w * g, g, c.b2 * s1);
-        const float avg = sqrtf(s1) + c.eps;
-        s2 = fmaf(c.mu, s2, g / avg);
-        p = fmaf(-c.lr, s2, p);
-    } else {
-        const float d = g - s1;
-        s1 = c.b1w < 0.5f ? fmaf(c.b1w, d, s1) : g - d * (1.0f - c.b1w);      // (Tensor.lerp_'s two forms)
-        s2 = fmaf(c.b2w * g, g, c.b2 * s2);
-        const float denom = sqrtf(s2) / c.bc2s + c.eps;
-        p = fmaf(-c.step, s1 / denom, p);
-    }
-}
 
 // One 16 x 16 tile of dy^T x: the four waves take a quarter of the contraction index each.  red: 1024 floats of LDS.
 // (The three operand loops and the LDS reduction are train_step.hip's wgrad_tile_rms without its look-ahead and spin forms, and the
@@ -199,7 +140,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(OptArgs a, int n_
         idl_dev::gather_block(g, (int64_t)b0, tix);
         return;
     }
-    const Coef<KIND> c = make_coef<KIND>(a);
+    const Coef<KIND> c = make_coef<KIND>(a.hyper, a.step_in);
     if (blk < a.wg_tiles) {
         __shared__ float red[1024];
         wgrad_tile<KIND>(a, blk, c, red, tix);

@@ -15,13 +15,14 @@
 //                     the four bias gradients as column sums with the update behind them, the step loss and step counter, and the
 //                     assembly of the NEXT batch into the other x buffer
 //                     (small_wgrad_rms_momentum: the same launch with torch's momentum buffer in the update, for RMSprop under
-//                     CyclicLR's cycle_momentum)
+//                     CyclicLR's cycle_momentum; small_wgrad_opt: the same launch with torch's SGD or Adam, models.py:89-92)
 //
 // Dropout: Philox4x32-10 keyed by the seed, counter (element group, layer, ctl[0]).  Layer ids 11 (after layer 1) and 12 (classifier)
 // are distinct from NetLinear's 1 and 2.  The layer-1 mask is recovered in the backward from the sign of a1 (kept and active <=> a1 > 0,
 // as NetLinear's kernels do); the classifier's acts on LeakyReLU outputs, which can be negative, so the backward draws it again.
 // No atomics anywhere: every sum runs in a fixed order, so a replayed graph reproduces eager launches bit for bit.
 #include "common.h"
+#include "opt_update_device.h"
 #include "philox_device.h"
 #include "scaler_device.h"
 #include "wave_ops.h"
@@ -612,6 +613,161 @@ __global__ __launch_bounds__(WG_THREADS) void small_wgrad_momentum_kernel(SmallW
     if (blk < a.gather_end) idl_dev::gather_block(a.gth, (int64_t)blk, (int)(threadIdx.x & 255));
 }
 
+// ---------------------------------------------------------------- the last launch with torch's SGD or Adam (models.py:89-92)
+// small_wgrad_opt_kernel<KIND>: the grid, roles and block order of small_wgrad_rms_kernel; the epilogue is opt_update<KIND> of
+// opt_update_device.h (KIND 1: SGD with momentum and weight decay, 2: Adam) on (g, p, state1, state2), its coefficients from a DEVICE
+// double[5] (make_coef: Adam's bias corrections in double).  Adam's step count is the optimizer's own, not ctl[0] (the dropout counter, which
+// restarts with every voter): every workgroup that updates reads *step_in, and the ONE thread that advances ctl[0] writes *step_in + 1 to
+// *step_out, a different word -- no word read in this launch is written in it (not all workgroups are resident before the first one ends).
+// (grad_tile_opt / bias_cols_opt are grad_tile / bias_cols with that epilogue: siblings, because the two RMSprop kernels' code is pinned
+//  as it is and moves with any change to the templates they instantiate -- a fix to the product loop is made in both.)
+struct OptBufs {
+    float *g1[4], *b1[4];             // SGD: momentum_buffer, Adam: exp_avg, of the four weights / the four biases
+    float *g2[4], *b2[4];             // Adam: exp_avg_sq
+    const double *hyper;
+    const int64_t *step_in;
+    int64_t *step_out;
+};
+
+template <int KIND>
+__device__ __forceinline__ void grad_tile_opt(const GradJob &j, int t, int m, const idl_dev::Coef<KIND> &c, float *lds, float *st1, float *st2)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l = lane & 15, q = lane >> 4;
+    const int i0 = (t / j.tiles_n) * WG_TM, j0 = (t % j.tiles_n) * WG_TN;
+    const int ks = (m + 3) / 4, s0 = wv * ks / WG_WAVES, s1 = (wv + 1) * ks / WG_WAVES;
+    int ia[WG_RB], jb[WG_CB];
+#pragma unroll
+    for (int rb = 0; rb < WG_RB; ++rb) ia[rb] = min(i0 + 16 * rb + l, j.M - 1);
+#pragma unroll
+    for (int cb = 0; cb < WG_CB; ++cb) jb[cb] = min(j0 + 16 * cb + l, j.N - 1);
+    f32x4_t acc[WG_RB][WG_CB];
+#pragma unroll
+    for (int rb = 0; rb < WG_RB; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < WG_CB; ++cb) acc[rb][cb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // (the product loop of grad_tile: clamped rows, a step past this wave's share contributes zero through A)
+    constexpr int U = 8;
+    for (int s = s0; s < s1; s += U) {
+        float av[U][WG_RB], bv[U][WG_CB];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int k = 4 * (s + u) + q;
+            const bool ok = s + u < s1 && k < m;
+            const int kr = min(k, m - 1);
+#pragma unroll
+            for (int rb = 0; rb < WG_RB; ++rb) {
+                const float t = j.dy[(int64_t)kr * j.M + ia[rb]];
+                av[u][rb] = ok ? t : 0.f;
+            }
+#pragma unroll
+            for (int cb = 0; cb < WG_CB; ++cb) bv[u][cb] = j.xin[(int64_t)kr * j.N + jb[cb]];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int rb = 0; rb < WG_RB; ++rb)
+#pragma unroll
+                for (int cb = 0; cb < WG_CB; ++cb) acc[rb][cb] = mfma(av[u][rb], bv[u][cb], acc[rb][cb]);
+    }
+    float (*red)[WG_RB * WG_CB][4][64] = (float (*)[WG_RB * WG_CB][4][64])lds;
+    if (wv > 0) {
+#pragma unroll
+        for (int rb = 0; rb < WG_RB; ++rb)
+#pragma unroll
+            for (int cb = 0; cb < WG_CB; ++cb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) red[wv - 1][rb * WG_CB + cb][r][lane] = acc[rb][cb][r];
+    }
+    __syncthreads();
+    if (wv != 0) return;
+#pragma unroll
+    for (int rb = 0; rb < WG_RB; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < WG_CB; ++cb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float g = acc[rb][cb][r];
+                for (int w = 0; w < WG_WAVES - 1; ++w) g += red[w][rb * WG_CB + cb][r][lane];
+                const int i = i0 + 16 * rb + 4 * q + r, jj = j0 + 16 * cb + l;       // C/D: row 4q + r, column l
+                if (i < j.M && jj < j.N) {
+                    const int64_t e = (int64_t)i * j.N + jj;
+                    if (j.grad != nullptr) j.grad[e] = g;
+                    float p = j.W[e], a = st1[e], b = 0.f;
+                    if constexpr (KIND == idl_dev::KIND_ADAM) b = st2[e];
+                    idl_dev::opt_update<KIND>(g, p, a, b, c);
+                    st1[e] = a;
+                    if constexpr (KIND == idl_dev::KIND_ADAM) st2[e] = b;
+                    j.W[e] = p;
+                }
+            }
+}
+
+template <int KIND>
+__device__ __forceinline__ void bias_cols_opt(const BiasJob &j, int t, int m, const idl_dev::Coef<KIND> &c, float *lds, float *st1, float *st2)
+{
+    const int tid = threadIdx.x, cc = tid & (BIAS_COLS - 1), rg = tid / BIAS_COLS;      // 8 row groups
+    const int col = t * BIAS_COLS + cc;
+    const int ccol = min(col, j.N - 1);
+    float s = 0.f;
+    for (int r = rg; r < m; r += WG_THREADS / BIAS_COLS) s += j.dy[(int64_t)r * j.N + ccol];
+    float (*red)[BIAS_COLS] = (float (*)[BIAS_COLS])lds;
+    red[rg][cc] = s;
+    __syncthreads();
+    if (rg != 0 || col >= j.N) return;
+    float g = red[0][cc];
+    for (int w = 1; w < WG_THREADS / BIAS_COLS; ++w) g += red[w][cc];
+    if (j.grad != nullptr) j.grad[col] = g;
+    float p = j.b[col], a = st1[col], b = 0.f;
+    if constexpr (KIND == idl_dev::KIND_ADAM) b = st2[col];
+    idl_dev::opt_update<KIND>(g, p, a, b, c);
+    st1[col] = a;
+    if constexpr (KIND == idl_dev::KIND_ADAM) st2[col] = b;
+    j.b[col] = p;
+}
+
+// (A kernel of its own for the reason small_wgrad_momentum_kernel is one.  a.hyper, RMSprop's float hyperparameters, is not read here;
+//  GradJob::v / BiasJob::v, RMSprop's running averages, are not either: the states come in ob.)
+template <int KIND>
+__global__ __launch_bounds__(WG_THREADS) void small_wgrad_opt_kernel(SmallWgArgs a, OptBufs ob)
+{
+    __shared__ float lds[(WG_WAVES - 1) * WG_RB * WG_CB * 256];
+    const int bid = (int)blockIdx.x;
+    if (bid < a.b_end[3]) {
+        const idl_dev::Coef<KIND> c = idl_dev::make_coef<KIND>(ob.hyper, ob.step_in);
+        int lo = 0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (bid < a.g_end[t]) { grad_tile_opt<KIND>(a.g[t], bid - lo, a.m, c, lds, ob.g1[t], ob.g2[t]); return; }
+            lo = a.g_end[t];
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (bid < a.b_end[t]) { bias_cols_opt<KIND>(a.b[t], bid - lo, a.m, c, lds, ob.b1[t], ob.b2[t]); return; }
+            lo = a.b_end[t];
+        }
+    }
+    if (bid == a.loss_blk) {
+        if (threadIdx.x >= 64) return;
+        const int lane = threadIdx.x;
+        float s = 0.f;
+        if (a.loss_rows != nullptr)
+            for (int r = lane; r < a.m; r += 64) s += a.loss_rows[r];
+        s = idl_dev::wave_sum_f(s);
+        if (lane == 0) {
+            if (a.loss_rows != nullptr) {
+                const float nce = s / (float)a.m;
+                const float tot = a.w_nce * nce + a.w_iic * a.out[3];
+                a.out[2] = nce; a.out[0] = tot; a.out[1] += tot;
+            }
+            a.ctl[0] += 1;
+            *ob.step_out = *ob.step_in + 1;
+        }
+        return;
+    }
+    const int blk = 2 * (bid - a.loss_blk - 1) + (int)(threadIdx.x >> 8);
+    if (blk < a.gather_end) idl_dev::gather_block(a.gth, (int64_t)blk, (int)(threadIdx.x & 255));
+}
+
 // ---------------------------------------------------------------- the two dropout masks of a step (tests)
 __global__ __launch_bounds__(256) void small_masks_kernel(uint64_t seed, uint32_t step, int m, float *mask1, float *mask2)
 {
@@ -662,18 +818,19 @@ int idl_small_mid_bwd(const float *z, const float *f, const float *inv, const fl
     return IDL_OK;
 }
 
-// The two forms of the step's last launch share everything but the optimizer's epilogue: momentum_buffer == NULL is idl_small_wgrad_rms.
+// The forms of the step's last launch share everything but the optimizer's epilogue: momentum_buffer == NULL is idl_small_wgrad_rms;
+// kind != 0 is idl_small_wgrad_opt (SGD / Adam: ob holds its states, hyperparameters and step words; square_avg and hyper are not looked at).
 static int small_wgrad_launch(float *const *params, float *const *grads, float *const *square_avg, float *const *momentum_buffer,
                               const float *hyper, int64_t *ctl,
                               const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
                               const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
                               float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
                               int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
-                              float *y_next, void *stream)
+                              float *y_next, void *stream, int kind = 0, const OptBufs *ob = nullptr)
 {
-    IDL_REQUIRE(params && square_avg && hyper && ctl && x && dr1 && a1 && da2 && a2 && dh && d2 && dlogits, "NULL buffer");
+    IDL_REQUIRE(params && (kind != 0 || (square_avg && hyper)) && ctl && x && dr1 && a1 && da2 && a2 && dh && d2 && dlogits, "NULL buffer");
     IDL_REQUIRE(m >= 1 && F >= 1 && C >= 1 && C <= SMAX_C, "small_wgrad_rms: m, F >= 1, n_clusters in 1..256");
-    for (int t = 0; t < 8; ++t) IDL_REQUIRE(params[t] && square_avg[t], "small_wgrad_rms: NULL parameter or running average");
+    for (int t = 0; t < 8; ++t) IDL_REQUIRE(params[t] && (kind != 0 || square_avg[t]), "small_wgrad_rms: NULL parameter or running average");
     IDL_REQUIRE(gather_batch == 0 || (feats && pair_idx && mean && scale && y_next && n >= 1 && f == F),
                 "small_wgrad_rms: the next batch needs the store, the permutation and an output of width F");
     SmallWgArgs a{};
@@ -683,13 +840,13 @@ static int small_wgrad_launch(float *const *params, float *const *grads, float *
     for (int t = 0; t < 4; ++t) {
         GradJob &j = a.g[t];
         j.dy = dys[t]; j.xin = xs[t]; j.M = Ms[t]; j.N = Ns[t]; j.tiles_n = (Ns[t] + WG_TN - 1) / WG_TN;
-        j.W = params[2 * t]; j.v = square_avg[2 * t]; j.grad = grads ? grads[2 * t] : nullptr;
+        j.W = params[2 * t]; j.v = kind == 0 ? square_avg[2 * t] : nullptr; j.grad = grads ? grads[2 * t] : nullptr;
         end += ((Ms[t] + WG_TM - 1) / WG_TM) * j.tiles_n;
         a.g_end[t] = end;
     }
     for (int t = 0; t < 4; ++t) {
         BiasJob &j = a.b[t];
-        j.dy = dys[t]; j.N = Ms[t]; j.b = params[2 * t + 1]; j.v = square_avg[2 * t + 1]; j.grad = grads ? grads[2 * t + 1] : nullptr;
+        j.dy = dys[t]; j.N = Ms[t]; j.b = params[2 * t + 1]; j.v = kind == 0 ? square_avg[2 * t + 1] : nullptr; j.grad = grads ? grads[2 * t + 1] : nullptr;
         end += (Ms[t] + BIAS_COLS - 1) / BIAS_COLS;
         a.b_end[t] = end;
     }
@@ -703,7 +860,11 @@ static int small_wgrad_launch(float *const *params, float *const *grads, float *
         a.gather_end = (int)idl_dev::gather_blocks(f, gather_batch);
         end += (a.gather_end + 1) / 2;
     }
-    if (momentum_buffer != nullptr) {
+    if (kind == idl_dev::KIND_SGD) {
+        hipLaunchKernelGGL(small_wgrad_opt_kernel<idl_dev::KIND_SGD>, dim3((unsigned)end), dim3(WG_THREADS), 0, (hipStream_t)stream, a, *ob);
+    } else if (kind == idl_dev::KIND_ADAM) {
+        hipLaunchKernelGGL(small_wgrad_opt_kernel<idl_dev::KIND_ADAM>, dim3((unsigned)end), dim3(WG_THREADS), 0, (hipStream_t)stream, a, *ob);
+    } else if (momentum_buffer != nullptr) {
         MomBufs mb{};
         for (int t = 0; t < 4; ++t) {
             IDL_REQUIRE(momentum_buffer[2 * t] && momentum_buffer[2 * t + 1], "small_wgrad_rms_momentum: NULL momentum buffer");
@@ -739,6 +900,36 @@ int idl_small_wgrad_rms_momentum(float *const *params, float *const *grads, floa
     IDL_REQUIRE(momentum_buffer != nullptr, "small_wgrad_rms_momentum: NULL momentum buffers");
     return small_wgrad_launch(params, grads, square_avg, momentum_buffer, hyper, ctl, x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows,
                               w_nce, w_iic, out, feats, n, f, view_stride, pair_idx, gather_batch, n_pairs, mean, scale, inv_scale, y_next, stream);
+}
+
+int idl_small_wgrad_opt(int kind, float *const *params, float *const *grads, float *const *state1, float *const *state2,
+                        const double *hyper, const int64_t *step_in, int64_t *step_out, int64_t *ctl,
+                        const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
+                        const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
+                        float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
+                        int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
+                        float *y_next, void *stream)
+{
+    IDL_REQUIRE(kind == idl_dev::KIND_SGD || kind == idl_dev::KIND_ADAM, "small_wgrad_opt: kind 1 (SGD with momentum) or 2 (Adam)");
+    IDL_REQUIRE(state1 != nullptr && (kind == idl_dev::KIND_SGD || state2 != nullptr),
+                "small_wgrad_opt: SGD needs momentum_buffer (state1), Adam exp_avg (state1) and exp_avg_sq (state2)");
+    IDL_REQUIRE(hyper != nullptr && (((uintptr_t)hyper) & 7u) == 0, "small_wgrad_opt: hyper is a device double[5]");
+    IDL_REQUIRE(step_in && step_out && step_in != step_out, "small_wgrad_opt: the step count is read from one word and written to another");
+    IDL_REQUIRE(ctl == nullptr || ((const void *)step_in != (const void *)ctl && (const void *)step_in != (const void *)(ctl + 1)),
+                "small_wgrad_opt: step_in must not be a word this launch writes");
+    OptBufs ob{};
+    for (int t = 0; t < 4; ++t) {
+        ob.g1[t] = state1[2 * t]; ob.b1[t] = state1[2 * t + 1];
+        IDL_REQUIRE(ob.g1[t] && ob.b1[t], "small_wgrad_opt: NULL entry in state1");
+        if (kind == idl_dev::KIND_ADAM) {
+            ob.g2[t] = state2[2 * t]; ob.b2[t] = state2[2 * t + 1];
+            IDL_REQUIRE(ob.g2[t] && ob.b2[t], "small_wgrad_opt: NULL entry in state2");
+        }
+    }
+    ob.hyper = hyper; ob.step_in = step_in; ob.step_out = step_out;
+    return small_wgrad_launch(params, grads, nullptr, nullptr, nullptr, ctl, x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows, w_nce,
+                              w_iic, out, feats, n, f, view_stride, pair_idx, gather_batch, n_pairs, mean, scale, inv_scale, y_next, stream,
+                              kind, &ob);
 }
 
 int idl_small_dropout_masks(uint64_t seed, int64_t step, int m, float *mask1, float *mask2, void *stream)

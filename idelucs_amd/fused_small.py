@@ -12,7 +12,8 @@ even number of steps (one stream, no forked branches); the steps that do not fil
 The parameters are the nn.Parameters of model.net (state_dict / predict / weights_init unchanged); RMSprop state lives here.
 FusedSmallTrainer(..., momentum=mu) is the momentum form: torch's RMSprop with a momentum_buffer, which is what the Triangle
 scheduler's CyclicLR makes of the reference's optimizer (models.py:87-88, 99); its last launch is idl_small_wgrad_rms_momentum and
-set_momentum() follows the scheduler beside set_lr().
+set_momentum() follows the scheduler beside set_lr().  FusedSmallOptTrainer (below) is the step with torch's SGD or Adam
+(models.py:89-92): the same five launches and idl_small_wgrad_opt as the last one.
 """
 import ctypes
 
@@ -61,6 +62,18 @@ class _SmallBuffers:
 class FusedSmallTrainer:
     def __init__(self, net, lr, weight, lamb, weight_decay=0.01, alpha=0.99, eps=1e-8, seed=0, momentum=None):
         """momentum: None -> the momentum-free step; a number -> the momentum form (momentum_buffer per tensor, set_momentum())."""
+        self._init_network(net, weight, lamb, seed)
+        self.square_avg = [torch.zeros_like(p) for p in self.params]
+        self.with_momentum = momentum is not None
+        self.momentum_buffer = [torch.zeros_like(p) for p in self.params] if self.with_momentum else []
+        self.hyper = torch.tensor([lr, alpha, eps, weight_decay, 1.0 - alpha] + ([float(momentum)] if self.with_momentum else []),
+                                  dtype=torch.float32, device=self.dev)
+        n = len(self.params)
+        self._vp = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.square_avg])
+        self._mp = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.momentum_buffer]) if self.with_momentum else None
+
+    def _init_network(self, net, weight, lamb, seed):
+        """Everything of the trainer that does not depend on the optimizer: the parameters, the gradients, the counters, the buffers."""
         lin1, lin2, lini, linc = net.layers[0], net.layers[3], net.instance, net.classifier[1]
         self.net = net
         self.params = [lin1.weight, lin1.bias, lin2.weight, lin2.bias, lini.weight, lini.bias, linc.weight, linc.bias]
@@ -70,21 +83,13 @@ class FusedSmallTrainer:
                 or self.C > MAX_C:
             raise ValueError(f"FusedSmallTrainer needs myNet (400 -> 128 -> 64 / C) and n_clusters <= {MAX_C}")
         self.grads = [torch.zeros_like(p) for p in self.params]
-        self.square_avg = [torch.zeros_like(p) for p in self.params]
         self.weight, self.lamb, self.seed = float(weight), float(lamb), int(seed) & (2 ** 64 - 1)
-        self.with_momentum = momentum is not None
-        self.momentum_buffer = [torch.zeros_like(p) for p in self.params] if self.with_momentum else []
-        self.hyper = torch.tensor([lr, alpha, eps, weight_decay, 1.0 - alpha] + ([float(momentum)] if self.with_momentum else []),
-                                  dtype=torch.float32, device=self.dev)
         self.ctl = torch.zeros(2, dtype=torch.int64, device=self.dev)        # [step counter, batch offset]
         self.out = torch.zeros(4, dtype=torch.float32, device=self.dev)      # [step loss, running sum, nce, iic]
         self._bufs = {}
         self._graphs = {}
         self._perm = None
-        n = len(self.params)
-        self._pp = (ctypes.c_void_p * n)(*[p.data_ptr() for p in self.params])
-        self._vp = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.square_avg])
-        self._mp = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.momentum_buffer]) if self.with_momentum else None
+        self._pp = (ctypes.c_void_p * len(self.params))(*[p.data_ptr() for p in self.params])
         self.keep_grads = False         # True: the step also writes dW1 to grads[0] (tests; the small tensors' gradients are always kept)
 
     def _gp(self):
@@ -152,12 +157,20 @@ class FusedSmallTrainer:
         st = next_from
         gth = ((_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), m // 2, st.n_pairs, _p(st.mean), _p(st.scale), _p(st.inv_scale),
                 _p(bf.xs[1 - xi])) if st is not None else (None, 0, 0, 0, None, 0, 0, None, None, None, None))
-        tail = (_p(self.hyper), _p(self.ctl), _p(x), _p(bf.dr1), _p(bf.a1), _p(bf.da2), _p(bf.a2), _p(bf.dh), _p(bf.d2), _p(bf.dlogits), m, F, C,
-                _p(bf.loss_rows), 1.0 - self.weight, self.weight, _p(self.out), *gth, _stream())
+        self._last_launch((_p(x), _p(bf.dr1), _p(bf.a1), _p(bf.da2), _p(bf.a2), _p(bf.dh), _p(bf.d2), _p(bf.dlogits), m, F, C,
+                           _p(bf.loss_rows), 1.0 - self.weight, self.weight, _p(self.out), *gth, _stream()))
+
+    def _last_launch(self, tail):
+        """The step's last launch: every gradient with the optimizer's update in its epilogue, the step loss, the step counter, the next batch.
+        tail: the arguments every form of it takes from `x` on."""
         if self.with_momentum:
-            chk(_L.idl_small_wgrad_rms_momentum(self._pp, self._gp(), self._vp, self._mp, *tail))
+            _lib.check(_L.idl_small_wgrad_rms_momentum(self._pp, self._gp(), self._vp, self._mp, _p(self.hyper), _p(self.ctl), *tail))
         else:
-            chk(_L.idl_small_wgrad_rms(self._pp, self._gp(), self._vp, *tail))
+            _lib.check(_L.idl_small_wgrad_rms(self._pp, self._gp(), self._vp, _p(self.hyper), _p(self.ctl), *tail))
+
+    def _graph_key_extra(self):
+        """What a captured graph bakes in besides the store's addresses and the batch shape (a tuple; nothing here)."""
+        return ()
 
     def _gather(self, store, bf, b):
         _lib.check(_L.idl_gather_pairs_at(_p(store.feats), store.n, store.f, store.n * store.f, _p(self._perm), _p(self.ctl[1:]),
@@ -185,15 +198,17 @@ class FusedSmallTrainer:
             per = min(STEPS_PER_GRAPH, n_full // 2 * 2)
             if use_graph and per >= 2:
                 # every address the captured launches bake in is part of the key (a store refitted in place keeps its graph)
-                key = (2 * batch_sz, store.feats.data_ptr(), store.mean.data_ptr(), store.scale.data_ptr(), store.inv_scale.data_ptr(),
+                base = (2 * batch_sz, store.feats.data_ptr(), store.mean.data_ptr(), store.scale.data_ptr(), store.inv_scale.data_ptr(),
                        self._perm.data_ptr(), store.n, store.f, store.n_pairs, per, self.keep_grads)
+                key = base + self._graph_key_extra()
                 g = self._graphs.get(key)
                 if g is None:
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
                         for i in range(per):
                             self.step_on_batch(bf, xi=i % 2, next_from=store)
-                    self._graphs = {key: g}           # one store at a time
+                    self._graphs = {k_: v for k_, v in self._graphs.items() if k_[:len(base)] == base}      # one store at a time
+                    self._graphs[key] = g
                 for _ in range(n_full // per):
                     g.replay()
                 done = n_full // per * per
@@ -204,3 +219,79 @@ class FusedSmallTrainer:
             self._gather(store, bf, rem)
             self.step_on_batch(bf)
         return self.out[1], n_full + (1 if rem else 0)
+
+
+KIND_SGD, KIND_ADAM = 1, 2
+
+
+class FusedSmallOptTrainer(FusedSmallTrainer):
+    """The step of FusedSmallTrainer with torch.optim.SGD or torch.optim.Adam (reference models.py:89-92) in its last launch,
+    idl_small_wgrad_opt.  Opt-in: IID_model(args) with args['small_opt_step'] = 'native' (CLI: --small_opt_step native).  Nothing in the
+    five launches in front of it knows which optimizer follows; buffers, dropout streams, dropout_masks(), keep_grads, partial batches and
+    the epoch loop are inherited.  SGD keeps momentum_buffer per tensor, Adam exp_avg and exp_avg_sq plus its step count in two words that
+    swap roles from step to step (the launch reads one and writes the other).  The hyperparameters are copied from the torch optimizer's
+    group before every epoch (sync_hyper): the schedulers keep acting on that object, CyclicLR on momentum / beta1 as well as the rate."""
+
+    def __init__(self, net, optimizer, weight, lamb, seed=0):
+        """optimizer: the torch.optim.SGD / torch.optim.Adam object whose first group holds the hyperparameters (its state is not used)."""
+        if isinstance(optimizer, torch.optim.SGD):
+            self.kind = KIND_SGD
+        elif isinstance(optimizer, torch.optim.Adam):
+            self.kind = KIND_ADAM
+        else:
+            raise ValueError("FusedSmallOptTrainer needs a torch.optim.SGD or torch.optim.Adam object")
+        grp = optimizer.param_groups[0]
+        if grp.get('nesterov') or grp.get('dampening') or grp.get('amsgrad') or grp.get('maximize'):
+            raise ValueError("FusedSmallOptTrainer: nesterov, dampening, amsgrad and maximize are not supported")
+        self.optimizer = optimizer
+        self._init_network(net, weight, lamb, seed)
+        self.state1 = [torch.zeros_like(p) for p in self.params]             # SGD: momentum_buffer; Adam: exp_avg
+        self.state2 = [torch.zeros_like(p) for p in self.params] if self.kind == KIND_ADAM else []      # Adam: exp_avg_sq
+        self.hyper64 = torch.zeros(5, dtype=torch.float64, device=self.dev)      # [lr, momentum | beta1, beta2, eps, weight_decay]
+        self._hyper_host = [None] * 5
+        self.steps = torch.zeros(2, dtype=torch.int64, device=self.dev)          # the optimizer's step count: steps[_tpar] is current
+        self._tpar = 0
+        n = len(self.params)
+        self._s1p = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.state1])
+        self._s2p = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.state2]) if self.state2 else None
+        self.sync_hyper()
+
+    def state_tensors(self):
+        return list(self.state1) + list(self.state2)
+
+    def step_count(self):
+        """The optimizer's step count (waits for the device)."""
+        return int(self.steps[self._tpar].item())
+
+    def begin_voter(self, voter, keep_state=False):
+        """Dropout stream of voter v as FusedSmallTrainer.begin_voter sets it.  keep_state: the previous voter's optimizer state stays
+        (IDELUCS_VOTER_STATE=carry); the step count is part of it."""
+        self.ctl[0:1].fill_((int(voter) & 0xFF) << 24)
+        if keep_state:
+            return
+        for v in self.state_tensors():
+            v.zero_()
+        self.steps.zero_()
+        self._tpar = 0
+
+    def sync_hyper(self):
+        """Copy the torch optimizer's current group to the device (before every epoch: the schedulers act on that object)."""
+        grp = self.optimizer.param_groups[0]
+        if self.kind == KIND_SGD:
+            vals = [grp['lr'], grp['momentum'], 0.0, 0.0, grp['weight_decay']]
+        else:
+            vals = [grp['lr'], grp['betas'][0], grp['betas'][1], grp['eps'], grp['weight_decay']]
+        for i, v in enumerate(vals):
+            v = float(v)
+            if v != self._hyper_host[i]:
+                self.hyper64[i:i + 1].fill_(v)    # (fill_ on a view: no host-to-device copy from pageable memory)
+                self._hyper_host[i] = v
+
+    def _last_launch(self, tail):
+        _lib.check(_L.idl_small_wgrad_opt(self.kind, self._pp, self._gp(), self._s1p, self._s2p, _p(self.hyper64),
+                                          _p(self.steps[self._tpar:]), _p(self.steps[1 - self._tpar:]), _p(self.ctl), *tail))
+        self._tpar ^= 1
+
+    def _graph_key_extra(self):
+        """The role of the two step words: an epoch with an odd number of steps flips it, and a captured graph bakes their addresses."""
+        return (self._tpar,)

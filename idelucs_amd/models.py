@@ -115,6 +115,10 @@ class IID_model():
         # model_size='small': autograd (the default) or, opt-in, the explicit step of fused_small.FusedSmallTrainer
         self._small = None
         self._use_small = args['model_size'] == 'small' and self._small_step(args) == 'native'
+        # ... with SGD or Adam: autograd (the default) or, opt-in, the same step with fused_small.FusedSmallOptTrainer's last launch
+        self._small_opt = (args['model_size'] == 'small' and args['optimizer'] in ('SGD', 'Adam')
+                           and self._small_opt_step(args) == 'native')
+        self._use_small = self._use_small or self._small_opt
         # NetLinear with SGD or Adam: autograd (the default) or, opt-in, the explicit step of fused_opt.FusedLinearOptTrainer
         self._linopt = None
         self._use_linopt = (args['model_size'] == 'linear' and args['optimizer'] in ('SGD', 'Adam')
@@ -131,7 +135,21 @@ class IID_model():
             raise ValueError(f"small_step must be 'autograd' or 'native', not {mode!r}")
         if mode == 'native' and (args['optimizer'] != 'RMSprop' or not 1 <= args['n_clusters'] <= 256 or not 1 <= args['batch_sz'] <= 1024):
             raise ValueError("small_step='native' supports optimizer='RMSprop', n_clusters in 1..256 and batch_sz in 1..1024 "
-                             f"(got optimizer={args['optimizer']!r}, n_clusters={args['n_clusters']}, batch_sz={args['batch_sz']})")
+                             f"(got optimizer={args['optimizer']!r}, n_clusters={args['n_clusters']}, batch_sz={args['batch_sz']}); "
+                             "the native step with optimizer='SGD' or 'Adam' is small_opt_step='native'")
+        return mode
+
+    @staticmethod
+    def _small_opt_step(args):
+        """args['small_opt_step'] of a model_size='small' model trained with SGD or Adam: 'autograd' (absent or None) or 'native'
+        (n_clusters <= 256, batch_sz <= 1024); anything else raises ValueError.  (RMSprop's key is small_step; model_size='linear': the
+        key is not looked at.)"""
+        mode = args.get('small_opt_step') or 'autograd'
+        if mode not in ('autograd', 'native'):
+            raise ValueError(f"small_opt_step must be 'autograd' or 'native', not {mode!r}")
+        if mode == 'native' and (not 1 <= args['n_clusters'] <= 256 or not 1 <= args['batch_sz'] <= 1024):
+            raise ValueError("small_opt_step='native' supports n_clusters in 1..256 and batch_sz in 1..1024 "
+                             f"(got n_clusters={args['n_clusters']}, batch_sz={args['batch_sz']})")
         return mode
 
     @staticmethod
@@ -251,6 +269,14 @@ class IID_model():
                 self._fused.begin_voter(self._voter)
             self._fused.set_lr(self.optimizer.param_groups[0]['lr'])       # schedulers act on the torch optimizer
             total, n_batches = self._fused.run_epoch(st, self.batch_sz, generator=self._gen)
+            return total / (n_batches - 1)                                  # models.py:135 quirk (divide by last index)
+        if self._small_opt:
+            if self._small is None:
+                from .fused_small import FusedSmallOptTrainer
+                self._small = FusedSmallOptTrainer(self.net, self.optimizer, self.weight, self.l, seed=self.seed)
+                self._small.begin_voter(self._voter)
+            self._small.sync_hyper()                                        # schedulers act on the torch optimizer: rate, momentum / beta1
+            total, n_batches = self._small.run_epoch(st, self.batch_sz, generator=self._gen)
             return total / (n_batches - 1)                                  # models.py:135 quirk (divide by last index)
         if self._use_small:
             if self._small is None:

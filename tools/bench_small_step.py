@@ -12,7 +12,11 @@ matrix peak.
 rmsprop_momentum='follow' trains under the Triangle scheduler), whether the native median clears the autograd median by more than the
 autograd rounds' own spread, and beside them the default momentum-free native step in the same rounds.
 
-Usage:  python tools/bench_small_step.py [--rounds R] [--steps S] [--momentum MU] [--out FILE]
+--optimizer SGD|Adam: the optimizer objects of reference models.py:89-92 in both forms (torch's SGD(momentum 0.9, weight_decay 0.01) /
+Adam under autograd; fused_small.FusedSmallOptTrainer, small_opt_step='native'), the same acceptance figure, and the default RMSprop
+native step beside them in the same rounds.
+
+Usage:  python tools/bench_small_step.py [--rounds R] [--steps S] [--momentum MU | --optimizer SGD|Adam] [--out FILE]
 """
 import argparse
 import json
@@ -56,14 +60,17 @@ def main():
     ap.add_argument("--clusters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--momentum", type=float, default=None)
+    ap.add_argument("--optimizer", choices=["SGD", "Adam"], default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.optimizer is not None and a.momentum is not None:
+        ap.error("--momentum is RMSprop's: not with --optimizer")
     import numpy as np
     import torch
     from torch.profiler import profile, ProfilerActivity
     from idelucs_amd import _lib, models
     from idelucs_amd.PytorchUtils import myNet
-    from idelucs_amd.fused_small import FusedSmallTrainer
+    from idelucs_amd.fused_small import FusedSmallOptTrainer, FusedSmallTrainer
     _lib.require_gpu()
     dev = torch.device("cuda")
     k, C, B = 6, a.clusters, a.batch
@@ -74,20 +81,30 @@ def main():
     torch.manual_seed(0)
     net_a = myNet(F, C).to(dev)
     net_a.apply(models.weights_init)
-    opt = torch.optim.RMSprop(net_a.parameters(), lr=1e-3, weight_decay=0.01, momentum=a.momentum or 0.0)
+
+    def optimizer(params):
+        if a.optimizer == "SGD":
+            return torch.optim.SGD(params, lr=1e-3, weight_decay=0.01, momentum=0.9)
+        if a.optimizer == "Adam":
+            return torch.optim.Adam(params, lr=1e-3)
+        return torch.optim.RMSprop(params, lr=1e-3, weight_decay=0.01, momentum=a.momentum or 0.0)
+    opt = optimizer(net_a.parameters())
     auto = types.SimpleNamespace(net=net_a, optimizer=opt, weight=0.25, l=2.8)
     perm = torch.randperm(st.n_pairs, device=dev)
 
     torch.manual_seed(0)
     net_n = myNet(F, C).to(dev)
     net_n.apply(models.weights_init)
-    tr = FusedSmallTrainer(net_n, 1e-3, 0.25, 2.8, seed=0, momentum=a.momentum)
+    if a.optimizer is not None:
+        tr = FusedSmallOptTrainer(net_n, optimizer(net_n.parameters()), 0.25, 2.8, seed=0)
+    else:
+        tr = FusedSmallTrainer(net_n, 1e-3, 0.25, 2.8, seed=0, momentum=a.momentum)
     tr.begin_voter(0)
     tr._perm = perm
     per = 16
     bf = tr.buffers(m)
     plain = None
-    if a.momentum is not None:                           # the default step beside it: the momentum-free launch, its own buffers and graph
+    if a.momentum is not None or a.optimizer is not None:        # the default step beside it: the momentum-free RMSprop launch, its own buffers and graph
         torch.manual_seed(0)
         net_p = myNet(F, C).to(dev)
         net_p.apply(models.weights_init)
@@ -172,7 +189,7 @@ def main():
     extra = {}
     if plain is not None:
         spread = max(t_auto) - min(t_auto)
-        extra = {"momentum": a.momentum, "autograd_spread_us": round(spread, 2),
+        extra = {"momentum": a.momentum, "optimizer": a.optimizer or "RMSprop", "autograd_spread_us": round(spread, 2),
                  "native_below_autograd_by_more_than_its_spread": bool(us_a - us_n > spread),
                  "default_native_us_per_step": round(float(np.median(t_plain)), 2), "default_native_rounds_us": [round(t, 2) for t in t_plain]}
     line = json.dumps({**extra, "tool": "bench_small_step", "m": m, "F": F, "C": C, "n_pairs": st.n_pairs, "steps_per_round": steps,
