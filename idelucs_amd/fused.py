@@ -393,7 +393,8 @@ class _LinearStepParts:
         this step assembles the next one (into bf.xs[1 - xi] when the middle launches do it, else into bf.x).
         defer_tail (run_epoch's steps): the step's optimizer tail may wait for the next step's first launch (flush_tail)."""
         if pipelined:
-            self.step_on_batch(bf, train=train, batch_advance=bf.m // 2, next_from=store, xi=xi if self.F % 4 == 0 else 0, defer_tail=defer_tail)
+            # (a step that is not early assembles the next batch into bf.x in its last launch: every such step runs on bf.xs[0])
+            self.step_on_batch(bf, train=train, batch_advance=bf.m // 2, next_from=store, xi=xi if self._early(bf, store) else 0, defer_tail=defer_tail)
         else:
             self._gather(store, bf)
             self.step_on_batch(bf, train=train, batch_advance=bf.m // 2)
@@ -587,6 +588,8 @@ class FusedLinearTrainer(_LinearStepParts):
         # the sums launch carries the forward middle (six launches): the lone step with the tail on the dW1 tiles and no tail pending from another ending
         merged = self._sums_fwd and tail_on_wgrad and not rec and self._pending is None
         r1 = _r1T_of(pb, bf, xi) if merged else part[0]      # [H1, m]: (else) slab 0 of the partial sums, where mid_fwd leaves the activations
+        if not rec:
+            bf._l1_src = "r1T" if merged else "part"
         wh, wl, flag = self._planes_operands(bf, pb, xi)
         if cold:
             self._evict()
@@ -641,6 +644,8 @@ class FusedLinearTrainer(_LinearStepParts):
         pb = _planes_of(bf, F)
         part = pb["part"][xi]
         r1 = part.view(-1, m, H1)[0]            # [m, H1]: slab 0 of part[8][m][512]
+        if not rec:
+            bf._l1_src = "part_rows"
         wh, wl, flag = self._planes_operands(bf, pb, xi)
         if cold:
             self._evict()
@@ -674,6 +679,7 @@ class FusedLinearTrainer(_LinearStepParts):
         m, H1, F = bf.m, self.H1, self.F
         self._fp32_step(bf, xi)
         x, r1 = bf.xs[xi], _r1_of(bf, xi)
+        bf._l1_src = "r1_of"
         if self._pending is not None:
             self._tail_launch(*self._pending, l1=(x, m, r1.view(H1, m)))
         else:
@@ -694,6 +700,8 @@ class FusedLinearTrainer(_LinearStepParts):
         k = self._k if early else _launch
         self._fp32_step(bf, xi)
         x, r1 = bf.xs[xi], bf.r1
+        if self._rec is None:
+            bf._l1_src = "r1_t" if both else "r1"
         self._general_fwd_bwd(bf, tr, batch_advance, st, xi, k=k, mm=self._mm, dz=False, dw2=st is None)
         # ---- dW1 on own MFMA tiles with RMSprop in their epilogue: at the head of the optimizer launch of a pipelined step, else a
         # launch of its own (a recorded step takes the tiles only inside its optimizer launch); dW1 as a GEMM where the tiles do not apply
@@ -734,6 +742,24 @@ class FusedLinearTrainer(_LinearStepParts):
         if pb is None or not pb.get("dr1_as_planes", False):
             return bf.dr1
         return ((pb["dh"].view(torch.float16).double() + pb["dl"].view(torch.float16).double()) * 2.0 ** -int(self._dr1_scale[0].item())).float()
+
+    def layer1_output(self, bf, xi=0):
+        """Layer 1's ReLU (+ Dropout) output of the last step on bf, run at parity xi, as an [m, 512] tensor (tests; no launch): the general
+        form's bf.r1 (transposed where the product was W1 x^T), the tiles form's image of that parity, slab 0 of the parity's partial sums
+        (transposed at n_clusters <= 48), or the transposed activations of a sums launch that carried the forward middle."""
+        src = getattr(bf, "_l1_src", None)
+        if src is None:
+            raise RuntimeError("no step has run on these buffers")
+        if src == "r1":
+            return bf.r1
+        if src == "r1_t":
+            return bf.r1T.t()
+        if src == "r1_of":
+            return _r1_of(bf, xi).view(self.H1, bf.m).t()
+        pb = bf._planes
+        if src == "r1T":
+            return _r1T_of(pb, bf, xi).t()
+        return pb["part"][xi].view(-1, bf.m, self.H1)[0] if src == "part_rows" else pb["part"][xi][0].t()
 
     def _dy_planes_args(self, pb):
         return (_p(pb["dh"]), _p(pb["dl"]), _p(self._dr1_scale))

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import DATA, GOLDEN
+from linear_dropout_ref import _autograd_step, masks as restated_masks
 
 pytestmark = pytest.mark.gpu
 
@@ -47,57 +48,6 @@ def _random_net(F, C, dev, seed=0):
     net = NetLinear(F, C)
     net.apply(weights_init)
     return net.to(dev)
-
-
-def _same_branch(want, have, pre, bound, name):
-    """The units the float64 forward keeps (want) and the ones the trainer kept (have) are the same set, but for units whose float64
-    pre-activation lies within fp32 rounding of zero: |pre| <= 1e-5 x sum |x_k| |w_k| (some 170 fp32 epsilons of the dot product's
-    terms), and no more than 1e-4 of all units."""
-    mism = want != have
-    n = int(mism.sum().item())
-    print(f"  {name}: {n} of {mism.numel()} units at a ReLU kink" + (f" (|pre| / bound <= {float((pre.abs()[mism] / bound[mism]).max()):.1e})" if n else ""))
-    if n:
-        assert bool((pre.abs()[mism] <= 1e-5 * bound[mism]).all()), (name, n, float((pre.abs()[mism] / bound[mism]).max()))
-        assert n <= 1e-4 * mism.numel(), (name, n)
-
-
-def _autograd_step(net, x, kept, masks=None):
-    """The reference step (models.py:117-133) written out on a float64 copy of net: dropout off, or the given keep masks x 2 in place of
-    nn.Dropout.  -> (loss, [6 gradients as float32]).
-    kept = (layer 1's output > 0 [m, 512], the classifier's masked latent > 0 [m, 64]) of the trainer's step on the same parameters: ReLU
-    has no derivative at 0, and a unit whose pre-activation is zero to fp32 rounding falls on either side of it in two correct forwards --
-    its whole contribution to the weight gradients (one sample's outer product: 1e-2 of dW1's largest entry at F = 256) then differs, which
-    says nothing about either step.  The reference therefore differentiates the branch the trainer took, after checking (_same_branch) that
-    the two forwards chose differently at such units only."""
-    import torch
-    import torch.nn.functional as Fn
-    from idelucs_amd.LossFunctions import IID_loss
-    ref = copy.deepcopy(net).double()
-    x = x.double()
-    l1, l2, l3 = ref.layers[0], ref.layers[3], ref.classifier[2]
-    ps = [l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias]
-    scale = 2.0 if masks is not None else 1.0
-    with torch.no_grad():
-        pre1 = Fn.linear(x, l1.weight, l1.bias)
-        want1 = (pre1 > 0) & masks[0] if masks is not None else pre1 > 0
-        _same_branch(want1, kept[0], pre1, Fn.linear(x.abs(), l1.weight.abs(), l1.bias.abs()), "layer 1")
-    a1 = Fn.linear(x, l1.weight, l1.bias) * kept[0].double() * scale
-    h = Fn.linear(a1, l2.weight, l2.bias)
-    with torch.no_grad():
-        want2 = (h > 0) & masks[1] if masks is not None else h > 0
-        _same_branch(want2, kept[1], h, Fn.linear(a1.abs(), l2.weight.abs(), l2.bias.abs()), "the latent")
-    r2 = h * kept[1].double() * scale
-    z = torch.softmax(Fn.linear(r2, l3.weight, l3.bias), dim=1)
-    b = x.shape[0] // 2
-    f = Fn.normalize(h, dim=1)                          # info_nce_loss (LossFunctions.py:65-98) without its cast to float32
-    s = (f @ f.t()) / 0.85
-    r = torch.arange(2 * b, device=s.device)
-    pos = s[r, (r + b) % (2 * b)]
-    s = s.masked_fill(r.unsqueeze(0) == r.unsqueeze(1), float("-inf"))
-    nce = (torch.logsumexp(s, dim=1) - pos).mean()
-    loss = 0.75 * nce + 0.25 * IID_loss(z[:b], z[b:], lamb=2.8)
-    loss.backward()
-    return float(loss.item()), [p.grad.detach().float().clone() for p in ps]
 
 
 class _Store:
@@ -220,7 +170,8 @@ def test_three_steps_with_hyperparameters_a_scheduler_changed(dev, opt, F, m, C)
 @pytest.mark.parametrize("F,m,C", [(4096, 1024, 20), (1024, 512, 200), (256, 512, 5)])
 def test_dropout_step_matches_autograd_with_the_trainers_masks(dev, opt, F, m, C):
     """Voter 3's first step.  The mask after layer 1 is drawn with NetLinear's existing layer id and stream (idl_relu_dropout_fwd, layer 1,
-    the trainer's seed and counter); the classifier's from the step's own masked latent (a kept, active unit is one whose output is > 0)."""
+    the trainer's seed and counter) and must be the host restatement's (linear_dropout_ref.masks); the classifier's IS the restatement's,
+    which the step's own masked latent must follow (a kept, active unit is one whose output is > 0)."""
     import torch
     from idelucs_amd import _lib
     from idelucs_amd.fused import _p, _stream
@@ -235,13 +186,16 @@ def test_dropout_step_matches_autograd_with_the_trainers_masks(dev, opt, F, m, C
     _lib.check(_lib.lib.idl_relu_dropout_fwd(_p(ones), ones.numel(), 1, tr.seed, _p(tr.ctl), 1, _stream()))
     mask1 = ones > 0
     assert abs(mask1.float().mean().item() - 0.5) < 0.01
+    # ... and both masks are the host restatement's of (seed, voter 3's first step word): the latent's is passed as restated, so the step's
+    # own r2 > 0 must be (h > 0) & that mask (_same_branch)
+    want1, mask2 = (torch.from_numpy(a).to(dev) for a in restated_masks(tr.seed, 3 << 24, m))
+    assert torch.equal(mask1, want1)
     p0 = copy.deepcopy(net)
     bf = tr.buffers(m)
     bf.xs[0].copy_(x)
     tr.step_on_batch(bf, train=True, batch_advance=m // 2, next_from=st, xi=0)
     torch.cuda.synchronize()
-    mask2 = bf.r2 > 0
-    loss_ref, grads_ref = _autograd_step(p0, x, (tr.layer1_output(bf) > 0, mask2), masks=(mask1, mask2))
+    loss_ref, grads_ref = _autograd_step(p0, x, (tr.layer1_output(bf) > 0, bf.r2 > 0), masks=(mask1, mask2))
     got = tr.out[0].item()
     print(f"{opt} F={F} m={m} C={C}: loss {got:.7f} autograd with the trainer's masks {loss_ref:.7f}")
     assert abs(got - loss_ref) <= 2e-4 * abs(loss_ref), (got, loss_ref)
