@@ -250,6 +250,10 @@ def build_parser():
     p.add_argument("--rmsprop_momentum", action="store", type=str, default=argparse.SUPPRESS, choices=["ignore", "follow"],
                    help="--optimizer RMSprop with --scheduler Triangle: the native steps ignore the momentum CyclicLR writes into the "
                         "optimizer (the default) or follow it, as torch and the reference do")
+    p.add_argument("--store", action="store", type=str, default=argparse.SUPPRESS, choices=["resident", "streamed"],
+                   help="where the training rows live: the [views, N, 4^k] feature store resident in HBM (the default), or streamed -- every batch "
+                        "vectorised from the packed bases when it is needed, predict in row chunks: no N x 4^k buffer in the run "
+                        "(model_size='linear', 4 <= k <= 9, --rng philox)")
     return p
 
 

@@ -84,6 +84,14 @@ SIGNATURES = {
     "idl_counts_stream_workspace": (_i64, [_i64, _i64]),
     "idl_counts_stream_stats": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "idl_counts_stream_finish": (_int, [_i64, _i64, _vp, _vp, _vp, _vp]),
+    "idl_col_stats_stream_workspace": (_i64, [_i64, _i64]),
+    "idl_col_stats_stream": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "idl_col_stats_stream_finish": (_int, [_i64, _i64, _vp, _vp, _vp, _vp]),
+    "idl_vectorise_pairs_supported": (_int, [_int, _i64, _i64, _i64]),
+    "idl_vectorise_pairs_at": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
+                                      _vp, _vp]),
+    "idl_vectorise_pairs_planes_at": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
+                                             _vp, _vp, _vp, _vp, _vp]),
     "idl_gather_pairs": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "idl_gather_pairs_at": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "idl_relu_dropout_fwd": (_int, [_vp, _i64, _int, _c.c_uint64, _vp, _int, _vp]),

@@ -8,10 +8,13 @@ _PINNED = {"GT_file": None, "optimizer": "RMSprop", "lambda": 2.8, "lr": 1e-3, "
 
 
 class iDeLUCS_cluster():
-    def __init__(self, sequence_file, n_clusters=4, n_epochs=500, n_mimics=3, batch_sz=512, k=4, weight=0.25, n_voters=1):
+    def __init__(self, sequence_file, n_clusters=4, n_epochs=500, n_mimics=3, batch_sz=512, k=4, weight=0.25, n_voters=1, store=None):
+        """store (not in the reference): None / 'resident', or 'streamed' -- no N x 4^k buffer in the run (IID_model's args['store'])."""
         chosen = dict(sequence_file=sequence_file, n_clusters=n_clusters, n_epochs=n_epochs, n_mimics=n_mimics,
                       batch_sz=batch_sz, k=k, weight=weight, n_voters=n_voters)
         self.args = {**chosen, **_PINNED}
+        if store is not None:
+            self.args["store"] = store
 
     def fit_predict(self, kmers=None):
         """(y_pred int64 [N], latent float64 [N, 64]) of the LAST voter; no ensembling here, and the

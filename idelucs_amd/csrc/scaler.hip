@@ -344,6 +344,61 @@ __global__ __launch_bounds__(STAT_THREADS) void counts_slab_stats_kernel(const i
     for (int e = 0; e < 4; ++e) { p1[e] = a1[e]; p2[e] = a2[e]; }
 }
 
+// col_shifted_sums_kernel<float, 4> for a matrix of float32 rows that arrives a chunk at a time (x addresses the chunk's first row): the
+// same row blocks of the whole matrix, the same ascending row order and the same expressions per column, a chunk that begins inside a row
+// block continuing from the partial the previous chunk left -- so the sums are col_shifted_sums_kernel's whatever the cuts.  The shift x0
+// is row 0 of the matrix, kept as float64 for the finishing kernel.
+__global__ __launch_bounds__(STAT_THREADS) void rows_slab_stats_kernel(const float *x, int64_t row_lo, int64_t rows, int64_t f, int64_t rows_per_block,
+                                                                       double *x0, double *partial1, double *partial2)
+{
+    const int64_t c = ((int64_t)blockIdx.x * STAT_THREADS + threadIdx.x) * 4;
+    if (c >= f) return;
+    const int64_t blk = row_lo / rows_per_block + blockIdx.y;
+    const int64_t b0 = blk * rows_per_block;
+    const int64_t r0 = b0 > row_lo ? b0 : row_lo;
+    int64_t r1 = b0 + rows_per_block;
+    if (r1 > row_lo + rows) r1 = row_lo + rows;
+    double sh[4], a1[4], a2[4];
+    if (row_lo == 0) {
+        const float4 v = *(const float4 *)(x + c);
+        sh[0] = (double)v.x; sh[1] = (double)v.y; sh[2] = (double)v.z; sh[3] = (double)v.w;
+        if (blockIdx.y == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x0[c + e] = sh[e];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sh[e] = x0[c + e];
+    }
+    double *p1 = partial1 + blk * f + c, *p2 = partial2 + blk * f + c;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        a1[e] = r0 == b0 ? 0.0 : p1[e];
+        a2[e] = r0 == b0 ? 0.0 : p2[e];
+    }
+    const float *rowp = x + (r0 - row_lo) * f + c;             // row r of the matrix is row r - row_lo of the chunk
+    int64_t left = r1 - r0;
+    for (; left >= SLAB_ROWS; left -= SLAB_ROWS, rowp += SLAB_ROWS * f) {
+        float4 v[SLAB_ROWS];
+#pragma unroll
+        for (int u = 0; u < SLAB_ROWS; ++u) v[u] = *(const float4 *)(rowp + (int64_t)u * f);
+#pragma unroll
+        for (int u = 0; u < SLAB_ROWS; ++u) {
+            const float v4[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const double t = (double)v4[e] - sh[e]; a1[e] += t; a2[e] += t * t; }
+        }
+    }
+    for (; left > 0; --left, rowp += f) {
+        const float4 v = *(const float4 *)rowp;
+        const float v4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const double t = (double)v4[e] - sh[e]; a1[e] += t; a2[e] += t * t; }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { p1[e] = a1[e]; p2[e] = a2[e]; }
+}
+
 __global__ __launch_bounds__(256) void gather_pairs_kernel(idl_dev::GatherArgs g)
 {
     idl_dev::gather_block(g, blockIdx.x, threadIdx.x);
@@ -538,6 +593,35 @@ int idl_counts_stream_stats(const int32_t *counts, const int32_t *totals, int64_
     hipLaunchKernelGGL(counts_slab_stats_kernel, grid, dim3(STAT_THREADS), 0, (hipStream_t)stream, counts, totals, row_lo, rows, f, rpb, x0, p1, p2);
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
+}
+
+/* idl_col_stats for a float32 matrix that arrives a chunk of rows at a time (4 | f): idl_counts_stream_stats' protocol with the rows
+ * themselves in place of counts and totals; idl_col_stats_stream_finish gives idl_col_stats' mean / scale bit for bit, whatever the cuts. */
+int64_t idl_col_stats_stream_workspace(int64_t n, int64_t f)
+{
+    return idl_counts_stats_workspace(n, f);
+}
+
+int idl_col_stats_stream(const float *x, int64_t row_lo, int64_t rows, int64_t n, int64_t f, void *workspace, void *stream)
+{
+    IDL_REQUIRE(n >= 1 && f >= 4 && (f & 3) == 0, "col_stats_stream needs n >= 1 and 4 | f");
+    IDL_REQUIRE(row_lo >= 0 && rows >= 0 && rows <= n && row_lo <= n - rows, "col_stats_stream: the chunk leaves the matrix");
+    if (rows == 0) return IDL_OK;
+    IDL_REQUIRE(x && workspace && (((uintptr_t)x) & 15u) == 0 && (((uintptr_t)workspace) & 7u) == 0, "col_stats_stream: NULL or misaligned buffer");
+    const int64_t blocks = stat_row_blocks(n);
+    const int64_t rpb = (n + blocks - 1) / blocks;
+    double *p1 = (double *)workspace, *p2 = p1 + blocks * f, *x0 = p2 + blocks * f;
+    const int64_t touched = (row_lo + rows - 1) / rpb - row_lo / rpb + 1;          // <= blocks <= 256
+    const dim3 grid((unsigned)((f / 4 + STAT_THREADS - 1) / STAT_THREADS), (unsigned)touched);
+    hipLaunchKernelGGL(rows_slab_stats_kernel, grid, dim3(STAT_THREADS), 0, (hipStream_t)stream, x, row_lo, rows, f, rpb, x0, p1, p2);
+    IDL_HIP_TRY(hipGetLastError());
+    return IDL_OK;
+}
+
+int idl_col_stats_stream_finish(int64_t n, int64_t f, const void *workspace, double *mean, double *scale, void *stream)
+{
+    IDL_REQUIRE(n >= 1 && f >= 4 && (f & 3) == 0, "col_stats_stream_finish needs n >= 1 and 4 | f");
+    return idl_counts_stream_finish(n, f, workspace, mean, scale, stream);
 }
 
 int idl_counts_stream_finish(int64_t n, int64_t f, const void *workspace, double *mean, double *scale, void *stream)

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "common.h"
+#include "scaler_device.h"
 
 namespace {
 
@@ -1770,6 +1771,7 @@ int launch_vectorise(const VecArgs &a_in, const idl::DeviceInfo &di, hipStream_t
 }
 
 #include "vectorise_slices.h"   // k = 8, 9: the histogram exceeds one CU's LDS
+#include "vectorise_pairs.h"    // a training batch's rows straight from the packed bases (idl_vectorise_pairs_at)
 
 int dispatch_vectorise(int k, const VecArgs &a, hipStream_t st)
 {
@@ -1964,6 +1966,78 @@ int idl_vectorise_ranges(const void *codes, const void *mask, const int64_t *slo
                          void *out, int64_t view_stride, int64_t max_len, void *stream)
 {
     return vectorise_impl(codes, mask, slot_off, lengths, n, k, mode, init, out_kind, n_views, edits, edit_ranges, 1, out, view_stride, max_len, stream);
+}
+
+int idl_vectorise_pairs_supported(int k, int64_t f, int64_t batch, int64_t max_len)
+{
+    return vectorise_pairs_shape_ok(k, f, batch, max_len) ? 1 : 0;
+}
+
+static int vectorise_pairs_impl(const void *codes, const void *mask, const int64_t *slot_off, const int64_t *lengths, int64_t n, int k, int mode,
+                                int init, int n_views, const uint32_t *edits, const int64_t *edit_ranges, int64_t max_len, const double *mean,
+                                const double *scale, const double *inv_scale, const int64_t *pair_idx, const int64_t *base, int64_t base_add,
+                                int64_t batch, int64_t n_pairs, float *y, void *y_hi, void *y_lo, int *overflow_flag, void *stream)
+{
+    IDL_REQUIRE(mode == IDL_MODE_KMER, "vectorise_pairs makes plain k-mer rows (IDL_MODE_KMER): canonical and CGR rows are not built");
+    IDL_REQUIRE(init == IDL_INIT_ONE, "vectorise_pairs makes the rows of IDL_INIT_ONE (IDL_INIT_FROM_OUT and IDL_INIT_ZERO are refused)");
+    IDL_REQUIRE(k >= 4 && k <= IDL_MAX_K, "vectorise_pairs: k outside 4..IDL_MAX_K");
+    IDL_REQUIRE(n >= 1 && n_views >= 2 && n_views <= 64 && batch >= 0 && n_pairs >= 0, "vectorise_pairs needs n >= 1, 2 <= n_views <= 64, batch >= 0, n_pairs >= 0");
+    IDL_REQUIRE(idl_vectorise_pairs_supported(k, 1ll << (2 * k), batch, max_len), "vectorise_pairs: batch or max_len beyond 2^30");
+    IDL_REQUIRE((edits == nullptr) == (edit_ranges == nullptr), "edits and edit_ranges must both be given or both NULL");
+    if (batch == 0) return IDL_OK;
+    IDL_REQUIRE((y_hi == nullptr) == (y_lo == nullptr), "vectorise_pairs: both planes or neither");
+    IDL_REQUIRE(codes && mask && slot_off && lengths && mean && scale && pair_idx && (y || y_hi), "NULL buffer");
+    IDL_REQUIRE(((uintptr_t)codes & 15u) == 0 && ((uintptr_t)mask & 7u) == 0 && ((uintptr_t)y & 15u) == 0 && (((uintptr_t)y_hi | (uintptr_t)y_lo) & 7u) == 0,
+                "codes/y must be 16-byte aligned, mask and the planes 8-byte aligned");
+    idl::DeviceInfo di;
+    int rc = idl::device_info(&di);
+    if (rc != IDL_OK) return rc;
+    VecArgs a{};
+    a.codes = (const uint4 *)codes;
+    a.mask = (const uint2 *)mask;
+    a.slot_off = slot_off;
+    a.lengths = lengths;
+    a.n = n;
+    a.mode = mode;
+    a.init = init;
+    a.out_kind = IDL_OUT_FREQ_F32;
+    a.n_views = n_views;
+    a.edits = edits;
+    a.edit_off = edit_ranges;
+    a.eo_shift = 1;
+    a.out = y;
+    a.view_stride = 0;
+    a.max_len = max_len;
+    const PairArgs p{pair_idx, base, base_add, batch, n_pairs, mean, scale, inv_scale, y, (uint16_t *)y_hi, (uint16_t *)y_lo, overflow_flag};
+    hipStream_t st = (hipStream_t)stream;
+    switch (k) {
+    case 4: return launch_vectorise_pairs<4>(a, p, di, st);
+    case 5: return launch_vectorise_pairs<5>(a, p, di, st);
+    case 6: return launch_vectorise_pairs<6>(a, p, di, st);
+    case 7: return launch_vectorise_pairs<7>(a, p, di, st);
+    case 8: return launch_vectorise_pairs_slices<8>(a, p, di, st);
+    case 9: return launch_vectorise_pairs_slices<9>(a, p, di, st);
+    }
+    return IDL_ERR_ARG;
+}
+
+int idl_vectorise_pairs_at(const void *codes, const void *mask, const int64_t *slot_off, const int64_t *lengths, int64_t n, int k, int mode,
+                           int init, int n_views, const uint32_t *edits, const int64_t *edit_ranges, int64_t max_len, const double *mean,
+                           const double *scale, const double *inv_scale, const int64_t *pair_idx, const int64_t *base, int64_t base_add,
+                           int64_t batch, int64_t n_pairs, float *y, void *stream)
+{
+    return vectorise_pairs_impl(codes, mask, slot_off, lengths, n, k, mode, init, n_views, edits, edit_ranges, max_len, mean, scale, inv_scale, pair_idx,
+                                base, base_add, batch, n_pairs, y, nullptr, nullptr, nullptr, stream);
+}
+
+int idl_vectorise_pairs_planes_at(const void *codes, const void *mask, const int64_t *slot_off, const int64_t *lengths, int64_t n, int k, int mode,
+                                  int init, int n_views, const uint32_t *edits, const int64_t *edit_ranges, int64_t max_len, const double *mean,
+                                  const double *scale, const double *inv_scale, const int64_t *pair_idx, const int64_t *base, int64_t base_add,
+                                  int64_t batch, int64_t n_pairs, float *y, void *y_hi, void *y_lo, int *overflow_flag, void *stream)
+{
+    IDL_REQUIRE(y_hi && y_lo, "vectorise_pairs_planes: the two planes must be given (fp32 only: idl_vectorise_pairs_at)");
+    return vectorise_pairs_impl(codes, mask, slot_off, lengths, n, k, mode, init, n_views, edits, edit_ranges, max_len, mean, scale, inv_scale, pair_idx,
+                                base, base_add, batch, n_pairs, y, y_hi, y_lo, overflow_flag, stream);
 }
 
 /* the k = 8, 9 kernel's dynamic LDS per workgroup and the workgroups per CU its launcher puts on the chip (build checks, reports) */

@@ -54,8 +54,24 @@ __device__ __forceinline__ uint32_t slice_bin(uint32_t km, int mode)
     return km;
 }
 
-template <int K>
-__global__ __launch_bounds__(SL_NT) void vectorise_slices_kernel(VecArgs a, const int32_t *rank_tab)
+// Where the items of a launch come from.  The whole-store kernel takes item `it` of the grid as (sequence it / n_views, view it % n_views) and
+// stores the row as the vectoriser made it; vectorise_pairs.h takes the item from a pair list and standardises the float32 row on its way out.
+struct SliceGridItems {
+    __device__ __forceinline__ int64_t count(const VecArgs &a) const { return a.n * a.n_views; }
+    __device__ __forceinline__ bool item(const VecArgs &a, int64_t it, int64_t row_len, int64_t &s, int &v, int64_t &out_base) const
+    {
+        s = it / a.n_views;
+        v = (int)(it - s * a.n_views);
+        out_base = (int64_t)v * a.view_stride + s * row_len;
+        return true;
+    }
+    // four float32 frequencies of the row, at a.out + o (col: the row's column of f.x)
+    __device__ __forceinline__ void store_f32(const VecArgs &a, int64_t o, int64_t, float4 f) const { *(float4 *)((float *)a.out + o) = f; }
+};
+
+// one workgroup's share of the items: the body of vectorise_slices_kernel and of vectorise_pairs_slices_kernel
+template <int K, typename Items>
+__device__ __forceinline__ void slices_body(const VecArgs &a, const int32_t *rank_tab, const Items &items)
 {
     constexpr int F = 1 << (2 * K);
     constexpr uint32_t KM = (1u << (2 * K)) - 1u;
@@ -82,15 +98,15 @@ __global__ __launch_bounds__(SL_NT) void vectorise_slices_kernel(VecArgs a, cons
     const uint32_t iv = (a.init == IDL_INIT_ONE) ? 1u : 0u;
     const int first_sweep = (canonical && a.out_kind != IDL_OUT_COUNTS_I32) ? 0 : 1;
 
-    const int64_t items = a.n * a.n_views;
-    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
-        const int64_t s = it / a.n_views;
-        const int v = (int)(it - s * a.n_views);
+    const int64_t n_items = items.count(a);
+    for (int64_t it = blockIdx.x; it < n_items; it += gridDim.x) {
+        int64_t s, out_base;
+        int v;
+        if (!items.item(a, it, row_len, s, v, out_base)) continue;      // (the same answer in every thread of the workgroup)
         const int64_t slot0 = a.slot_off[s];
         const int64_t L = a.lengths[s];
         const int64_t nslots = (L + 63) >> 6;
         const int64_t nsc = (nslots + SL_SC - 1) / SL_SC;
-        const int64_t out_base = (int64_t)v * a.view_stride + s * row_len;
         const uint32_t *E = nullptr;
         int64_t ne = 0;
         if (a.edits != nullptr) {
@@ -228,7 +244,7 @@ __global__ __launch_bounds__(SL_NT) void vectorise_slices_kernel(VecArgs a, cons
                                 f.x = (float)((double)h.x / Sd); f.y = (float)((double)h.y / Sd);
                                 f.z = (float)((double)h.z / Sd); f.w = (float)((double)h.w / Sd);
                             }
-                            *(float4 *)((float *)a.out + o) = f;
+                            items.store_f32(a, o, (int64_t)lo_bin + i4 * 4, f);
                         }
                     }
                 }
@@ -237,6 +253,12 @@ __global__ __launch_bounds__(SL_NT) void vectorise_slices_kernel(VecArgs a, cons
         }
         __syncthreads();
     }
+}
+
+template <int K>
+__global__ __launch_bounds__(SL_NT) void vectorise_slices_kernel(VecArgs a, const int32_t *rank_tab)
+{
+    slices_body<K>(a, rank_tab, SliceGridItems{});
 }
 
 // rank_tab[g] = canonical k-mers (b <= rc(b)) below bin 64 * g, g in [0, 4^k / 64]; built on the host once per (device, k)

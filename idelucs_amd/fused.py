@@ -103,6 +103,18 @@ def rows_lockstep_applies(m, H1, F, C, n_rows, cus):
             and m % 16 == 0 and F % 4 == 0 and n_rows < PLANES_MAX_ROWS and _L.idl_nce_fused_workspace(m) > 0 and rows_shape_applies(m, H1, F, cus))
 
 
+def _resident(st):
+    """Whether st keeps its rows in HBM (utils.FeatureStore, or any object with its fields) -- else a utils.StreamedFeatureStore."""
+    return getattr(st, "resident", True)
+
+
+def _addresses(st):
+    """Every address a launch on st bakes in: part of a captured graph's key."""
+    if hasattr(st, "addresses"):
+        return st.addresses()
+    return tuple(t.data_ptr() for t in (st.feats, st.mean, st.scale, st.inv_scale))
+
+
 def _launch(fn, *args):
     """One kernel launch, performed now (the launcher of launch_losses outside a recording)."""
     _lib.check(fn(*args))
@@ -280,7 +292,16 @@ class _LinearStepParts:
     def _next_batch(self, st, m, *, y=None, planes=(None, None), flag=None, part=0, part_end=8, parts=8, base_add=None):
         """The next batch's assembly by a launch (idl_next_batch_t): the store, the pair list and the offset -- ctl[1], which a middle launch
         reads before the step has advanced it (base_add: m // 2 rows on) --, the destination y and / or the two planes with their overflow flag,
-        and the share [part, part_end) of `parts` this launch takes."""
+        and the share [part, part_end) of `parts` this launch takes.
+        A streamed store (utils.StreamedFeatureStore) has no rows to copy: the batch -- fp32, planes, or both, as asked for here -- is vectorised by ONE
+        launch of its own (idl_vectorise_pairs_at / _planes_at), issued here, in front of the launch that would have carried share 0, so it reads the
+        offset where that launch would have; the step's launches get no assembly at all (None: NULL)."""
+        if not _resident(st):
+            if self._rec_active():
+                raise RuntimeError("a streamed feature store assembles the batches of a lone voter's step: its launch cannot be recorded for a lockstep batch")
+            if part == 0:
+                st.pairs_at(self._perm, self.ctl[1:], m // 2 if base_add is None else base_add, m // 2, st.n_pairs, y, planes, flag)
+            return None
         return _lib.idl_next_batch_t(_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), _p(self.ctl[1:]), m // 2 if base_add is None else base_add,
                                      st.n_pairs, m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(y), _p(planes[0]), _p(planes[1]), _p(flag),
                                      part, part_end, parts)
@@ -380,10 +401,16 @@ class _LinearStepParts:
         k(_L.idl_bias_grads, _p(bf.dr1), _p(r1), H1, _p(gb1), _p(bf.dlat), self.H2, _p(gb2), _p(bf.dlogits), C, _p(gb3),
           m, tr, adv_ctl, adv, None, None, _stream())
 
+    def _rec_active(self):
+        return getattr(self, "_rec", None) is not None
+
     def _gather(self, store, bf):
         b = bf.m // 2
-        _lib.check(_L.idl_gather_pairs_at(_p(store.feats), store.n, store.f, store.n * store.f, _p(self._perm), _p(self.ctl[1:]),
-                                          b, _p(store.mean), _p(store.scale), _p(store.inv_scale), _p(bf.x), _stream()))
+        if not _resident(store):      # the same entry as the steps' added launch
+            store.pairs_at(self._perm, self.ctl[1:], 0, b, store.n_pairs, bf.x)
+        else:
+            _lib.check(_L.idl_gather_pairs_at(_p(store.feats), store.n, store.f, store.n * store.f, _p(self._perm), _p(self.ctl[1:]),
+                                              b, _p(store.mean), _p(store.scale), _p(store.inv_scale), _p(bf.x), _stream()))
         if getattr(bf, "_planes", None) is not None:
             bf._planes["valid"][0] = False
             bf._planes["x32"][0] = True
@@ -847,8 +874,8 @@ class FusedLinearTrainer(_LinearStepParts):
             while per > 2 and n_full < 2 + 2 * per:      # short epochs: the capture itself runs 2 + per real steps
                 per = max(2, per // 4 * 2)
             # every address the captured launches bake in is part of the key (a store refitted in place keeps its graph)
-            key = (2 * batch_sz, store.feats.data_ptr(), store.mean.data_ptr(), store.scale.data_ptr(), store.inv_scale.data_ptr(),
-                   self._perm.data_ptr(), store.n, store.f, store.n_views, per)
+            # (a streamed store: its packed bases, offsets, lengths, edits and edit ranges in place of feats)
+            key = (2 * batch_sz, *_addresses(store), self._perm.data_ptr(), store.n, store.f, store.n_views, per)
             if use_graph and n_full >= 8:
                 g = self._graphs.get(key)
                 if g is None:

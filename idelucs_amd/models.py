@@ -125,6 +125,31 @@ class IID_model():
                             and self._linear_step(args) == 'native')
         if follow and self._use_fused:      # NetLinear: the step of fused_opt.FusedLinearOptTrainer with RMSprop as its optimizer
             self._use_fused, self._use_linopt = False, True
+        # where the training rows live: 'resident' (the [views, N, F] store in HBM) or 'streamed' (utils.StreamedFeatureStore: every batch vectorised
+        # from the packed bases when it is needed; no N x F buffer in the run, predict included)
+        self._streamed_store = self._store_mode(args) == 'streamed'
+
+    @staticmethod
+    def _store_mode(args):
+        """args['store']: 'resident' (absent or None) or 'streamed' (model_size='linear', 4 <= k <= 9, rng='philox', and none of the opt-in native
+        steps, which assemble their batches from the resident store inside their own launches); anything else raises ValueError."""
+        mode = args.get('store') or 'resident'
+        if mode not in ('resident', 'streamed'):
+            raise ValueError(f"store must be 'resident' or 'streamed', not {mode!r}")
+        if mode == 'resident':
+            return mode
+        if args['model_size'] != 'linear':
+            raise ValueError("store='streamed' makes plain k-mer rows only: model_size='small' trains on canonical rows, which a streamed store does not "
+                             "build (use store='resident')")
+        if not 4 <= args['k'] <= _lib.MAX_K:
+            raise ValueError(f"store='streamed' supports 4 <= k <= {_lib.MAX_K} (got k={args['k']})")
+        if (args.get('rng') or utils._default_rng_mode()) != 'philox':
+            raise ValueError("store='streamed' needs the device-drawn mimics (rng='philox'): rng='compat' is not supported")
+        for key, value in (('linear_step', 'native'), ('small_step', 'native'), ('small_opt_step', 'native'), ('rmsprop_momentum', 'follow')):
+            if args.get(key) == value:
+                raise ValueError(f"store='streamed' is not supported with {key}={value!r}: that native step assembles its batches from the resident "
+                                 "store inside its own launches (use store='resident', or leave the key out)")
+        return mode
 
     @staticmethod
     def _small_step(args):
@@ -197,8 +222,12 @@ class IID_model():
         each, utils.build_feature_store) and expose an iterable of device batches."""
         # (a second call -- the same file again, or another of the same record count -- refits the previous store in place: the
         #  captured step graph bakes the store's addresses and is then not captured again)
-        self.store = utils.build_feature_store(self.sequence_file, self.n_mimics, k=self.k, reduce=self.reduce,
-                                               rng=self.rng, seed=self.seed, device=self.device, streamed=True, reuse=self.store)
+        if self._streamed_store:        # (no reuse: a new store has new addresses, and the step graph is captured again)
+            self.store = utils.build_feature_store(self.sequence_file, self.n_mimics, k=self.k, reduce=self.reduce, rng=self.rng, seed=self.seed,
+                                                   device=self.device, resident=False, chunk_rows=self.predict_chunk_rows)
+        else:
+            self.store = utils.build_feature_store(self.sequence_file, self.n_mimics, k=self.k, reduce=self.reduce,
+                                                   rng=self.rng, seed=self.seed, device=self.device, streamed=True, reuse=self.store)
         self.dataloader = utils.DeviceBatchLoader(self.store, self.batch_sz)
         self._shared.clear()
 
@@ -354,6 +383,8 @@ class IID_model():
         float32 inputs would not fit PREDICT_CACHE_BYTES: there _predict_inputs stops caching them anyway, and its float64 rows
         (12 N F bytes with the float32 result) are what runs out of memory.  N is the store's; without a store, the route below.
         IDELUCS_DEV=predict_stream=1 / 0: always (where the rows allow it) / never."""
+        if self._streamed_store:      # a run without an N x F buffer: whatever PREDICT_CACHE_BYTES would allow
+            return True
         want = utils.OPTIONS["predict_stream"]
         if want == "0" or not utils.stream_route_ok(self.k, self.reduce):
             return False
@@ -367,8 +398,12 @@ class IID_model():
             self.net.eval()
             # the forward runs on the generator's whole buffer, every row where it stands in the chunk grid of the file: each chunk is the
             # same product shape and a row's place in it does not depend on `rows`, so a row shard has the bits of those rows in a full predict
-            for lo, hi, x, at in utils.predict_feature_chunks(self.sequence_file, k=self.k, reduce=self.reduce, device=self.device, rows=rows,
-                                                              chunk_rows=self.predict_chunk_rows, padded=True):
+            if self._streamed_store and self.store is not None:     # the packed bases are on the device already: predict_feature_chunks' passes on them
+                chunks = utils.feature_chunks_of_input(self.store.din, self.k, self.reduce, rows, self.predict_chunk_rows, padded=True)
+            else:
+                chunks = utils.predict_feature_chunks(self.sequence_file, k=self.k, reduce=self.reduce, device=self.device, rows=rows,
+                                                      chunk_rows=self.predict_chunk_rows, padded=True)
+            for lo, hi, x, at in chunks:
                 o, l = self.net(x)
                 outs.append(o[at:at + hi - lo])
                 lats.append(l[at:at + hi - lo])

@@ -105,6 +105,8 @@ def can_batch(model):
     # (the CLI hands the scheduler over as the reference does, as a string: "None" unless Plateau / Triangle was asked for)
     if not (model._use_fused and model.batch_sz % 16 == 0 and model.schedule not in ('Plateau', 'Triangle')):
         return False
+    if getattr(model, "_streamed_store", False):      # a streamed store's batches are a launch of the lone voter's step: one voter after the other
+        return False
     return bool(model.n_clusters <= 48 or lockstep_rows_applies(model))
 
 

@@ -597,6 +597,16 @@ class FeatureStore:
     all resident in HBM.  Pair p of the reference's x_train (utils.py:353) is
     (feats[0][p % N], feats[1 + p // N][p % N]), standardised."""
 
+    resident = True
+
+    @property
+    def device(self):
+        return self.feats.device
+
+    def addresses(self):
+        """Every address a launch on this store bakes in (fused.run_epoch's graph key)."""
+        return tuple(t.data_ptr() for t in (self.feats, self.mean, self.scale, self.inv_scale))
+
     def __init__(self, names, lengths, feats, mean, scale, k, reduce):
         self._names, self.lengths = names, lengths           # names: a list, or a FastaFile (its names are decoded on first use)
         self.feats, self.mean, self.scale = feats, mean, scale
@@ -624,6 +634,115 @@ class FeatureStore:
         _lib.check(_L.idl_gather_pairs(_ptr(self.feats), self.n, self.f, self.n * self.f, _ptr(pair_idx), b,
                                        _ptr(self.mean), _ptr(self.scale), _ptr(out), _stream_ptr()))
         return out
+
+
+class StreamedFeatureStore:
+    """FeatureStore without `feats`: what the rows are made of -- the packed bases on the device, the mimic edits of every view as
+    (begin, end) ranges, the scaler fitted on view 0 -- and every batch vectorised when it is asked for (idl_vectorise_pairs_at), with
+    the bits FeatureStore.gather_pairs gives on the resident store.  16 N F bytes of HBM (three mimics) become about a quarter of a
+    byte per base.  Plain k-mer rows, 4 <= k <= 9, device-drawn mimics (rng='philox')."""
+
+    resident = False
+
+    def __init__(self, names, lengths, din, edits, edit_ranges, mean, scale, k, n_views):
+        self._names, self.lengths = names, lengths           # names: a list, or a FastaFile (its names are decoded on first use)
+        self.din = din                                        # codes, mask, slot_off, lengths: the kernel reads them for as long as the store lives
+        self.edits, self.edit_ranges = edits, edit_ranges     # edit_ranges int64 [n_views * n, 2]
+        self.mean, self.scale = mean, scale
+        self.k, self.reduce = k, False
+        self.n_views, self.n, self.f = int(n_views), int(din.n), int(_L.idl_row_len(_lib.MODE_KMER, k))
+        self.n_pairs = (self.n_views - 1) * self.n
+        self.max_len = int(getattr(din, "max_len", 0) or 0)
+        self.inv_scale = torch.empty_like(scale)
+        self.refresh()
+
+    names = FeatureStore.names
+    refresh = FeatureStore.refresh
+
+    @property
+    def device(self):
+        return self.mean.device
+
+    def addresses(self):
+        """Every address a launch on this store bakes in (fused.run_epoch's graph key)."""
+        return tuple(t.data_ptr() for t in (self.din.codes, self.din.mask, self.din.slot_off, self.din.lengths, self.edits, self.edit_ranges,
+                                            self.mean, self.scale, self.inv_scale))
+
+    def pairs_at(self, pair_idx, base, base_add, batch, n_pairs, y, planes=(None, None), flag=None):
+        """idl_vectorise_pairs_at on this store: pairs pair_idx[*base + base_add + b], b < batch, places at or beyond n_pairs skipped -> y [2 batch, F].
+        planes = (hi, lo) int16 [2 batch, F]: the batch also (y None: only) as the two-plane step's fp16 planes, `flag` their overflow word
+        (idl_vectorise_pairs_planes_at)."""
+        d = self.din
+        head = (_ptr(d.codes), _ptr(d.mask), _ptr(d.slot_off), _ptr(d.lengths), self.n, self.k, _lib.MODE_KMER, _lib.INIT_ONE, self.n_views,
+                _ptr(self.edits), _ptr(self.edit_ranges), self.max_len, _ptr(self.mean), _ptr(self.scale), _ptr(self.inv_scale), _ptr(pair_idx),
+                _ptr(base), int(base_add), int(batch), int(n_pairs), _ptr(y))
+        if planes[0] is None:
+            _lib.check(_L.idl_vectorise_pairs_at(*head, _stream_ptr()))
+        else:
+            _lib.check(_L.idl_vectorise_pairs_planes_at(*head, _ptr(planes[0]), _ptr(planes[1]), _ptr(flag), _stream_ptr()))
+        return y
+
+    def gather_pairs(self, pair_idx, out=None):
+        """-> [2*B, F] float32: rows [0,B) 'true', [B,2B) 'modified' -- FeatureStore.gather_pairs of the resident store, bit for bit."""
+        b = pair_idx.numel()
+        if out is None:
+            out = torch.empty((2 * b, self.f), dtype=torch.float32, device=self.device)
+        return self.pairs_at(pair_idx, None, 0, b, b, out)
+
+
+def _edit_ranges(edit_off, n_items):
+    """The (begin, end) form [n_items, 2] of a view-major edit index: the one-pass generator's ranges as they are, a CSR array converted."""
+    if edit_off.dim() == 2:
+        return edit_off
+    return torch.stack([edit_off[:n_items], edit_off[1:n_items + 1]], dim=1).contiguous()
+
+
+def col_stats_of_view0(din, k, edits, edit_ranges, chunk_rows=None):
+    """col_stats(feats[0]) without feats: view 0's float32 rows vectorised a chunk of records at a time into ONE [chunk_rows, F] buffer
+    (the chunk of feature_chunks_of_input: predict_chunk_rows) and their statistics accumulated (idl_col_stats_stream) -> (mean, scale),
+    those of the resident store bit for bit."""
+    f = int(_L.idl_row_len(_lib.MODE_KMER, k))
+    n, dev = din.n, din.codes.device
+    cr = min(predict_chunk_rows(f, chunk_rows), n)
+    buf = torch.empty((cr, f), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(_L.idl_col_stats_stream_workspace(n, f), 8), dtype=torch.uint8, device=dev)
+    for a in range(0, n, cr):
+        b = min(a + cr, n)
+        _vectorise(_RowRange(din, a, b), k, _lib.MODE_KMER, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 1, edits, edit_ranges[a:b], buf[:b - a].unsqueeze(0))
+        _lib.check(_L.idl_col_stats_stream(_ptr(buf), a, b - a, n, f, _ptr(ws), _stream_ptr()))
+    mean = torch.empty(f, dtype=torch.float64, device=dev)
+    scale = torch.empty(f, dtype=torch.float64, device=dev)
+    _lib.check(_L.idl_col_stats_stream_finish(n, f, _ptr(ws), _ptr(mean), _ptr(scale), _stream_ptr()))
+    return mean, scale
+
+
+def _build_streamed_store(sequence_file, tfs, k, reduce, rng, seed, dev, fasta, chunk_rows):
+    if rng != "philox":
+        raise ValueError("a streamed feature store needs the device-drawn mimics (rng='philox'): rng='compat' keeps its edits on the host's RNG stream")
+    if reduce:
+        raise ValueError("a streamed feature store makes plain k-mer rows: the canonical rows of model_size='small' (reduce=True) are not built")
+    f = int(_L.idl_row_len(_lib.MODE_KMER, k)) if 1 <= k <= _lib.MAX_K else -1
+    if not _L.idl_vectorise_pairs_supported(k, f, 0, 0):
+        raise ValueError(f"a streamed feature store needs 4 <= k <= {_lib.MAX_K} (got k={k})")
+    # buffers of the store's own (not the one-pass reader's arenas, which the next file read overwrites): they live as long as it does
+    if fasta is not None:
+        ff, din = fasta, _DeviceInput(fasta, dev)
+        edits, edit_off = _philox_edits(din, [t.spec() for t in tfs], seed)
+    else:
+        ff = FastaFile(sequence_file, check=True, pack="deferred")
+        try:
+            din = _StreamedInput(ff, dev)
+            edits, edit_off = _philox_edits(din, [t.spec() for t in tfs], seed)     # (slots that overflow: the exact two-pass protocol, inside)
+            din.fill()
+        finally:
+            ff.close()
+    if din.n < 1:
+        raise ValueError("a streamed feature store needs at least one sequence")
+    if not _L.idl_vectorise_pairs_supported(k, f, 0, din.max_len):
+        raise ValueError(f"a streamed feature store needs sequences shorter than 2^30 bases (longest: {din.max_len})")
+    ranges = _edit_ranges(edit_off, len(tfs) * din.n)
+    mean, scale = col_stats_of_view0(din, k, edits, ranges, chunk_rows)
+    return StreamedFeatureStore(ff.names if fasta is not None else ff, ff.lengths, din, edits, ranges, mean, scale, k, len(tfs))
 
 
 def col_stats(x, out=None):
@@ -921,8 +1040,11 @@ class _OnePassInput:
 
 
 def build_feature_store(sequence_file, n_mimics, k=6, reduce=False, rng=None, seed=0, device=None, fasta=None, streamed=False,
-                        reuse=None):
+                        reuse=None, resident=True, chunk_rows=None):
     """Vectorise every mimic view of every sequence in one kernel launch and fit the scaler.
+    resident=False (rng='philox', plain k-mer rows, 4 <= k <= 9): no [n_views, N, F] buffer at all -> a StreamedFeatureStore, whose batches
+    are vectorised when they are asked for, with the resident store's bits; the scaler is fitted in one chunked pass over view 0
+    (chunk_rows rows at a time, default predict_chunk_rows).  `streamed` (how the FILE reaches the device) and `reuse` are not looked at.
     streamed=True (device RNG only): parse once, pack record chunks into pinned memory and copy each chunk to the device
     while the next is being packed; the mimic sites are drawn meanwhile (they need only the lengths).
     reuse = a FeatureStore the caller is done with: when the new store has its shape (the same file again, another file of the
@@ -931,6 +1053,8 @@ def build_feature_store(sequence_file, n_mimics, k=6, reduce=False, rng=None, se
     rng = rng or _default_rng_mode()
     dev = _device(device)
     tfs = mimic_transforms(n_mimics)
+    if not resident:
+        return _build_streamed_store(sequence_file, tfs, k, reduce, rng, seed, dev, fasta, chunk_rows)
 
     def finish(names, lengths, feats, n):
         """Scaler fit + the store: into `reuse` when its buffers were taken (feats is reuse.feats then), else a new one."""
@@ -1134,7 +1258,7 @@ class DeviceBatchLoader:
         return (self.store.n_pairs + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
-        perm = torch.randperm(self.store.n_pairs, device=self.store.feats.device, generator=self.generator)
+        perm = torch.randperm(self.store.n_pairs, device=self.store.device, generator=self.generator)
         for i in range(0, self.store.n_pairs, self.batch_size):
             idx = perm[i:i + self.batch_size]
             y = self.store.gather_pairs(idx)
