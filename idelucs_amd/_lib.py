@@ -125,6 +125,7 @@ SIGNATURES = {
     "idl_planes_exponent": (_int, [_int]),
     "idl_split_planes": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "idl_l1_planes_parts": (_int, []),
+    "idl_store_wt_mask": (_int, []),
     "idl_l1_planes_supported": (_int, [_int, _int, _int]),
     "idl_l1_planes": (_int, [_vp, _vp, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
     "idl_l1_planes_rows": (_int, [_vp, _vp, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "planes.h"
+#include "store_policy.h"
 
 namespace l1p_dev {
 
@@ -51,6 +52,7 @@ struct L1pArgs {
     int ldw, ldx;                  // elements between two rows of W1's / the batch's planes (>= K, multiples of 8)
     int dbg;                       // diagnostics (IDELUCS_DEV=l1p_dbg; wrong results): 1 no DMA, 4 no stores of the partial sums
     int rows;                      // 1: the same sums stored as part[KSPLIT][m][n_out] (a row of the batch contiguous; idl_l1_planes_rows)
+    int wt;                        // store_policy.h: idl_store::WT_PART makes the stores of the partial sums write-through
 };
 
 __host__ __device__ inline bool supported(int m, int n_out, int K)
@@ -213,6 +215,7 @@ __device__ __forceinline__ void l1p_body(const L1pArgs &g, const int bid, unsign
     constexpr int EP = 68;
     static_assert(4 * 64 * EP * 4 <= LDS_BYTES, "the four waves' epilogue images");
     float *img = (float *)smem + wv * (64 * EP);
+    const bool wt = (g.wt & idl_store::WT_PART) != 0;
     if (g.rows) {
         // part[KSPLIT][m][n_out]: the image is written turned (img[batch row][hidden unit]: an accumulator's four consecutive hidden units are one
         // 16-byte LDS store) and leaves as 16 bytes a lane along n_out -- the values are those of the form below, element for element
@@ -235,7 +238,7 @@ __device__ __forceinline__ void l1p_body(const L1pArgs &g, const int bid, unsign
         for (int u = 0; u < 16; ++u) {
             const int idx = lane + 64 * u, cl = idx >> 4, c4 = idx & 15;
             const float4 v = *(const float4 *)(img + cl * EP + 4 * c4);
-            *(float4 *)(outr + (int64_t)cl * g.n_out + 4 * c4) = v;
+            idl_store::store16((float4 *)(outr + (int64_t)cl * g.n_out + 4 * c4), v, wt);
         }
         return;
     }
@@ -255,7 +258,7 @@ __device__ __forceinline__ void l1p_body(const L1pArgs &g, const int bid, unsign
     for (int u = 0; u < 16; ++u) {
         const int idx = lane + 64 * u, rl = idx >> 4, c4 = idx & 15;
         const float4 v = *(const float4 *)(img + rl * EP + 4 * c4);
-        *(float4 *)(out + (int64_t)rl * g.m + 4 * c4) = v;
+        idl_store::store16((float4 *)(out + (int64_t)rl * g.m + 4 * c4), v, wt);
     }
 }
 

@@ -265,6 +265,7 @@ int idl_opt_step_gather_wgrad(int kind, int count, float *const *params, const f
         IDL_REQUIRE(pair_idx && mean && scale && y && n >= 1 && f >= 1 && batch >= 1 && n_pairs >= 0, "opt_step: bad gather arguments");
         IDL_REQUIRE(batch_advance == 0, "opt_step: the launch that assembles the next batch reads ctl[1] and cannot advance it");
         g = idl_dev::GatherArgs{feats, n, f, view_stride, pair_idx, ctl + 1, batch, n_pairs, mean, scale, inv_scale, y};
+        g.wt = idl_store::wt_mask();
     }
     int nb_total = 0;
     for (int i = 0; i < count; ++i) {

@@ -54,6 +54,8 @@ int idl_split_planes(const float *src, int64_t n, int exponent, void *hi, void *
 
 int idl_l1_planes_parts(void) { return l1p_dev::KSPLIT; }
 
+int idl_store_wt_mask(void) { return idl_store::wt_mask(); }
+
 int idl_l1_planes_supported(int m, int n_out, int n_in) { return l1p_dev::supported(m, n_out, n_in) ? 1 : 0; }
 
 static int l1_planes_impl(const void *w_hi, const void *w_lo, int ld_w, const void *x_hi, const void *x_lo, int ld_x, int m, int n_out, int n_in, float *part, int rows,
@@ -65,7 +67,7 @@ static int l1_planes_impl(const void *w_hi, const void *w_lo, int ld_w, const vo
     IDL_REQUIRE(((((uintptr_t)w_hi) | ((uintptr_t)w_lo) | ((uintptr_t)x_hi) | ((uintptr_t)x_lo) | ((uintptr_t)part)) & 15u) == 0, "l1_planes: buffers must be 16-byte aligned");
     static const int l1p_dbg = idl::dev_env("l1p_dbg") ? atoi(idl::dev_env("l1p_dbg")) : 0;      // (timing ablations; l1_planes_device.h)
     l1p_dev::L1pArgs a{(const uint16_t *)w_hi, (const uint16_t *)w_lo, (const uint16_t *)x_hi, (const uint16_t *)x_lo, part, m, n_out, n_in,
-                       (n_out / l1p_dev::TM) * (m / l1p_dev::TN) * l1p_dev::KSPLIT, ld_w, ld_x, l1p_dbg, rows};
+                       (n_out / l1p_dev::TM) * (m / l1p_dev::TN) * l1p_dev::KSPLIT, ld_w, ld_x, l1p_dbg, rows, idl_store::wt_mask()};
     if (void *plan = idl::take_plan()) {          // recorded, not launched (idl_plan_begin): several voters in one launch, train_step.hip
         idl::fill_plan(plan, idl::PLAN_L1_PLANES, 0, dim3((unsigned)a.n_tiles), l1p_dev::THREADS, l1p_dev::LDS_BYTES, a);
         return IDL_OK;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "planes.h"
+#include "store_policy.h"
 
 namespace idl_dev {
 
@@ -36,6 +37,7 @@ struct GatherArgs {
     int64_t base_add;           // added to *base (a launch that assembles the batch AFTER the one the offset points at)
     uint16_t *yh, *yl;          // optional (gather_tile only): the batch ALSO as two fp16 planes [2 batch][f] (planes.h, scale 2^X_EXP)
     int *over;                  // ... and the flag raised when an entry left the planes' range (|x| > 8 125: clamped in the planes)
+    int wt;                     // store_policy.h: idl_store::WT_NEXT_PLANES makes gather_tile's stores write-through
 };
 
 // one workgroup copies + standardises one output row; rows [0, batch) are the "true" halves, [batch, 2*batch) the "modified" ones
@@ -111,6 +113,10 @@ __device__ __forceinline__ void gather_tile(const GatherArgs &g, int64_t blk, in
     const int64_t rg = blk / slices, i = (blk - rg * slices) * 256 + tid;
     if (i >= n4) return;
     const int64_t base = (g.base ? *g.base : 0) + g.base_add;
+    // write-through planes leave as 16 bytes a lane: lanes i, i + 1 (i even) pair up (store_policy.h).  n4 odd would leave the last lane of a row
+    // without a partner and every other row 8 bytes off a 16-byte boundary: those rows keep the plain 8-byte stores
+    const bool wt = (g.wt & idl_store::WT_NEXT_PLANES) != 0;
+    const bool paired = wt && (n4 & 1) == 0 && ((((uintptr_t)g.yh) | ((uintptr_t)g.yl)) & 15u) == 0;
     const float4 *src4[R];
     float4 vv[R];
 #pragma unroll
@@ -144,13 +150,18 @@ __device__ __forceinline__ void gather_tile(const GatherArgs &g, int64_t blk, in
             o.x = std_f32(v.x, mu[0], sc[0]); o.y = std_f32(v.y, mu[1], sc[1]);
             o.z = std_f32(v.z, mu[2], sc[2]); o.w = std_f32(v.w, mu[3], sc[3]);
         }
-        if (g.y != nullptr) ((float4 *)(g.y + (rg * R + u) * g.f))[i] = o;      // (NULL with planes: every consumer of the batch reads the planes)
+        if (g.y != nullptr) idl_store::store16((float4 *)(g.y + (rg * R + u) * g.f) + i, o, wt);      // (NULL with planes: every consumer of the batch reads the planes)
         if (g.yh != nullptr) {
             constexpr float ps = (float)(1 << idl_planes::X_EXP);
             uint2 h, l;
             if (idl_planes::split4(o.x * ps, o.y * ps, o.z * ps, o.w * ps, h, l) && g.over != nullptr) *g.over = 1;
-            ((uint2 *)(g.yh + (rg * R + u) * g.f))[i] = h;
-            ((uint2 *)(g.yl + (rg * R + u) * g.f))[i] = l;
+            if (paired) {
+                const bool odd = (tid & 1) != 0;           // (= i's parity: a slice starts at a multiple of 256)
+                idl_store::store16_wt((uint2 *)((odd ? g.yl : g.yh) + (rg * R + u) * g.f) + (i - (odd ? 1 : 0)), idl_store::pair_planes(h, l, odd));
+            } else {
+                ((uint2 *)(g.yh + (rg * R + u) * g.f))[i] = h;
+                ((uint2 *)(g.yl + (rg * R + u) * g.f))[i] = l;
+            }
         }
     }
 }

@@ -856,7 +856,7 @@ static int small_wgrad_launch(float *const *params, float *const *grads, float *
     a.gather_end = 0;
     if (gather_batch > 0) {
         a.gth = idl_dev::GatherArgs{feats, n, f, view_stride, pair_idx, ctl + 1, gather_batch, n_pairs, mean, scale, inv_scale, y_next, 0,
-                                    nullptr, nullptr, nullptr};
+                                    nullptr, nullptr, nullptr, idl_store::wt_mask()};
         a.gather_end = (int)idl_dev::gather_blocks(f, gather_batch);
         end += (a.gather_end + 1) / 2;
     }

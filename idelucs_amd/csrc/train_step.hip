@@ -1467,7 +1467,7 @@ static int riders_of(const char *who, const idl_next_batch_t *nb, Riders &out)
     if (!(nb->pair_idx && nb->mean && nb->scale && (nb->y || yh) && nb->n >= 1 && nb->f >= 4 && (nb->f & 3) == 0 && nb->batch >= 1 && nb->n_pairs >= 0))
         return bad("bad gather arguments (4 | f)");
     out.g = idl_dev::GatherArgs{nb->feats, nb->n, nb->f, nb->view_stride, nb->pair_idx, nb->base, nb->batch, nb->n_pairs, nb->mean, nb->scale, nb->inv_scale, nb->y,
-                                nb->base_add, yh, yl, nb->overflow_flag};
+                                nb->base_add, yh, yl, nb->overflow_flag, idl_store::wt_mask()};
     const int64_t ng = idl_dev::gather_tiles<MID_GATHER_ROWS>(nb->f, nb->batch);
     out.t0 = (int)(ng * nb->part / nb->parts); out.t1 = (int)(ng * nb->part_end / nb->parts);
     return IDL_OK;
@@ -1829,6 +1829,7 @@ int idl_rmsprop_step(const idl_opt_tail_t *tail, const idl_next_batch_t *next_ba
         IDL_REQUIRE(nb->part == 0 && nb->part_end == nb->parts, "rmsprop_step: the optimizer launch assembles the whole batch, not a share");
         IDL_REQUIRE(nb->pair_idx && nb->mean && nb->scale && nb->y && nb->n >= 1 && nb->f >= 1 && nb->batch >= 1 && nb->n_pairs >= 0, "rmsprop_step: bad gather arguments");
         g = idl_dev::GatherArgs{nb->feats, nb->n, nb->f, nb->view_stride, nb->pair_idx, tail->ctl + 1, nb->batch, nb->n_pairs, nb->mean, nb->scale, nb->inv_scale, nb->y};
+        g.wt = idl_store::wt_mask();
     }
     return rmsprop_launch(*tail, g, stream, TailCarrier{});
 }
@@ -1931,6 +1932,7 @@ int idl_wgrad_xplanes_rms(const void *dy_hi, const void *dy_lo, int *dy_scale, c
     x.tiles_m = n_out / wgp_dev::TM; x.tiles = x.tiles_m * (n_in / wgp_dev::TN);
     static const int wgp_dbg = idl::dev_env("wgp_dbg") ? atoi(idl::dev_env("wgp_dbg")) : 0;      // (timing ablations; wgrad_planes_device.h)
     x.dbg = wgp_dbg;
+    x.wt = idl_store::wt_mask();
     TailCarrier by;
     by.xp = &x;
     return rmsprop_launch(*tail, idl_dev::GatherArgs{}, stream, by);

@@ -43,6 +43,7 @@ extern "C" int idl_wgrad_rmsprop_xplanes(const void *dy_hi, const void *dy_lo, i
     a.tiles_m = n_out / TM; a.tiles = a.tiles_m * (n_in / TN);
     static const int wgp_dbg = idl::dev_env("wgp_dbg") ? atoi(idl::dev_env("wgp_dbg")) : 0;      // (timing ablations; wgrad_planes_device.h)
     a.dbg = wgp_dbg;
+    a.wt = idl_store::wt_mask();
     if (const int rc = idl::raise_dyn_lds<wgrad_dplanes_kernel>(LDS_BYTES + 16)) return rc;
     hipLaunchKernelGGL(wgrad_dplanes_kernel, dim3((unsigned)a.tiles), dim3(NT), LDS_BYTES + 16, (hipStream_t)stream, a);      // (+ 16: the tail's words)
     IDL_HIP_TRY(hipGetLastError());

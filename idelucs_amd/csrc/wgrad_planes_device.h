@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "planes.h"
+#include "store_policy.h"
 #include "wgrad_device.h"
 
 namespace wgp_dev {
@@ -43,6 +44,7 @@ struct XpArgs {
     const float *hyper;
     int m, n_out, n_in, ldx, tiles_m, tiles;
     int dbg;                               // diagnostics (IDELUCS_DEV=wgp_dbg; wrong results): 8 no epilogue
+    int wt;                                // store_policy.h: idl_store::WT_W_V (W, V) and WT_W_PLANES (W's planes) make those stores write-through
 };
 
 __device__ __forceinline__ int swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }      // cdna_hip_programming.md T10 (b)
@@ -276,6 +278,9 @@ __device__ __forceinline__ void dplanes_body(const XpArgs &a, unsigned char *sme
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     bool over = false;
+    // (W's planes write-through: lanes c4, c4 + 1 (c4 even) of a row pair up for 16-byte stores, store_policy.h; 8 | n_in, wgrad_xplanes_supported)
+    const bool wt_wv = (a.wt & idl_store::WT_W_V) != 0;
+    const bool wt_pl = (a.wt & idl_store::WT_W_PLANES) != 0 && ((((uintptr_t)a.wh) | ((uintptr_t)a.wl)) & 15u) == 0;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int idx = lane + 64 * u, rl = idx >> 4, c4 = idx & 15;
@@ -286,13 +291,18 @@ __device__ __forceinline__ void dplanes_body(const XpArgs &a, unsigned char *sme
             f32x4 w4 = w_pre[u], v4 = v_pre[u];
 #pragma unroll
             for (int e = 0; e < 4; ++e) { float w = w4[e], v = v4[e]; wg_dev::rms_update(g4[e], w, v, hy); w4[e] = w; v4[e] = v; }
-            *(f32x4 *)(a.W + at) = w4;
-            *(f32x4 *)(a.V + at) = v4;
+            idl_store::store16((f32x4 *)(a.W + at), w4, wt_wv);
+            idl_store::store16((f32x4 *)(a.V + at), v4, wt_wv);
             if (a.wh != nullptr) {
                 constexpr float ps = (float)(1 << idl_planes::W_EXP);
                 uint2 h, l2;
                 over |= idl_planes::split4(w4[0] * ps, w4[1] * ps, w4[2] * ps, w4[3] * ps, h, l2);
-                *(uint2 *)(a.wh + at) = h; *(uint2 *)(a.wl + at) = l2;
+                if (wt_pl) {
+                    const bool odd = (lane & 1) != 0;          // (= c4's parity)
+                    idl_store::store16_wt((odd ? a.wl : a.wh) + (at - (odd ? 4 : 0)), idl_store::pair_planes(h, l2, odd));
+                } else {
+                    *(uint2 *)(a.wh + at) = h; *(uint2 *)(a.wl + at) = l2;
+                }
             }
         }
     }
