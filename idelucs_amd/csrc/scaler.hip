@@ -3,10 +3,16 @@
 // All three are HBM-streaming kernels over the row-major feature store [rows, f]:
 //   col_stats    : StandardScaler.fit as the reference uses it (idelucs/utils.py:357-359 on the
 //                  float32 "true" view, :404-405 on float64 un-mutated rows): float64 mean and
-//                  population variance per column in ONE pass over the data -- sums of (x - x0) and
-//                  (x - x0)^2 with x0 = the column's first row, so the variance formula has nothing
-//                  to cancel -- within 1e-15 relative of sklearn's two-pass _incremental_mean_and_var
-//                  (exactly 0 -> scale 1 for a constant column), deterministic order.
+//                  population variance per column in ONE pass over the data -- sums of t = x - x0 and
+//                  t^2 with the shift x0 = the column's FIRST ROW (not its mean), deterministic order.
+//                  var = (sum t^2 - (sum t)^2 / n) / n then cancels by kappa = 1 + (x0 - mean)^2 / var,
+//                  which is near 1 when row 0 is a typical row and at most n + 1 when it is the one
+//                  outlier.  With gamma = (rows_per_block + ceil(blocks / 16) + 20) * 2^-53 (the longest
+//                  chain of additions) the relative error of the scale against the exact one (and so
+//                  against sklearn's two-pass _incremental_mean_and_var) is at most
+//                  1.5 * gamma * kappa + 4 * 2^-53, that of the mean at most gamma * mean|x - x0| +
+//                  4 * 2^-53 * |mean| (derivation: tests/scaler_ref.py; checked per column by
+//                  tests/test_gpu_scaler.py).  A constant column gives exactly 0 -> scale 1.
 //   standardise  : StandardScaler.transform (utils.py:361-366): (x - mean) then / scale, each
 //                  evaluated in float64 and rounded to the array's type.
 //   gather_pairs : AugmentedDataset/DataLoader batch collation (utils.py:370-389, :422-429) on the
