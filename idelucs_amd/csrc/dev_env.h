@@ -34,4 +34,13 @@ inline const char *dev_env(const char *name)
     return nullptr;
 }
 
+// an integer knob: `def` where the key is not set or its value lies outside [lo, hi]
+inline int dev_env_int(const char *name, int def, int lo, int hi)
+{
+    const char *e = dev_env(name);
+    if (e == nullptr) return def;
+    const int v = atoi(e);
+    return v >= lo && v <= hi ? v : def;
+}
+
 }  // namespace idl

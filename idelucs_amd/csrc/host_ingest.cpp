@@ -1,4 +1,6 @@
-// host_ingest.cpp -- FASTA reader, check_sequence and the 2-bit slot packer (host side; no GPU).
+// host_ingest.cpp -- FASTA reader, check_sequence and the 2-bit slot packer (host side; no GPU): the mapping cache, the record
+// tables of the two readers, the one-pass reader's copies and the C entry points.  Bytes -> slots is fasta_pack.h, the reader's
+// threads are ingest_threads.h.
 //
 // Restates, as one pass over the file bytes, what the reference does with Python line iteration:
 //   idelucs/utils.py:137-188 / :224-260  record state machine ('#' skipped, '>' flushes the current
@@ -6,66 +8,27 @@
 //                                        .strip()ped and joined, unconditional flush at EOF)
 //   idelucs/utils.py:26-51               check_sequence (header checks, translate, delete, validate)
 // and produces the packed slot layout documented in include/idelucs_hip.h.
+#include <fcntl.h>
 #include <stdint.h>
-#include "dev_env.h"
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <memory>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "common.h"
-
-namespace {
-
-struct Tables {
-    uint8_t translate[256];  // utils.py:42-43 basemask; 0 = deleted (" \t\n\r"), 1 = invalid byte
-    uint8_t code[256];       // kmers.pyx:19-34: 'A'0 'C'1 'G'2 'T'3, everything else 4
-    Tables()
-    {
-        for (int i = 0; i < 256; ++i) { translate[i] = 1; code[i] = 4; }
-        const char *from = "acgtuUswkmyrbdhvnSWKMYRBDHV-";
-        const char *to = "ACGTTTNNNNNNNNNNNNNNNNNNNNNN";
-        for (const char *c = "ACGTN"; *c; ++c) translate[(uint8_t)*c] = (uint8_t)*c;
-        for (int i = 0; from[i]; ++i) translate[(uint8_t)from[i]] = (uint8_t)to[i];
-        translate[(uint8_t)' '] = translate[(uint8_t)'\t'] = translate[(uint8_t)'\n'] = translate[(uint8_t)'\r'] = 0;
-        code[(uint8_t)'A'] = 0; code[(uint8_t)'C'] = 1; code[(uint8_t)'G'] = 2; code[(uint8_t)'T'] = 3;
-    }
-};
-const Tables T;
-
-inline bool py_bytes_space(uint8_t b) { return b == ' ' || (b >= 9 && b <= 13); }  // bytes.strip() set
-
-// chr(b) as UTF-8 (the reference formats chr(stripped[0]) into the message, utils.py:47-49)
-std::string chr_utf8(uint8_t b)
-{
-    std::string s;
-    if (b < 0x80) s.push_back((char)b);
-    else { s.push_back((char)(0xC0 | (b >> 6))); s.push_back((char)(0x80 | (b & 0x3F))); }
-    return s;
-}
-
-void pack_one(const uint8_t *seq, int64_t len, uint8_t *codes, uint8_t *mask)
-{
-    const int64_t slots = (len + 63) / 64;
-    uint32_t *cw = (uint32_t *)codes;
-    uint32_t *mw = (uint32_t *)mask;
-    for (int64_t w = 0; w < slots * 4; ++w) {  // 16 bases per code word
-        uint32_t c = 0, m = 0;
-        const int64_t base = w * 16;
-        for (int j = 0; j < 16; ++j) {
-            const int64_t i = base + j;
-            const unsigned v = (i < len) ? T.code[seq[i]] : 4u;
-            if (v == 4u) m |= 0x8000u >> j;
-            else c |= (uint32_t)v << (30 - 2 * j);
-        }
-        cw[w] = c;
-        if ((w & 1) == 0) mw[w >> 1] = m << 16;
-        else mw[w >> 1] |= m;
-    }
-}
-
-}  // namespace
+#include "dev_env.h"
+#include "fasta_pack.h"
+#include "ingest_threads.h"
 
 // ------------------------------------------------------------------------------------------------
 // FASTA reader.  The reference walks the file line by line in Python (utils.py:137-188, :224-260); here
@@ -77,24 +40,6 @@ void pack_one(const uint8_t *seq, int64_t len, uint8_t *codes, uint8_t *mask)
 // (`lines` is only reset on a flush, utils.py:184/257); the first failing record in file order decides
 // the error.
 // ------------------------------------------------------------------------------------------------
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <sys/syscall.h>
-#include <unistd.h>
-
-#include <pthread.h>
-#include <sched.h>
-
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <thread>
-
 namespace {
 
 struct Rec {
@@ -103,599 +48,40 @@ struct Rec {
     int64_t len;             // cleaned length
 };
 
-// CPUs the process may actually use: the cgroup's CPU quota (cgroup v2 cpu.max, v1 cfs quota / period) where one is set, else 0.
-// The process's own cgroup comes from /proc/self/cgroup (without a cgroup namespace -- systemd, Slurm -- the limit sits
-// in a nested directory, not in /sys/fs/cgroup itself); every level up to the root is read, the tightest quota counts.
-int cgroup_cpus()
+// chr(b) as UTF-8 (the reference formats chr(stripped[0]) into the message, utils.py:47-49)
+std::string chr_utf8(uint8_t b)
 {
-    auto quota_of = [](const std::string &dir, bool v2) -> double {
-        long quota = -1, period = -1;
-        if (v2) {
-            if (FILE *f = fopen((dir + "/cpu.max").c_str(), "r")) {
-                char q[32] = {0};
-                if (fscanf(f, "%31s %ld", q, &period) == 2 && strcmp(q, "max") != 0) quota = atol(q);
-                fclose(f);
-            }
-        } else {
-            if (FILE *g = fopen((dir + "/cpu.cfs_quota_us").c_str(), "r")) { if (fscanf(g, "%ld", &quota) != 1) quota = -1; fclose(g); }
-            if (FILE *g = fopen((dir + "/cpu.cfs_period_us").c_str(), "r")) { if (fscanf(g, "%ld", &period) != 1) period = -1; fclose(g); }
-        }
-        return (quota > 0 && period > 0) ? (double)quota / (double)period : 0.0;
-    };
-    std::string v2_path = "/", v1_path = "/";
-    if (FILE *f = fopen("/proc/self/cgroup", "r")) {
-        char line[1024];
-        while (fgets(line, sizeof(line), f)) {
-            line[strcspn(line, "\n")] = 0;
-            const char *c1 = strchr(line, ':');
-            const char *c2 = c1 ? strchr(c1 + 1, ':') : nullptr;
-            if (!c2) continue;
-            const std::string ctrl(c1 + 1, c2);
-            if (ctrl.empty()) v2_path = c2 + 1;                                            // "0::/path"
-            else if (ctrl == "cpu" || ctrl == "cpu,cpuacct" || ctrl == "cpuacct,cpu") v1_path = c2 + 1;
-        }
-        fclose(f);
-    }
-    double best = 0.0;
-    auto walk = [&](const std::string &root, std::string rel, bool v2) {
-        for (;;) {
-            const double q = quota_of(root + (rel == "/" ? "" : rel), v2);
-            if (q > 0.0 && (best == 0.0 || q < best)) best = q;
-            if (rel == "/" || rel.empty()) break;
-            const size_t cut = rel.find_last_of('/');
-            rel = (cut == 0 || cut == std::string::npos) ? "/" : rel.substr(0, cut);
-        }
-    };
-    walk("/sys/fs/cgroup", v2_path, true);
-    walk("/sys/fs/cgroup/cpu", v1_path, false);
-    return best > 0.0 ? (int)(best + 0.999) : 0;
+    std::string s;
+    if (b < 0x80) s.push_back((char)b);
+    else { s.push_back((char)(0xC0 | (b >> 6))); s.push_back((char)(0x80 | (b & 0x3F))); }
+    return s;
 }
 
-// Reader threads.  IDELUCS_THREADS overrides.  Default (round 4, profiles/r04_ingest_threads.txt: the 1 GB cfg2 file on a 256-thread
-// host whose cgroup grants 16 CPUs): parse + pack 11.0 ms with 16 threads, 8.2 with 32, 7.6 with 48-64, but with the H2D copies in
-// flight 11.4 / 12.0 / 13.6 and ingest-to-features 17.9 / 14.3 / 15.3 -- the threads block in page faults and in the copy calls, so
-// twice the CPU quota pays and more does not.  Hence min(32, hardware threads, 2 x cgroup quota), and THAT is shared out over the
-// ranks of the node (LOCAL_WORLD_SIZE: every rank of a multi-GPU job reads the file itself).
-int n_threads()
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// utils.py:37-40 header checks.  (A record without id bytes passes: that is also the empty file's one record, whose buf is NULL
+// and must not reach memchr.)
+int header_kind(const uint8_t *buf, const Rec &r)
 {
-    if (const char *e = getenv("IDELUCS_THREADS")) { const int t = atoi(e); if (t >= 1 && t <= 256) return t; }
-    static const int chosen = [] {
-        int t = (int)std::thread::hardware_concurrency();
-        if (t <= 0) t = 1;
-        if (const int q = cgroup_cpus(); q > 0 && 2 * q < t) t = 2 * q;
-        if (t > 32) t = 32;
-        int ranks = 1;
-        if (const char *e = getenv("LOCAL_WORLD_SIZE")) { const int r = atoi(e); if (r >= 1 && r <= 64) ranks = r; }
-        t /= ranks;
-        return t < 1 ? 1 : t;
-    }();
-    return chosen;
+    if (r.id_e <= r.id_b) return REC_OK;
+    const uint8_t h0 = buf[r.id_b];
+    if (h0 == '>' || h0 == '#' || py_bytes_space(h0) || (h0 >= 0x1c && h0 <= 0x1f)) return REC_BAD_HEADER;
+    if (memchr(buf + r.id_b, '\t', r.id_e - r.id_b)) return REC_TAB;
+    return REC_OK;
 }
 
-size_t par_min_bytes()                  // files smaller than this are handled by one thread
+// the reference's message for a record that failed with `kind` (byte: the invalid one of REC_BAD_BASE); returns the error code
+int report_bad_record(const uint8_t *buf, const Rec &r, int kind, uint8_t byte)
 {
-    if (const char *e = idl::dev_env("par_min")) return (size_t)atoll(e);
-    return (size_t)1 << 22;
-}
-
-// ---- NUMA placement of the reader (round 5; VERDICT r4 #1a).  Two things have a place: the file's page-cache pages (1 GB read) and
-// the pinned arenas (375 MB written, then read by the DMA engine) -- hipHostMalloc puts pinned memory on the node nearest to the
-// current device (ROCr's default without hipHostMallocNumaUser).  Measured on the pool's 2-socket boxes (profiles/r05_ingest_numa.txt,
-// 1 GB cfg2 file, 32 threads): with file and GPU on one node, parse + pack 8.2 ms unbound, 6.9 bound there, 14.6 bound to the other
-// node; with the file on the other node than the GPU, ingest-to-features 14.4 ms beside the GPU and 10.8 beside the FILE -- reads
-// across the socket link cost, posted writes hardly.  The threads of a job that copies to a device are therefore bound, for the
-// job, to the node of the file's pages (file_numa_node below) and, when the file does not say, to the device's node (workers
-// keep the binding, the caller's own is restored).  IDELUCS_DEV=numa=off switches it off, =device ignores the file, =<node> forces a node.
-struct CpuBind {
-    cpu_set_t set;                      // the node's CPUs open to this process
-    std::vector<cpu_set_t> per_thread;  // thread i of a job: the hardware threads of ONE core, cores dealt round-robin over the node's L3 domains
-    int node = -1;
-    bool on = false;
-    const cpu_set_t &of(int i) const { return per_thread.empty() ? set : per_thread[(size_t)i % per_thread.size()]; }
-};
-
-int first_cpu_of_list(const char *path)      // first number of a sysfs cpu list ("64-71,192-199" -> 64), -1 when unreadable
-{
-    FILE *f = fopen(path, "r");
-    if (!f) return -1;
-    int v = -1;
-    if (fscanf(f, "%d", &v) != 1) v = -1;
-    fclose(f);
-    return v;
-}
-
-// OPT-IN (IDELUCS_DEV=numa_pin=1): one core per reader thread, spread over the L3 domains, instead of the node's whole CPU set for every
-// thread.  Built because the pool's threads, woken where they last ran, finished between 4.6 and 8.7 ms where freshly created ones
-// took 4.8 .. 6.1; measured on three boxes (gpurun_out/r05_c..e, kept as profiles/r05_ingest_ab.txt): the pinned threads do finish
-// closer together (9.1 .. 11.9 against 5.4 .. 12.1 ms) but the LAST one no earlier, and every job starts 1.3 ms late -- a thread
-// that may run on two CPUs only waits for them (deep idle, or somebody else's time slice) where the scheduler would have taken any
-// idle CPU of the node.  Ingest-to-features 14.5 / 11.8 / 16.3 ms pinned against 13.5 / 11.6 / 16.3 node-wide: node-wide is the default.
-void spread_over_cores(CpuBind *b)
-{
-    const char *e = idl::dev_env("numa_pin");
-    if (!(e && atoi(e) == 1)) return;
-    struct Core { int l3, first; cpu_set_t cpus; };
-    std::vector<Core> cores;
-    for (int c = 0; c < CPU_SETSIZE; ++c) {
-        if (!CPU_ISSET(c, &b->set)) continue;
-        char path[128];
-        snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", c);
-        const int first = first_cpu_of_list(path);
-        if (first < 0) return;                         // no topology to read: keep the node-wide set
-        bool seen = false;
-        for (Core &k : cores) if (k.first == first) { CPU_SET(c, &k.cpus); seen = true; break; }
-        if (seen) continue;
-        snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", c);
-        Core k;
-        k.first = first;
-        k.l3 = first_cpu_of_list(path);
-        CPU_ZERO(&k.cpus);
-        CPU_SET(c, &k.cpus);
-        cores.push_back(k);
-    }
-    if (cores.size() < 2) return;
-    std::vector<int> l3s;
-    for (const Core &k : cores) if (std::find(l3s.begin(), l3s.end(), k.l3) == l3s.end()) l3s.push_back(k.l3);
-    std::vector<size_t> next(l3s.size(), 0);
-    std::vector<std::vector<size_t>> by_l3(l3s.size());
-    for (size_t i = 0; i < cores.size(); ++i) by_l3[(size_t)(std::find(l3s.begin(), l3s.end(), cores[i].l3) - l3s.begin())].push_back(i);
-    for (size_t placed = 0, g = 0; placed < cores.size(); g = (g + 1) % l3s.size()) {
-        if (next[g] < by_l3[g].size()) { b->per_thread.push_back(cores[by_l3[g][next[g]++]].cpus); ++placed; }
-    }
-}
-
-bool parse_cpulist(const char *path, cpu_set_t *out)
-{
-    FILE *f = fopen(path, "r");
-    if (!f) return false;
-    char buf[4096] = {0};
-    const size_t got = fread(buf, 1, sizeof(buf) - 1, f);
-    fclose(f);
-    if (got == 0) return false;
-    CPU_ZERO(out);
-    const char *p = buf;
-    while (*p) {
-        while (*p == ',' || *p == ' ' || *p == '\n') ++p;
-        if (!*p) break;
-        char *e = nullptr;
-        const long a = strtol(p, &e, 10);
-        if (e == p) return false;
-        long b = a;
-        p = e;
-        if (*p == '-') { b = strtol(p + 1, &e, 10); if (e == p + 1) return false; p = e; }
-        for (long c = a; c <= b && c < CPU_SETSIZE; ++c) if (c >= 0) CPU_SET((int)c, out);
-    }
-    return CPU_COUNT(out) > 0;
-}
-
-// the CPUs of the NUMA node device `dev` hangs off, within what this thread may run on; .on = false when there is nothing to do
-CpuBind bind_for_device(int dev, int want_threads, int file_node = -1)
-{
-    CpuBind b;
-    const char *env = idl::dev_env("numa");
-    if (env && (strcmp(env, "off") == 0 || strcmp(env, "-1") == 0)) return b;
-    int node = -1;
-    if (env && *env >= '0' && *env <= '9') node = atoi(env);
-    else if (file_node >= 0 && !(env && strcmp(env, "device") == 0)) node = file_node;      // beside the file (IDELUCS_DEV=numa=device: beside the GPU)
-    else {
-        char id[64] = {0};
-        if (dev < 0 || hipDeviceGetPCIBusId(id, (int)sizeof(id) - 1, dev) != hipSuccess) return b;
-        for (char *c = id; *c; ++c) if (*c >= 'A' && *c <= 'F') *c = (char)(*c - 'A' + 'a');
-        char path[160];
-        snprintf(path, sizeof(path), "/sys/bus/pci/devices/%s/numa_node", id);
-        FILE *f = fopen(path, "r");
-        if (!f) return b;
-        if (fscanf(f, "%d", &node) != 1) node = -1;
-        fclose(f);
-    }
-    if (node < 0) return b;                       // a single-node host (or a VM that does not say)
-    char path[96];
-    snprintf(path, sizeof(path), "/sys/devices/system/node/node%d/cpulist", node);
-    cpu_set_t nodeset, mine;
-    if (!parse_cpulist(path, &nodeset)) return b;
-    if (sched_getaffinity(0, sizeof(mine), &mine) != 0) return b;
-    CPU_AND(&b.set, &nodeset, &mine);
-    // too few CPUs of that node are open to this process (a cpuset on the other socket): leave the threads where they are
-    if (CPU_COUNT(&b.set) == 0 || (CPU_COUNT(&b.set) < CPU_COUNT(&mine) && CPU_COUNT(&b.set) * 2 < want_threads)) return b;
-    b.node = node;
-    const char *pin = idl::dev_env("numa_pin");
-    if (CPU_EQUAL(&b.set, &mine) && !(pin && atoi(pin) == 1)) return b;     // already there (one node, or an outer binding): leave the threads alone
-    b.on = true;
-    spread_over_cores(&b);
-    return b;
+    if (kind == REC_BAD_HEADER) { idl::set_error("Bad character in sequence header"); return IDL_ERR_HEADER; }
+    if (kind == REC_TAB) { idl::set_error("tab included in header"); return IDL_ERR_HEADER; }
+    const std::string id((const char *)buf + r.id_b, r.id_e - r.id_b);
+    idl::set_error("Invalid DNA byte in sequence %s: '%s'", id.c_str(), chr_utf8(byte).c_str());
+    return IDL_ERR_BASE;
 }
 
 int g_last_bind_node = -1;      // what the last job was bound to (idl_ingest_numa_node)
 int g_last_file_node = -1;      // ... and where it found the file's pages (-1: not asked, not resident, spread, or not permitted)
-
-// The NUMA node that holds the page-cache pages of a mapped file, or -1.  64 pages spread over the mapping: those that are
-// resident (mincore: no I/O is started for a cold file) are touched, so that they are in this process's page table, and asked for
-// their node (move_pages with a NULL target only reports; some container runtimes refuse it: -1 then).  A node counts when it
-// holds 3/4 of the resident samples and at least 48 of the 64 were resident.
-// Why it matters (profiles/r05_ingest_numa.txt, a 2-socket box, GPU on node 0, 1 GB cfg2 file): reading the file across the
-// socket link is what costs -- pages on node 0: reader on node 0 10.8 ms ingest-to-features, on node 1 20.0; pages on node 1:
-// reader on node 0 (beside the GPU and the pinned arenas) 14.4 ms, on node 1 (beside the FILE, writing the arenas remotely)
-// 10.8.  The reader therefore goes where the file is, and to the device's node only when the file does not say.
-int file_numa_node(const uint8_t *map, size_t size)
-{
-    const long psz = sysconf(_SC_PAGESIZE);
-    if (psz <= 0 || size < (size_t)psz * 256) return -1;
-    constexpr int S = 64;
-    void *pages[S];
-    int status[S];
-    int n = 0;
-    for (int i = 0; i < S; ++i) {
-        const size_t off = (size / S * (size_t)i) & ~((size_t)psz - 1);
-        unsigned char vec = 0;
-        if (mincore((void *)(map + off), (size_t)psz, &vec) != 0 || !(vec & 1)) continue;
-        (void)*(volatile const uint8_t *)(map + off);
-        pages[n++] = (void *)(map + off);
-    }
-    if (n < 48) return -1;
-    if (syscall(SYS_move_pages, 0, (unsigned long)n, pages, (const int *)nullptr, status, 0) != 0) return -1;
-    int count[64] = {0}, seen = 0;
-    for (int i = 0; i < n; ++i) if (status[i] >= 0 && status[i] < 64) { ++count[status[i]]; ++seen; }
-    for (int node = 0; node < 64; ++node) if (count[node] * 4 >= seen * 3 && seen >= 48) return node;
-    return -1;
-}
-
-// The reader's threads, kept between calls (round 5; VERDICT r4 #1b).  A run calls parallel_for seven times per file (scan, validate,
-// pack, export ...); with std::thread per call that was 31 thread creations each -- ~1 ms of the 8 ms parse at 32 threads, and
-// every new thread's first HIP call sets up its device state again.  Workers sleep on a condition variable; a job is
-// (generation, thread count, callable); the caller runs index 0 itself and waits for the others.  One job at a time (callers
-// from several host threads take turns).  The pool is never destroyed (threads blocked at process exit are the kernel's to
-// reap); a forked child starts with an empty pool (its parent's threads do not exist there).
-class ReaderPool {
-public:
-    static ReaderPool &get()
-    {
-        std::lock_guard<std::mutex> lk(inst_mu());
-        static const bool hooked = [] {       // fork: nobody holds the instance lock across it; the child drops the parent's pool
-            pthread_atfork([] { inst_mu().lock(); }, [] { inst_mu().unlock(); }, [] { inst() = nullptr; inst_mu().unlock(); });
-            return true;
-        }();
-        (void)hooked;
-        if (inst() == nullptr) inst() = new ReaderPool();
-        return *inst();
-    }
-    template <typename F>
-    void run(int nt, F &&fn, const CpuBind *bind = nullptr)
-    {
-        std::lock_guard<std::mutex> one_job(job_mu_);
-        std::function<void(int)> f = [&fn](int t) { fn(t); };
-        cpu_set_t before;
-        // the caller, for the length of the job: the node's whole set -- it usually runs there already, so nothing migrates (bound to
-        // one core like the workers it started its share 1.3 ms late: sched_setaffinity away from the current CPU waits for the
-        // migration thread)
-        const bool rebind = bind != nullptr && bind->on && sched_getaffinity(0, sizeof(before), &before) == 0 &&
-                            sched_setaffinity(0, sizeof(cpu_set_t), &bind->set) == 0;
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            while ((int)th_.size() < nt - 1) {
-                const int idx = (int)th_.size() + 1;
-                th_.emplace_back([this, idx] { worker(idx); });
-                th_.back().detach();
-            }
-            fn_ = &f;
-            nt_ = nt;
-            pending_ = nt - 1;
-            if (bind != nullptr && bind->on) { bind_ = *bind; ++bind_gen_; }
-            ++gen_;
-        }
-        cv_work_.notify_all();
-        fn(0);
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            cv_done_.wait(lk, [this] { return pending_ == 0; });
-            fn_ = nullptr;
-        }
-        if (rebind) (void)sched_setaffinity(0, sizeof(before), &before);
-    }
-    int threads() const { return (int)th_.size(); }
-
-private:
-    static ReaderPool *&inst() { static ReaderPool *p = nullptr; return p; }      // (the parent's pool is leaked in a forked child on purpose)
-    static std::mutex &inst_mu() { static std::mutex m; return m; }
-    void worker(int idx)
-    {
-        uint64_t seen = 0, bound = 0;
-        for (;;) {
-            std::function<void(int)> *f = nullptr;
-            cpu_set_t want;
-            bool move = false;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_work_.wait(lk, [&] { return gen_ != seen; });
-                seen = gen_;
-                if (idx < nt_) f = fn_;
-                if (f != nullptr && bind_gen_ != bound) { want = bind_.of(idx); bound = bind_gen_; move = true; }
-            }
-            if (f == nullptr) continue;              // this job uses fewer threads
-            if (move) (void)sched_setaffinity(0, sizeof(want), &want);      // (a worker keeps its node until a job names another)
-            (*f)(idx);
-            bool last;
-            { std::lock_guard<std::mutex> lk(mu_); last = --pending_ == 0; }
-            if (last) cv_done_.notify_one();
-        }
-    }
-    std::mutex job_mu_, mu_;
-    std::condition_variable cv_work_, cv_done_;
-    std::vector<std::thread> th_;
-    std::function<void(int)> *fn_ = nullptr;
-    int nt_ = 0, pending_ = 0;
-    uint64_t gen_ = 0, bind_gen_ = 0;
-    CpuBind bind_;
-};
-
-template <typename F>
-void parallel_for(int nt, F &&fn, const CpuBind *bind = nullptr)       // fn(thread index)
-{
-    if (nt <= 1) { fn(0); return; }
-    static const bool pooled = [] { const char *e = idl::dev_env("reader_pool"); return !(e && atoi(e) == 0); }();
-    if (pooled) { ReaderPool::get().run(nt, fn, bind); return; }
-    // IDELUCS_DEV=reader_pool=0: a thread per call and index (round 4's form, kept for A/B runs); new threads inherit the caller's CPUs
-    cpu_set_t before;
-    const bool rebind = bind != nullptr && bind->on && sched_getaffinity(0, sizeof(before), &before) == 0 &&
-                        sched_setaffinity(0, sizeof(cpu_set_t), &bind->set) == 0;
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back([&fn, t, bind, rebind]() { if (rebind) (void)sched_setaffinity(0, sizeof(cpu_set_t), &bind->of(t)); fn(t); });
-    fn(0);
-    for (auto &x : th) x.join();
-    if (rebind) (void)sched_setaffinity(0, sizeof(before), &before);
-}
-
-// streaming 2-bit packer (first base in the top pair of each word; invalid-mask bit 31-j per base)
-struct Packer {
-    uint32_t *cw, *mw;
-    uint32_t c = 0, m = 0;
-    int j = 0;
-    int64_t w = 0;
-    bool dirty = false;                // an invalid base (N) was pushed: the record's mask is more than its tail padding
-    inline void push(unsigned code)
-    {
-        if (code == 4u) { m |= 0x8000u >> j; dirty = true; }
-        else c |= (uint32_t)code << (30 - 2 * j);
-        if (++j == 16) flush_word();
-    }
-    inline void flush_word()
-    {
-        cw[w] = c;
-        if ((w & 1) == 0) mw[w >> 1] = m << 16; else mw[w >> 1] |= m;
-        ++w; c = 0; m = 0; j = 0;
-    }
-    void finish(int64_t slots)
-    {
-        if (j > 0) { for (int t = j; t < 16; ++t) m |= 0x8000u >> t; j = 16; flush_word(); }
-        while (w < slots * 4) { c = 0; m = 0xFFFFu; flush_word(); }
-    }
-};
-
-enum { REC_OK = 0, REC_BAD_HEADER = 1, REC_TAB = 2, REC_BAD_BASE = 3 };
-
-// Walk the sequence bytes of one record.  emit(byte) is called for every byte that survives strip (+ check_sequence's
-// delete table when `check`); returns REC_BAD_BASE with *bad = offending byte when `check` finds an invalid one.
-template <typename Emit>
-inline int walk_record(const uint8_t *buf, const Rec &r, int check, Emit &&emit, uint8_t *bad)
-{
-    const uint8_t *p = buf + r.data_b, *end = buf + r.data_e;
-    while (p < end) {
-        const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
-        const uint8_t *le = nl ? nl + 1 : end;
-        if (*p != '#' && *p != '>') {
-            const uint8_t *a = p, *b = le;
-            while (a < b && py_bytes_space(*a)) ++a;
-            while (b > a && py_bytes_space(b[-1])) --b;
-            if (check) {
-                for (; a < b; ++a) {
-                    const uint8_t t = T.translate[*a];
-                    if (t == 0) continue;
-                    if (t == 1) { *bad = *a; return REC_BAD_BASE; }
-                    emit(t);
-                }
-            } else {
-                for (; a < b; ++a) emit(*a);
-            }
-        }
-        p = le;
-    }
-    return REC_OK;
-}
-
-
-// ---- eight bases at a time (SWAR): the overwhelmingly common input is runs of upper-case A/C/G/T, for which neither the
-// translate table nor the per-base packer is needed.  Anything else falls back to the byte loop above, so the result is the same.
-inline uint64_t load8(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }      // byte 0 = first base (little endian)
-
-inline bool all_acgt8(uint64_t x)
-{
-    auto zero_bytes = [](uint64_t v) { const uint64_t L = 0x7F7F7F7F7F7F7F7FULL; return ~(((v & L) + L) | v | L); };               // exact: 0x80 in every byte of v that is 0
-    const uint64_t hit = zero_bytes(x ^ 0x4141414141414141ULL) | zero_bytes(x ^ 0x4343434343434343ULL) |
-                         zero_bytes(x ^ 0x4747474747474747ULL) | zero_bytes(x ^ 0x5454545454545454ULL);
-    return hit == 0x8080808080808080ULL;
-}
-
-inline uint32_t pack8(uint64_t x)           // 8 valid bases -> 16 bits, first base in the top pair, A0 C1 G2 T3
-{
-    uint64_t c = (x >> 1) & 0x0303030303030303ULL;                    // A0 C1 G3 T2
-    c ^= (c >> 1) & 0x0101010101010101ULL;                            // A0 C1 G2 T3
-    const uint64_t M = (1ull << 30) | (1ull << 20) | (1ull << 10) | 1ull;  // byte i of a 4-byte group -> bit pair 30 - 2 i (no two terms overlap)
-    const uint32_t p0 = (uint32_t)(((uint64_t)(uint32_t)c * M) >> 24) & 0xFFu;
-    const uint32_t p1 = (uint32_t)(((uint64_t)(uint32_t)(c >> 32) * M) >> 24) & 0xFFu;
-    return (p0 << 8) | p1;
-}
-
-// ---- the same with AVX2 where the host has it (runtime dispatch; the SWAR code above is the portable path)
-#if defined(__x86_64__)
-#include <immintrin.h>
-#define IDL_HAVE_AVX2_PATH 1
-inline bool host_has_avx2() { static const bool h = __builtin_cpu_supports("avx2"); return h; }
-
-__attribute__((target("avx2"))) inline bool all_acgt32_avx2(const uint8_t *p)
-{
-    const __m256i v = _mm256_loadu_si256((const __m256i *)p);
-    const __m256i ok = _mm256_or_si256(_mm256_or_si256(_mm256_cmpeq_epi8(v, _mm256_set1_epi8('A')), _mm256_cmpeq_epi8(v, _mm256_set1_epi8('C'))),
-                                       _mm256_or_si256(_mm256_cmpeq_epi8(v, _mm256_set1_epi8('G')), _mm256_cmpeq_epi8(v, _mm256_set1_epi8('T'))));
-    return (uint32_t)_mm256_movemask_epi8(ok) == 0xFFFFFFFFu;
-}
-
-// number of leading 32-byte blocks of [a, b) that are pure upper-case A/C/G/T
-__attribute__((target("avx2"))) inline int64_t acgt_run32_avx2(const uint8_t *a, const uint8_t *b)
-{
-    int64_t k = 0;
-    while (b - a >= 32 && all_acgt32_avx2(a)) { a += 32; ++k; }
-    return k;
-}
-
-// 32 valid bases -> two code words (16 bases each, first base in the top pair, A0 C1 G2 T3)
-__attribute__((target("avx2"))) inline void pack32_avx2(const uint8_t *p, uint32_t *w)
-{
-    const __m256i v = _mm256_loadu_si256((const __m256i *)p);
-    __m256i c = _mm256_and_si256(_mm256_srli_epi16(v, 1), _mm256_set1_epi8(3));                  // A0 C1 G3 T2
-    c = _mm256_xor_si256(c, _mm256_and_si256(_mm256_srli_epi16(c, 1), _mm256_set1_epi8(1)));     // A0 C1 G2 T3
-    const __m256i p2 = _mm256_maddubs_epi16(c, _mm256_set1_epi16(0x0104));      // bytes (b0, b1) -> b0 * 4 + b1 in a 16-bit lane
-    const __m256i p4 = _mm256_madd_epi16(p2, _mm256_set1_epi32(0x00010010));     // 16-bit (q0, q1) -> q0 * 16 + q1 in a 32-bit lane: 4 bases, first on top
-    // the low byte of each 32-bit lane is one packed byte; a word wants its 4 bytes with the FIRST one most significant
-    const __m256i sh = _mm256_setr_epi8(12, 8, 4, 0, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-                                        12, 8, 4, 0, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1);
-    const __m256i g = _mm256_shuffle_epi8(p4, sh);
-    w[0] = (uint32_t)_mm256_extract_epi32(g, 0);
-    w[1] = (uint32_t)_mm256_extract_epi32(g, 4);
-}
-
-// ---- and with AVX-512 a whole slot at a time: 64 valid bases -> the slot's four code words in one 16-byte store
-inline bool host_has_avx512() { static const bool h = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512bw"); return h; }
-
-__attribute__((target("avx512f,avx512bw"))) inline bool pack64_avx512(const uint8_t *p, uint32_t *w4)
-{
-    const __m512i v = _mm512_loadu_si512((const void *)p);
-    const __mmask64 ok = _mm512_cmpeq_epi8_mask(v, _mm512_set1_epi8('A')) | _mm512_cmpeq_epi8_mask(v, _mm512_set1_epi8('C')) |
-                         _mm512_cmpeq_epi8_mask(v, _mm512_set1_epi8('G')) | _mm512_cmpeq_epi8_mask(v, _mm512_set1_epi8('T'));
-    if (ok != ~(__mmask64)0) return false;
-    __m512i c = _mm512_and_si512(_mm512_srli_epi16(v, 1), _mm512_set1_epi8(3));                  // A0 C1 G3 T2
-    c = _mm512_xor_si512(c, _mm512_and_si512(_mm512_srli_epi16(c, 1), _mm512_set1_epi8(1)));     // A0 C1 G2 T3
-    const __m512i p2 = _mm512_maddubs_epi16(c, _mm512_set1_epi16(0x0104));      // bytes (b0, b1) -> b0 * 4 + b1
-    const __m512i p4 = _mm512_madd_epi16(p2, _mm512_set1_epi32(0x00010010));     // (q0, q1) -> q0 * 16 + q1: 4 bases per 32-bit lane, first on top
-    // per 128-bit lane: the low bytes of its four 32-bit lanes, the FIRST most significant, into its first dword; then the four dwords together
-    const __m512i sh = _mm512_broadcast_i32x4(_mm_setr_epi8(12, 8, 4, 0, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1));
-    const __m512i g = _mm512_shuffle_epi8(p4, sh);
-    const __m512i idx = _mm512_setr_epi32(0, 4, 8, 12, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0);
-    _mm_storeu_si128((__m128i *)w4, _mm512_castsi512_si128(_mm512_permutexvar_epi32(idx, g)));
-    return true;
-}
-
-// memchr(p, '\n', n) for the one-pass reader's long sequence lines, with a software prefetch ahead of the scan: the hardware
-// prefetchers stop at every 4 KB page, so a thread streaming a mapping of the page cache takes one full memory latency per page
-// (IDELUCS_DEV=prefetch = bytes ahead, default 2048; 0 = plain memchr).  The scan is the first touch of the line; the packer behind
-// it reads the cache.
-__attribute__((target("avx512f,avx512bw"))) inline const uint8_t *find_nl_avx512(const uint8_t *p, size_t n, size_t ahead)
-{
-    const __m512i nl = _mm512_set1_epi8('\n');
-    size_t i = 0;
-    for (; i + 64 <= n; i += 64) {
-        _mm_prefetch((const char *)(p + i + ahead), _MM_HINT_T0);
-        const __mmask64 m = _mm512_cmpeq_epi8_mask(_mm512_loadu_si512((const void *)(p + i)), nl);
-        if (m) return p + i + __builtin_ctzll(m);
-    }
-    return i < n ? (const uint8_t *)memchr(p + i, '\n', n - i) : nullptr;
-}
-inline const uint8_t *find_nl(const uint8_t *p, size_t n)
-{
-    static const size_t ahead = [] { const char *e = idl::dev_env("prefetch"); const long v = e ? atol(e) : 2048; return (size_t)(v < 0 ? 0 : (v > 65536 ? 65536 : v)); }();
-    if (ahead != 0 && n >= 256 && host_has_avx512()) return find_nl_avx512(p, n, ahead);
-    return (const uint8_t *)memchr(p, '\n', n);
-}
-#else
-#define IDL_HAVE_AVX2_PATH 0
-inline const uint8_t *find_nl(const uint8_t *p, size_t n) { return (const uint8_t *)memchr(p, '\n', n); }
-#endif
-
-// walk_record specialised for counting the cleaned length (check mode)
-inline int walk_record_count(const uint8_t *buf, const Rec &r, int64_t *count, uint8_t *bad)
-{
-    const uint8_t *p = buf + r.data_b, *end = buf + r.data_e;
-    int64_t cnt = 0;
-    while (p < end) {
-        const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
-        const uint8_t *le = nl ? nl + 1 : end;
-        if (*p != '#' && *p != '>') {
-            const uint8_t *a = p, *b = le;
-            while (a < b && py_bytes_space(*a)) ++a;
-            while (b > a && py_bytes_space(b[-1])) --b;
-            while (a < b) {
-#if IDL_HAVE_AVX2_PATH
-                if (b - a >= 32 && host_has_avx2()) { const int64_t k = acgt_run32_avx2(a, b); cnt += 32 * k; a += 32 * k; if (a >= b) break; }
-#endif
-                if (b - a >= 8 && all_acgt8(load8(a))) { cnt += 8; a += 8; continue; }
-                const uint8_t *stop = (b - a >= 8) ? a + 8 : b;
-                for (; a < stop; ++a) {
-                    const uint8_t t = T.translate[*a];
-                    if (t == 0) continue;
-                    if (t == 1) { *bad = *a; return REC_BAD_BASE; }
-                    ++cnt;
-                }
-            }
-        }
-        p = le;
-    }
-    *count = cnt;
-    return REC_OK;
-}
-
-// walk_record specialised for packing (check mode; bdst may be NULL): whole 16-base words straight from two 8-byte loads
-inline void walk_record_pack(const uint8_t *buf, const Rec &r, Packer &pk, uint8_t *&bdst)
-{
-    const uint8_t *p = buf + r.data_b, *end = buf + r.data_e;
-    while (p < end) {
-        const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
-        const uint8_t *le = nl ? nl + 1 : end;
-        if (*p != '#' && *p != '>') {
-            const uint8_t *a = p, *b = le;
-            while (a < b && py_bytes_space(*a)) ++a;
-            while (b > a && py_bytes_space(b[-1])) --b;
-            while (a < b) {
-#if IDL_HAVE_AVX2_PATH
-                if (pk.j == 0 && (pk.w & 3) == 0 && b - a >= 64 && host_has_avx512()) {       // at a slot boundary: whole slots
-                    while (b - a >= 64 && pack64_avx512(a, pk.cw + pk.w)) {
-                        pk.mw[pk.w >> 1] = 0u; pk.mw[(pk.w >> 1) + 1] = 0u;
-                        pk.w += 4;
-                        if (bdst) { memcpy(bdst, a, 64); bdst += 64; }
-                        a += 64;
-                    }
-                    if (a >= b) break;
-                }
-                if (pk.j == 0 && b - a >= 32 && host_has_avx2()) {
-                    while (b - a >= 32 && all_acgt32_avx2(a)) {
-                        uint32_t w2[2];
-                        pack32_avx2(a, w2);
-                        pk.c = w2[0]; pk.m = 0; pk.j = 16; pk.flush_word();
-                        pk.c = w2[1]; pk.m = 0; pk.j = 16; pk.flush_word();
-                        if (bdst) { memcpy(bdst, a, 32); bdst += 32; }
-                        a += 32;
-                    }
-                    if (a >= b) break;
-                }
-#endif
-                if (pk.j == 0 && b - a >= 16) {
-                    const uint64_t x0 = load8(a), x1 = load8(a + 8);
-                    if (all_acgt8(x0) && all_acgt8(x1)) {
-                        pk.c = (pack8(x0) << 16) | pack8(x1); pk.m = 0; pk.j = 16; pk.flush_word();
-                        if (bdst) { memcpy(bdst, a, 16); bdst += 16; }
-                        a += 16;
-                        continue;
-                    }
-                }
-                const uint8_t *stop = (pk.j == 0 && b - a >= 16) ? a + 16 : ((b - a) > (16 - pk.j) ? a + (16 - pk.j) : b);
-                for (; a < stop; ++a) {
-                    const uint8_t t = T.translate[*a];
-                    if (t == 0 || t == 1) continue;          // (bad bytes were rejected when the file was opened)
-                    if (bdst) *bdst++ = t;
-                    pk.push(T.code[t]);
-                }
-            }
-        }
-        p = le;
-    }
-}
 
 }  // namespace
 
@@ -750,6 +136,29 @@ bool acquire_map(int fd, const struct stat &st, MapRef *out)
     return true;
 }
 
+// opens a regular file and sizes it: the descriptor, or -1 (cannot open) / -2 (cannot size, not a regular file)
+static int open_regular(const char *path, struct stat *st)
+{
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return -1;
+    if (fstat(fd, st) != 0 || !S_ISREG(st->st_mode)) { close(fd); return -2; }
+    return fd;
+}
+
+// the mapping of the file at `path` for a reader; an empty file maps to nothing (*empty says so: the general reader reads it as
+// one empty record, the one-pass reader declines it).  IDL_ERR_IO with the message set when it cannot be opened, sized or mapped.
+static int map_file(const char *path, MapRef *out, bool *empty)
+{
+    struct stat st;
+    const int fd = open_regular(path, &st);
+    if (fd < 0) { idl::set_error(fd == -1 ? "cannot open %s" : "cannot size %s", path); return IDL_ERR_IO; }
+    *empty = st.st_size == 0;
+    const bool mapped = *empty || acquire_map(fd, st, out);
+    close(fd);
+    if (!mapped) { idl::set_error("cannot map %s", path); return IDL_ERR_IO; }
+    return IDL_OK;
+}
+
 struct idl_fasta {
     MapRef buf;
     std::vector<Rec> recs;
@@ -762,6 +171,56 @@ struct idl_fasta {
     int64_t n_mask_unsent = 0;
     int64_t min_len = 0, max_len = 0;
 };
+
+namespace {
+
+// One record of an opened handle: its cleaned bytes to bdst and / or its packed slots to cdst / mdst (either may be NULL).
+void pack_record(const uint8_t *buf, const Rec &r, int check, uint8_t *bdst, uint8_t *cdst, uint8_t *mdst)
+{
+    const uint8_t *p = buf + r.data_b, *e = buf + r.data_e;
+    uint8_t bb = 0;
+    if (!cdst) {
+        if (check) { CopySink s{{}, bdst}; (void)clean_range(p, e, s, &bb); }
+        else raw_range(p, e, [&](uint8_t c) { *bdst++ = c; });
+        return;
+    }
+    const Packer at{(uint32_t *)cdst, (uint32_t *)mdst};
+    const int64_t slots = (r.len + 63) / 64;
+    // INVALID BYTES: the non-CHECKED sinks skip them.  The file was validated when it was opened, but the mapping is MAP_PRIVATE
+    // of a file that somebody may rewrite underneath it: packing an opened handle never fails, and with r.len fixed at the open
+    // it stays inside the record's (len + 63) / 64 slots as long as the bytes are what they were.  (The one-pass reader, which
+    // sees the bytes for the first time, reports them: one_pass_slice.)
+    if (check && bdst) { PackCopySink s{at, bdst}; (void)clean_range(p, e, s, &bb); s.pk.finish(slots); }
+    else if (check) { PackOnlySink s{at}; (void)clean_range(p, e, s, &bb); s.pk.finish(slots); }
+    else {
+        Packer pk = at;
+        if (bdst) raw_range(p, e, [&](uint8_t c) { *bdst++ = c; pk.push(T.code[c]); });
+        else raw_range(p, e, [&](uint8_t c) { pk.push(T.code[c]); });
+        pk.finish(slots);
+    }
+}
+
+// Records [lo, lo + m) of a handle on nt threads, each a run of records of about equal cleaned bases: record lo + i goes to
+// bytes + boff[i] (cleaned bytes; bytes may be NULL) and to codes + soff[i] * 16 / mask + soff[i] * 8 (codes may be NULL).
+// boff is the prefix sum of the m cleaned lengths (m + 1 entries, from 0).
+void pack_records(const idl_fasta *f, int64_t lo, int64_t m, const int64_t *boff, const int64_t *soff, int nt, uint8_t *bytes,
+                  uint8_t *codes, uint8_t *mask)
+{
+    const uint8_t *buf = f->buf.data();
+    const int64_t total = boff[m];
+    parallel_for(nt, [&](int t) {
+        // balance by cleaned bases
+        const int64_t b_lo = total * t / nt, b_hi = total * (t + 1) / nt;
+        int64_t i0 = std::lower_bound(boff, boff + m, b_lo) - boff;
+        const int64_t i1 = (t == nt - 1) ? m : std::lower_bound(boff, boff + m, b_hi) - boff;
+        if (t == 0) i0 = 0;
+        for (int64_t i = i0; i < i1; ++i)
+            pack_record(buf, f->recs[(size_t)(lo + i)], f->check, bytes ? bytes + boff[i] : nullptr, codes ? codes + soff[i] * 16 : nullptr,
+                        codes ? mask + soff[i] * 8 : nullptr);
+    });
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -800,7 +259,10 @@ int idl_pack(const uint8_t *bytes, const int64_t *byte_off, int64_t n, uint8_t *
     parallel_for(nt, [&](int t) {
         for (int64_t s = n * t / nt; s < n * (t + 1) / nt; ++s) {
             const int64_t len = byte_off[s + 1] - byte_off[s];
-            if (len > 0) pack_one(bytes + byte_off[s], len, codes + slot_off[s] * 16, mask + slot_off[s] * 8);
+            if (len <= 0) continue;
+            Packer pk{(uint32_t *)(codes + slot_off[s] * 16), (uint32_t *)(mask + slot_off[s] * 8)};
+            for (const uint8_t *b = bytes + byte_off[s], *e = b + len; b < e; ++b) pk.push(T.code[*b]);
+            pk.finish((len + 63) / 64);
         }
     });
     return IDL_OK;
@@ -810,22 +272,15 @@ int idl_fasta_open(const char *path, int check, idl_fasta **out)
 {
     IDL_REQUIRE(path && out, "NULL argument");
     *out = nullptr;
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) { idl::set_error("cannot open %s", path); return IDL_ERR_IO; }
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); idl::set_error("cannot size %s", path); return IDL_ERR_IO; }
-    idl_fasta *f = new idl_fasta();
+    std::unique_ptr<idl_fasta> f(new idl_fasta());
     f->check = check;
-    if (st.st_size > 0) {
-        if (!acquire_map(fd, st, &f->buf)) { close(fd); delete f; idl::set_error("cannot map %s", path); return IDL_ERR_IO; }
-    }
-    close(fd);
+    bool empty = false;
+    if (const int rc = map_file(path, &f->buf, &empty)) return rc;
     const uint8_t *buf = f->buf.data();
     const size_t size = f->buf.size();
     const int nt = (size > par_min_bytes() && size >= 64) ? n_threads() : 1;
     const bool timing = getenv("IDELUCS_INGEST_TIMING") != nullptr;
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_0 = now();
+    const double t_0 = now_ms();
 
     // 1. header lines ('>' at a line start), found by a parallel newline scan.  (This first touch of the mapping also takes its page
     // faults -- about 4 of the 10 ms at 1 GB; madvise(MADV_POPULATE_READ) per slice was 3 x slower, measured.)
@@ -842,9 +297,8 @@ int idl_fasta_open(const char *path, int check, idl_fasta **out)
         }
     });
 
-    const double t_1 = now();
+    const double t_1 = now_ms();
     // 2. the reference's state machine over the header lines
-    std::string dummy;
     size_t cur_b = 0;
     bool have_id = false;
     size_t id_b = 0, id_e = 0;
@@ -868,7 +322,7 @@ int idl_fasta_open(const char *path, int check, idl_fasta **out)
     }
     f->recs.push_back(Rec{have_id ? id_b : 0, have_id ? id_e : 0, cur_b, size, 0});   // unconditional flush at EOF
 
-    const double t_2 = now();
+    const double t_2 = now_ms();
     // 3. validate + count, in parallel; the first failing record in file order decides the error
     const int64_t n = (int64_t)f->recs.size();
     const int nt2 = (size > par_min_bytes() && n >= 2) ? n_threads() : 1;
@@ -886,45 +340,30 @@ int idl_fasta_open(const char *path, int check, idl_fasta **out)
     parallel_for(nt2, [&](int t) {
         for (int64_t i = cut[(size_t)t]; i < cut[(size_t)t + 1]; ++i) {
             Rec &r = f->recs[(size_t)i];
-            int kind = REC_OK;
             uint8_t bb = 0;
-            if (check) {                             // utils.py:37-40 header checks
-                if (r.id_e > r.id_b) {
-                    const uint8_t h0 = buf[r.id_b];
-                    if (h0 == '>' || h0 == '#' || py_bytes_space(h0) || (h0 >= 0x1c && h0 <= 0x1f)) kind = REC_BAD_HEADER;
-                }
-                if (kind == REC_OK && r.id_e > r.id_b && memchr(buf + r.id_b, '\t', r.id_e - r.id_b)) kind = REC_TAB;   // (empty file: buf is NULL)
-            }
+            int kind = check ? header_kind(buf, r) : REC_OK;
             if (kind == REC_OK) {
-                int64_t cnt = 0;
-                if (check) kind = walk_record_count(buf, r, &cnt, &bb);
-                else kind = walk_record(buf, r, check, [&](uint8_t) { ++cnt; }, &bb);
-                r.len = cnt;
+                CountSink s{};
+                if (check) kind = clean_range(buf + r.data_b, buf + r.data_e, s, &bb);
+                else raw_range(buf + r.data_b, buf + r.data_e, [&](uint8_t) { ++s.cnt; });
+                r.len = s.cnt;
             }
             if (kind != REC_OK) { first_bad[(size_t)t] = i; bad_kind[(size_t)t] = kind; bad_byte[(size_t)t] = bb; break; }
         }
     });
-    for (int t = 0; t < nt2; ++t) {
-        if (first_bad[(size_t)t] >= 0) {
-            const Rec &r = f->recs[(size_t)first_bad[(size_t)t]];
-            const std::string id((const char *)buf + r.id_b, r.id_e - r.id_b);
-            int rc = IDL_ERR_HEADER;
-            if (bad_kind[(size_t)t] == REC_BAD_HEADER) idl::set_error("Bad character in sequence header");
-            else if (bad_kind[(size_t)t] == REC_TAB) idl::set_error("tab included in header");
-            else { idl::set_error("Invalid DNA byte in sequence %s: '%s'", id.c_str(), chr_utf8(bad_byte[(size_t)t]).c_str()); rc = IDL_ERR_BASE; }
-            delete f;
-            return rc;
-        }
-    }
-    if (timing) fprintf(stderr, "idl_fasta_open: header scan %.1f ms, record table %.1f ms, validate + count %.1f ms (%d threads)\n", t_1 - t_0, t_2 - t_1, now() - t_2, nt);
+    for (int t = 0; t < nt2; ++t)
+        if (first_bad[(size_t)t] >= 0) return report_bad_record(buf, f->recs[(size_t)first_bad[(size_t)t]], bad_kind[(size_t)t], bad_byte[(size_t)t]);
+    if (timing) fprintf(stderr, "idl_fasta_open: header scan %.1f ms, record table %.1f ms, validate + count %.1f ms (%d threads)\n", t_1 - t_0, t_2 - t_1, now_ms() - t_2, nt);
     for (const Rec &r : f->recs) {
         f->total_bases += r.len;
         f->total_slots += (r.len + 63) / 64;
         f->names_bytes += (int64_t)(r.id_e - r.id_b);
     }
-    *out = f;
+    *out = f.release();
     return IDL_OK;
 }
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
 // One pass over the file: locate, validate, count and 2-bit pack at the same time (idl_fasta_open + idl_fasta_pack_range read
@@ -976,258 +415,182 @@ struct FastOut {
     Rec bad_rec{};
 };
 
-// one stripped sequence line [a, b): translate + validate + count + pack; REC_BAD_BASE with *bad on an invalid byte
-inline int pack_line_checked(const uint8_t *a, const uint8_t *b, Packer &pk, int64_t &cnt, uint8_t *bad)
-{
-    while (a < b) {
-#if IDL_HAVE_AVX2_PATH
-        if (pk.j == 0 && (pk.w & 3) == 0 && b - a >= 64 && host_has_avx512()) {               // at a slot boundary: whole slots
-            while (b - a >= 64 && pack64_avx512(a, pk.cw + pk.w)) {
-                pk.mw[pk.w >> 1] = 0u; pk.mw[(pk.w >> 1) + 1] = 0u;
-                pk.w += 4;
-                a += 64; cnt += 64;
-            }
-            if (a >= b) break;
+// what the slices of one idl_fasta_parse_pack call share
+struct OnePass {
+    const uint8_t *buf;
+    size_t size;
+    uint8_t *codes, *mask;                  // the caller's host arenas, cap_slots slots
+    int64_t cap_slots;
+    void *dev_codes, *dev_mask;             // device arenas of the same shape, or NULL
+    std::vector<hipStream_t> streams;       // thread t copies on stream t mod count
+    CopyStreams *cs = nullptr;              // where streams[1 ..] come from
+    int per_thread, ns;                     // slices per thread, slices
+    int64_t region_slots;                   // a slice's expected slots
+    int copy_div;
+    std::vector<int> sched;                 // the piece schedule: cuts in % of region_slots
+    int64_t COPY_SLOTS, COPY_MIN;           // a piece's largest / (but for the last) smallest size
+    bool sparse_mask, timing;
+    std::vector<FastOut> outs;              // per slice
+};
+
+// the pieces of one slice's region on their way to the device
+struct PieceSender {
+    const OnePass &j;
+    FastOut &o;
+    hipStream_t stream;
+    int64_t sent;                           // slots [region_lo, sent) have been sent
+    bool piece_dirty = false;               // a record since the last copy holds an N
+    void send(int64_t upto)
+    {
+        // the invalid-mask is a third of the bytes, and on clean input it says nothing the lengths do not: a piece without an N
+        // sends its packed bases only, and its records are flagged for the caller to rebuild their masks on the device
+        const bool with_mask = piece_dirty || !j.sparse_mask;
+        if (j.dev_codes != nullptr && upto > sent) {
+            const double ts = j.timing ? now_ms() : 0.0;
+            if (hipMemcpyAsync((uint8_t *)j.dev_codes + sent * 16, j.codes + sent * 16, (size_t)(upto - sent) * 16, hipMemcpyHostToDevice, stream) != hipSuccess ||
+                (with_mask && hipMemcpyAsync((uint8_t *)j.dev_mask + sent * 8, j.mask + sent * 8, (size_t)(upto - sent) * 8, hipMemcpyHostToDevice, stream) != hipSuccess))
+                o.copy_failed = 1;
+            if (j.timing) { o.t_send += now_ms() - ts; o.n_send += with_mask ? 2 : 1; }
         }
-        if (pk.j == 0 && b - a >= 32 && host_has_avx2()) {
-            while (b - a >= 32 && all_acgt32_avx2(a)) {
-                uint32_t w2[2];
-                pack32_avx2(a, w2);
-                pk.c = w2[0]; pk.m = 0; pk.j = 16; pk.flush_word();
-                pk.c = w2[1]; pk.m = 0; pk.j = 16; pk.flush_word();
-                a += 32; cnt += 32;
-            }
-            if (a >= b) break;
-        }
-#endif
-        if (pk.j == 0 && b - a >= 16) {
-            const uint64_t x0 = load8(a), x1 = load8(a + 8);
-            if (all_acgt8(x0) && all_acgt8(x1)) {
-                pk.c = (pack8(x0) << 16) | pack8(x1); pk.m = 0; pk.j = 16; pk.flush_word();
-                a += 16; cnt += 16;
-                continue;
-            }
-        }
-        const uint8_t *stop = (pk.j == 0 && b - a >= 16) ? a + 16 : ((b - a) > (16 - pk.j) ? a + (16 - pk.j) : b);
-        for (; a < stop; ++a) {
-            const uint8_t t = T.translate[*a];
-            if (t == 0) continue;
-            if (t == 1) { *bad = *a; return REC_BAD_BASE; }
-            pk.push(T.code[t]);
-            ++cnt;
-        }
+        o.mask_sent.resize(o.recs.size(), (j.dev_codes != nullptr && with_mask) ? 1 : 0);
+        piece_dirty = false;
+        sent = upto;
     }
-    return REC_OK;
+};
+
+enum { REC_REGION_FULL = -1 };              // (beside REC_*: the slice's region of the arenas has no room for the line)
+
+// slice sl of the file, on thread t: the records whose header line starts in it, into its region of the arenas
+void one_pass_slice(OnePass &j, const int t, const int sl)
+{
+    const uint8_t *buf = j.buf;
+    const size_t size = j.size;
+    const int ns = j.ns;
+    FastOut &o = j.outs[(size_t)sl];
+    if (j.timing) o.t_begin = now_ms();
+    const size_t b = size * (size_t)sl / (size_t)ns, e = size * (size_t)(sl + 1) / (size_t)ns;
+    const int64_t region_lo = j.cap_slots * sl / ns, region_hi = j.cap_slots * (sl + 1) / ns;
+    auto line_end = [&](size_t p) -> size_t {
+        const uint8_t *nl = find_nl(buf + p, size - p);
+        return nl ? (size_t)(nl - buf) + 1 : size;
+    };
+    size_t q = b;
+    if (b > 0) q = line_end(b - 1);                               // the first line that STARTS in this slice
+    // the first header line at or after q (thread 0 also vouches for everything before the file's first header: '#' lines only)
+    while (q < size && buf[q] != '>') {
+        if (sl == 0) { if (buf[q] != '#') { o.fallback = 1; return; } }
+        else if (q >= e) return;                                  // no record starts in this slice
+        q = line_end(q);
+    }
+    if (q >= size) { if (sl == 0) o.fallback = 1; return; }       // (slice 0: a file without any header line)
+    if (q >= e) return;
+    int64_t slot = region_lo;
+    size_t cut = 0;                                               // next entry of the piece schedule
+    const bool one_cut = j.per_thread > 1 && ns > 1;              // several slices per thread: one cut per slice, at 70 %
+    PieceSender snd{j, o, j.streams[(size_t)t % j.streams.size()], region_lo};
+    size_t hs = q;
+    while (hs < size && hs < e) {                                 // one record per turn; it may run past e
+        const size_t he = line_end(hs);
+        Rec r{hs + 1, (he - hs >= 2) ? he - 1 : hs + 1, he, he, 0};   // id = line[1:-1]: drops exactly one trailing byte whatever it is
+        if (r.id_e <= r.id_b) { o.fallback = 1; return; }         // empty id: the general reader's rolling semantics
+        uint8_t bb = 0;
+        int kind = header_kind(buf, r);
+        // INVALID BYTES: this reader sees the bytes for the first time, so its sink is the CHECKED one: it reports them
+        PackCheckedSink sink{Packer{(uint32_t *)(j.codes + slot * 16), (uint32_t *)(j.mask + slot * 8)}};
+        const uint8_t *lp = buf + he;
+        if (kind == REC_OK)                                       // the record's lines: up to the next '>' line
+            kind = visit_seq_lines(lp, buf + size, PrefetchNl(), [](uint8_t c) { return c == '>'; }, [&](const uint8_t *a, const uint8_t *bnd) {
+                if (slot + (sink.cnt + (int64_t)(bnd - a)) / 64 + 2 > region_hi) return (int)REC_REGION_FULL;
+                return clean_line(a, bnd, sink, &bb);
+            });
+        if (kind == REC_REGION_FULL) { o.fallback = 1; return; }
+        if (kind != REC_OK) { o.bad_kind = kind; o.bad_byte = bb; o.bad_rec = r; return; }
+        r.data_e = (size_t)(lp - buf);
+        r.len = sink.cnt;
+        const int64_t slots = (r.len + 63) / 64;
+        sink.pk.finish(slots);
+        snd.piece_dirty |= sink.pk.dirty;
+        o.recs.push_back(r);
+        o.slot.push_back(slot);
+        slot += slots;
+        if (slot - snd.sent >= j.COPY_SLOTS) snd.send(slot);
+        else if (!j.copy_div && cut < (one_cut ? std::min<size_t>(j.sched.size(), 1) : j.sched.size()) &&
+                 (slot - region_lo) * 100 >= j.region_slots * (one_cut ? 70 : j.sched[cut]) && slot - snd.sent >= j.COPY_MIN) {
+            snd.send(slot);
+            if (one_cut) cut = j.sched.size();
+            while (cut < j.sched.size() && (slot - region_lo) * 100 >= j.region_slots * j.sched[cut]) ++cut;
+        }
+        hs = r.data_e;
+    }
+    snd.send(slot);
+    o.slot.push_back(slot);                                       // end of this slice's records
+    if (j.timing) o.t_end = now_ms();
 }
 
-}  // namespace
-
-int idl_fasta_parse_pack(const char *path, uint8_t *codes, uint8_t *mask, int64_t cap_slots, void *dev_codes, void *dev_mask,
-                         void *stream, idl_fasta **out)
+// A thread sends what it has packed while it goes on parsing; what is still unsent when it finishes is the copy TAIL every
+// later stage waits for.  Round 4 cut a region into 3 equal pieces: the last third of everything (125 MB at cfg2) left when the
+// parsing was over, 2.6 ms at the link's 48 GB/s (IDELUCS_INGEST_TIMING=2: threads joined 8.0 ms, copies drained 10.6).  The
+// pieces now shrink -- cuts at 45 / 75 / 92 % of the region's expected slots, the rest at the end (IDELUCS_DEV=copy_sched="45,75,92")
+// -- for the same number of calls as four equal pieces: every hipMemcpyAsync takes the stream's lock and ~15 us of host time
+// (8 equal pieces 14.6 ms against 12.3-12.8 for 2-4, 16 pieces 18.9: round 4).  A piece is at most 6 MB (big files: more
+// pieces) and, but for the last, at least 384 KB.  IDELUCS_DEV=copy_div=<d> keeps round 4's d equal pieces for A/B runs.
+void set_copy_schedule(OnePass &j)
 {
-    IDL_REQUIRE(path && codes && mask && out && cap_slots >= 1, "fasta_parse_pack: NULL argument");
-    IDL_REQUIRE((dev_codes == nullptr) == (dev_mask == nullptr), "fasta_parse_pack: dev_codes and dev_mask go together");
-    *out = nullptr;
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) { idl::set_error("cannot open %s", path); return IDL_ERR_IO; }
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { close(fd); idl::set_error("cannot size %s", path); return IDL_ERR_IO; }
-    if (st.st_size == 0) { close(fd); return IDL_FALLBACK; }          // (the general reader's one empty record)
-    idl_fasta *f = new idl_fasta();
-    f->check = 1;
-    const bool mapped = acquire_map(fd, st, &f->buf);
-    close(fd);
-    if (!mapped) { delete f; idl::set_error("cannot map %s", path); return IDL_ERR_IO; }
+    j.region_slots = (int64_t)(j.size / 64) / j.ns + 1;
+    j.copy_div = idl::dev_env_int("copy_div", 0, 1, 64);
+    const char *e = idl::dev_env("copy_sched");
+    for (const char *p = e ? e : "45,75,92"; *p;) {       // (of a thread's share; with several slices per thread: of each slice, first cut only)
+        char *q = nullptr;
+        const long x = strtol(p, &q, 10);
+        if (q == p) break;
+        if (x > 0 && x < 100 && (j.sched.empty() || x > j.sched.back())) j.sched.push_back((int)x);
+        p = (*q == ',') ? q + 1 : q;
+    }
+    const int64_t COPY_MAX = (int64_t)1 << 18;
+    j.COPY_MIN = (int64_t)1 << 14;
+    j.COPY_SLOTS = j.copy_div ? std::min<int64_t>(COPY_MAX, std::max<int64_t>(j.COPY_MIN, j.region_slots / j.copy_div)) : COPY_MAX;
+}
+
+// copy streams: the caller's, and IDELUCS_DEV=copy_streams - 1 more of this library's own (thread t copies on stream t mod count;
+// they start behind whatever the caller's stream holds and the caller's stream waits for them at the end).  false: a HIP call failed.
+bool open_copy_streams(OnePass &j, hipStream_t stream, int dev)
+{
+    j.streams.assign(1, stream);
+    const int want = idl::dev_env_int("copy_streams", 1, 1, 8);
+    j.cs = want > 1 ? copy_streams(dev, want - 1) : nullptr;
+    if (j.cs == nullptr) return true;
+    if (hipEventRecord(j.cs->start, stream) != hipSuccess) j.cs = nullptr;
+    for (size_t i = 0; j.cs != nullptr && i < j.cs->extra.size(); ++i) {
+        if (hipStreamWaitEvent(j.cs->extra[i], j.cs->start, 0) != hipSuccess) return false;
+        j.streams.push_back(j.cs->extra[i]);
+    }
+    return true;
+}
+
+// the IDELUCS_INGEST_TIMING line of idl_fasta_parse_pack
+void report_timeline(const OnePass &j, double t_0, const std::vector<double> &th_begin, const std::vector<double> &th_end, hipStream_t stream, int bind_node)
+{
+    double b_max = 0, e_min = 1e300, e_max = 0, snd = 0;
+    int n_calls = 0;
+    for (size_t t = 0; t < th_end.size(); ++t) {
+        if (th_end[t] == 0) continue;
+        b_max = std::max(b_max, th_begin[t] - t_0); e_min = std::min(e_min, th_end[t] - t_0); e_max = std::max(e_max, th_end[t] - t_0);
+    }
+    for (const FastOut &o : j.outs) { snd += o.t_send; n_calls += o.n_send; }
+    const double t_join = now_ms() - t_0;
+    double t_drain = -1;
+    // IDELUCS_INGEST_TIMING=2 also waits for the copies here (diagnostic only: the caller overlaps this wait with its own work)
+    if (j.dev_codes != nullptr && atoi(getenv("IDELUCS_INGEST_TIMING")) >= 2 && hipStreamSynchronize(stream) == hipSuccess) t_drain = now_ms() - t_0;
+    fprintf(stderr, "idl_fasta_parse_pack timeline: last thread started %.2f ms, threads finished %.2f .. %.2f, joined %.2f, copies drained %.2f; "
+                    "%d slices, %d copy calls on %zu stream(s), %.2f ms of host time in them (sum over threads); bound to node %d (the file's pages: node %d)\n",
+            b_max, e_min, e_max, t_join, t_drain, j.ns, n_calls, j.streams.size(), snd, bind_node, g_last_file_node);
+}
+
+// merge: every thread copies its records to their place in the file's order (prefix of the per-thread counts) and sums its own
+size_t merge_slices(idl_fasta *f, const std::vector<FastOut> &outs, int nt)
+{
     const uint8_t *buf = f->buf.data();
-    const size_t size = f->buf.size();
-    const int nt = (size > par_min_bytes() && size >= 64) ? n_threads() : 1;
-    const bool timing = getenv("IDELUCS_INGEST_TIMING") != nullptr;
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_0 = now();
-    // The file is cut into SLICES (IDELUCS_DEV=slices per thread, default 4) that the threads take from a counter: the threads of a
-    // shared host do not run at one speed (a core's other hardware thread busy, a time slice lost: with one slice per thread they
-    // finished between 5.4 and 7.6 ms), and the call ends with its slowest.  A slice owns the records whose header line starts in
-    // it and its own region of the arenas, as a thread did.
-    const int per_thread = [] { const char *e = idl::dev_env("slices"); const int v = e ? atoi(e) : 4; return v >= 1 && v <= 64 ? v : 4; }();
-    const int ns = nt > 1 ? nt * per_thread : 1;
-    std::vector<FastOut> outs((size_t)ns);
-    std::vector<double> th_begin((size_t)nt, 0.0), th_end((size_t)nt, 0.0);
-    std::atomic<int> next_slice{0};
-    // A thread sends what it has packed while it goes on parsing; what is still unsent when it finishes is the copy TAIL every
-    // later stage waits for.  Round 4 cut a region into 3 equal pieces: the last third of everything (125 MB at cfg2) left when the
-    // parsing was over, 2.6 ms at the link's 48 GB/s (IDELUCS_INGEST_TIMING=2: threads joined 8.0 ms, copies drained 10.6).  The
-    // pieces now shrink -- cuts at 45 / 75 / 92 % of the region's expected slots, the rest at the end (IDELUCS_DEV=copy_sched="45,75,92")
-    // -- for the same number of calls as four equal pieces: every hipMemcpyAsync takes the stream's lock and ~15 us of host time
-    // (8 equal pieces 14.6 ms against 12.3-12.8 for 2-4, 16 pieces 18.9: round 4).  A piece is at most 6 MB (big files: more
-    // pieces) and, but for the last, at least 384 KB.  IDELUCS_DEV=copy_div=<d> keeps round 4's d equal pieces for A/B runs.
-    const int64_t region_slots = (int64_t)(size / 64) / ns + 1;
-    const int copy_div = [] { const char *e = idl::dev_env("copy_div"); const int d = e ? atoi(e) : 0; return d >= 1 && d <= 64 ? d : 0; }();
-    const std::vector<int> sched = [] {
-        std::vector<int> v;
-        const char *e = idl::dev_env("copy_sched");
-        for (const char *p = e ? e : "45,75,92"; *p;) {       // (of a thread's share; with several slices per thread: of each slice, first cut only)
-            char *q = nullptr;
-            const long x = strtol(p, &q, 10);
-            if (q == p) break;
-            if (x > 0 && x < 100 && (v.empty() || x > v.back())) v.push_back((int)x);
-            p = (*q == ',') ? q + 1 : q;
-        }
-        return v;
-    }();
-    const int64_t COPY_MAX = (int64_t)1 << 18, COPY_MIN = (int64_t)1 << 14;
-    const int64_t COPY_SLOTS = copy_div ? std::min<int64_t>(COPY_MAX, std::max<int64_t>(COPY_MIN, region_slots / copy_div)) : COPY_MAX;
-    // the copies below are issued from worker threads: a new thread's current device is 0, so each worker adopts the CALLER's device
-    // first (a rank of a multi-GPU job is bound to another one, and dev_codes / stream belong to it)
-    int caller_dev = -1;
-    if (dev_codes != nullptr && hipGetDevice(&caller_dev) != hipSuccess) caller_dev = -1;
-    g_last_file_node = (nt > 1 && caller_dev >= 0 && !idl::dev_env("numa")) ? file_numa_node(buf, size) : -1;
-    CpuBind bind = (nt > 1 && caller_dev >= 0) ? bind_for_device(caller_dev, nt, g_last_file_node) : CpuBind();
-    if (g_last_file_node >= 0 && bind.node != g_last_file_node) bind = bind_for_device(caller_dev, nt);       // (too few CPUs open there: the device's node)
-    g_last_bind_node = bind.node;
-    const bool sparse_mask = [] { const char *e = idl::dev_env("sparse_mask"); return !(e && atoi(e) == 0); }();
-    // copy streams: the caller's, and IDELUCS_DEV=copy_streams - 1 more of this library's own (thread t copies on stream t mod count;
-    // they start behind whatever the caller's stream holds and the caller's stream waits for them at the end)
-    std::vector<hipStream_t> streams(1, (hipStream_t)stream);
-    CopyStreams *cs = nullptr;
-    if (dev_codes != nullptr && nt > 1 && caller_dev >= 0) {
-        const int want = [] { const char *e = idl::dev_env("copy_streams"); const int v = e ? atoi(e) : 1; return v >= 1 && v <= 8 ? v : 1; }();
-        cs = want > 1 ? copy_streams(caller_dev, want - 1) : nullptr;
-        if (cs != nullptr) {
-            if (hipEventRecord(cs->start, (hipStream_t)stream) != hipSuccess) cs = nullptr;
-            for (size_t i = 0; cs != nullptr && i < cs->extra.size(); ++i) {
-                if (hipStreamWaitEvent(cs->extra[i], cs->start, 0) != hipSuccess) { idl::set_error("fasta_parse_pack: hipStreamWaitEvent failed"); delete f; return IDL_ERR_HIP; }
-                streams.push_back(cs->extra[i]);
-            }
-        }
-    }
-
-    auto do_slice = [&](const int t, const int sl) {
-        FastOut &o = outs[(size_t)sl];
-        if (timing) o.t_begin = now();
-        const size_t b = size * (size_t)sl / (size_t)ns, e = size * (size_t)(sl + 1) / (size_t)ns;
-        const int64_t region_lo = cap_slots * sl / ns, region_hi = cap_slots * (sl + 1) / ns;
-        auto line_end = [&](size_t p) -> size_t {
-            const uint8_t *nl = find_nl(buf + p, size - p);
-            return nl ? (size_t)(nl - buf) + 1 : size;
-        };
-        size_t q = b;
-        if (b > 0) q = line_end(b - 1);                               // the first line that STARTS in this slice
-        // the first header line at or after q (thread 0 also vouches for everything before the file's first header: '#' lines only)
-        while (q < size && buf[q] != '>') {
-            if (sl == 0) { if (buf[q] != '#') { o.fallback = 1; return; } }
-            else if (q >= e) return;                                  // no record starts in this slice
-            q = line_end(q);
-        }
-        if (q >= size) { if (sl == 0) o.fallback = 1; return; }       // (slice 0: a file without any header line)
-        if (q >= e) return;
-        int64_t slot = region_lo, sent = region_lo;
-        size_t cut = 0;                                               // next entry of the piece schedule
-        bool piece_dirty = false;                                     // a record since the last copy holds an N
-        const hipStream_t my_stream = streams[(size_t)t % streams.size()];
-        auto send = [&](int64_t upto) {
-            // the invalid-mask is a third of the bytes, and on clean input it says nothing the lengths do not: a piece without an N
-            // sends its packed bases only, and its records are flagged for the caller to rebuild their masks on the device
-            const bool with_mask = piece_dirty || !sparse_mask;
-            if (dev_codes != nullptr && upto > sent) {
-                const double ts = timing ? now() : 0.0;
-                if (hipMemcpyAsync((uint8_t *)dev_codes + sent * 16, codes + sent * 16, (size_t)(upto - sent) * 16, hipMemcpyHostToDevice, my_stream) != hipSuccess ||
-                    (with_mask && hipMemcpyAsync((uint8_t *)dev_mask + sent * 8, mask + sent * 8, (size_t)(upto - sent) * 8, hipMemcpyHostToDevice, my_stream) != hipSuccess))
-                    o.copy_failed = 1;
-                if (timing) { o.t_send += now() - ts; o.n_send += with_mask ? 2 : 1; }
-            }
-            o.mask_sent.resize(o.recs.size(), (dev_codes != nullptr && with_mask) ? 1 : 0);
-            piece_dirty = false;
-            sent = upto;
-        };
-        size_t hs = q;
-        while (hs < size && hs < e) {                                 // one record per turn; it may run past e
-            const size_t he = line_end(hs);
-            Rec r{hs + 1, (he - hs >= 2) ? he - 1 : hs + 1, he, he, 0};   // id = line[1:-1]: drops exactly one trailing byte whatever it is
-            if (r.id_e <= r.id_b) { o.fallback = 1; return; }         // empty id: the general reader's rolling semantics
-            int kind = REC_OK;
-            uint8_t bb = 0;
-            const uint8_t h0 = buf[r.id_b];                           // utils.py:37-40 header checks
-            if (h0 == '>' || h0 == '#' || py_bytes_space(h0) || (h0 >= 0x1c && h0 <= 0x1f)) kind = REC_BAD_HEADER;
-            if (kind == REC_OK && r.id_e > r.id_b && memchr(buf + r.id_b, '\t', r.id_e - r.id_b)) kind = REC_TAB;   // (empty file: buf is NULL)
-            Packer pk{(uint32_t *)(codes + slot * 16), (uint32_t *)(mask + slot * 8)};
-            int64_t cnt = 0;
-            size_t lp = he;
-            while (kind == REC_OK && lp < size && buf[lp] != '>') {
-                const size_t le = line_end(lp);
-                if (buf[lp] != '#') {
-                    const uint8_t *a = buf + lp, *bnd = buf + le;
-                    while (a < bnd && py_bytes_space(*a)) ++a;
-                    while (bnd > a && py_bytes_space(bnd[-1])) --bnd;
-                    if (slot + (cnt + (int64_t)(bnd - a)) / 64 + 2 > region_hi) { o.fallback = 1; return; }   // this region is full
-                    kind = pack_line_checked(a, bnd, pk, cnt, &bb);
-                }
-                lp = le;
-            }
-            if (kind != REC_OK) { o.bad_kind = kind; o.bad_byte = bb; o.bad_rec = r; return; }
-            r.data_e = lp;
-            r.len = cnt;
-            const int64_t slots = (cnt + 63) / 64;
-            pk.finish(slots);
-            piece_dirty |= pk.dirty;
-            o.recs.push_back(r);
-            o.slot.push_back(slot);
-            slot += slots;
-            if (slot - sent >= COPY_SLOTS) send(slot);
-            else if (!copy_div && cut < (per_thread > 1 && ns > 1 ? std::min<size_t>(sched.size(), 1) : sched.size()) &&
-                     (slot - region_lo) * 100 >= region_slots * (per_thread > 1 && ns > 1 ? 70 : sched[cut]) && slot - sent >= COPY_MIN) {
-                send(slot);
-                if (per_thread > 1 && ns > 1) cut = sched.size();
-                while (cut < sched.size() && (slot - region_lo) * 100 >= region_slots * sched[cut]) ++cut;
-            }
-            hs = lp;
-        }
-        send(slot);
-        o.slot.push_back(slot);                                       // end of this slice's records
-        if (timing) o.t_end = now();
-    };
-    parallel_for(nt, [&](int t) {
-        if (timing) th_begin[(size_t)t] = now();
-        if (t > 0 && caller_dev >= 0 && hipSetDevice(caller_dev) != hipSuccess) { outs[0].copy_failed = 1; return; }
-        for (int sl = next_slice.fetch_add(1); sl < ns; sl = next_slice.fetch_add(1)) do_slice(t, sl);
-        if (timing) th_end[(size_t)t] = now();
-    }, &bind);
-    // the caller's stream continues when the other copy streams have drained
-    for (size_t i = 1; i < streams.size(); ++i) {
-        if (hipEventRecord(cs->done[i - 1], streams[i]) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, cs->done[i - 1], 0) != hipSuccess)
-            outs[0].copy_failed = 1;
-    }
-    if (timing) {
-        double b_max = 0, e_min = 1e300, e_max = 0, snd = 0;
-        int n_calls = 0;
-        for (int t = 0; t < nt; ++t) {
-            if (th_end[(size_t)t] == 0) continue;
-            b_max = std::max(b_max, th_begin[(size_t)t] - t_0); e_min = std::min(e_min, th_end[(size_t)t] - t_0); e_max = std::max(e_max, th_end[(size_t)t] - t_0);
-        }
-        for (const FastOut &o : outs) { snd += o.t_send; n_calls += o.n_send; }
-        const double t_join = now() - t_0;
-        double t_drain = -1;
-        // IDELUCS_INGEST_TIMING=2 also waits for the copies here (diagnostic only: the caller overlaps this wait with its own work)
-        if (dev_codes != nullptr && atoi(getenv("IDELUCS_INGEST_TIMING")) >= 2 && hipStreamSynchronize((hipStream_t)stream) == hipSuccess) t_drain = now() - t_0;
-        fprintf(stderr, "idl_fasta_parse_pack timeline: last thread started %.2f ms, threads finished %.2f .. %.2f, joined %.2f, copies drained %.2f; "
-                        "%d slices, %d copy calls on %zu stream(s), %.2f ms of host time in them (sum over threads); bound to node %d (the file's pages: node %d)\n",
-                b_max, e_min, e_max, t_join, t_drain, ns, n_calls, streams.size(), snd, bind.node, g_last_file_node);
-    }
-
-    for (int t = 0; t < ns; ++t) {
-        const FastOut &o = outs[(size_t)t];
-        if (o.fallback) { delete f; return IDL_FALLBACK; }
-        if (o.copy_failed) { delete f; idl::set_error("fasta_parse_pack: hipMemcpyAsync failed: %s", hipGetErrorString(hipGetLastError())); return IDL_ERR_HIP; }
-        if (o.bad_kind != REC_OK) {                                   // the first failing record in file order decides
-            const std::string id((const char *)buf + o.bad_rec.id_b, o.bad_rec.id_e - o.bad_rec.id_b);
-            int rc = IDL_ERR_HEADER;
-            if (o.bad_kind == REC_BAD_HEADER) idl::set_error("Bad character in sequence header");
-            else if (o.bad_kind == REC_TAB) idl::set_error("tab included in header");
-            else { idl::set_error("Invalid DNA byte in sequence %s: '%s'", id.c_str(), chr_utf8(o.bad_byte).c_str()); rc = IDL_ERR_BASE; }
-            delete f;
-            return rc;
-        }
-    }
-    // merge: every thread copies its records to their place in the file's order (prefix of the per-thread counts) and sums its own
+    const int ns = (int)outs.size();
     std::vector<size_t> first((size_t)ns + 1, 0);
     for (int t = 0; t < ns; ++t) first[(size_t)t + 1] = first[(size_t)t] + outs[(size_t)t].recs.size();
     const size_t n = first[(size_t)ns];
@@ -1268,8 +631,76 @@ int idl_fasta_parse_pack(const char *path, uint8_t *codes, uint8_t *mask, int64_
     }
     f->min_len = n ? lo : 0;
     f->names_high = (high & 0x80u) ? 1 : 0;
-    if (timing) fprintf(stderr, "idl_fasta_parse_pack: one pass %.1f ms (%d threads, %zu records)\n", now() - t_0, nt, n);
-    *out = f;
+    return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+int idl_fasta_parse_pack(const char *path, uint8_t *codes, uint8_t *mask, int64_t cap_slots, void *dev_codes, void *dev_mask,
+                         void *stream, idl_fasta **out)
+{
+    IDL_REQUIRE(path && codes && mask && out && cap_slots >= 1, "fasta_parse_pack: NULL argument");
+    IDL_REQUIRE((dev_codes == nullptr) == (dev_mask == nullptr), "fasta_parse_pack: dev_codes and dev_mask go together");
+    *out = nullptr;
+    std::unique_ptr<idl_fasta> f(new idl_fasta());
+    f->check = 1;
+    bool empty = false;
+    if (const int rc = map_file(path, &f->buf, &empty)) return rc;
+    if (empty) return IDL_FALLBACK;                                   // (the general reader's one empty record)
+    const uint8_t *buf = f->buf.data();
+    const size_t size = f->buf.size();
+    const int nt = (size > par_min_bytes() && size >= 64) ? n_threads() : 1;
+    const double t_0 = now_ms();
+    OnePass j{buf, size, codes, mask, cap_slots, dev_codes, dev_mask};
+    j.timing = getenv("IDELUCS_INGEST_TIMING") != nullptr;
+    // The file is cut into SLICES (IDELUCS_DEV=slices per thread, default 4) that the threads take from a counter: the threads of a
+    // shared host do not run at one speed (a core's other hardware thread busy, a time slice lost: with one slice per thread they
+    // finished between 5.4 and 7.6 ms), and the call ends with its slowest.  A slice owns the records whose header line starts in
+    // it and its own region of the arenas, as a thread did.
+    j.per_thread = idl::dev_env_int("slices", 4, 1, 64);
+    j.ns = nt > 1 ? nt * j.per_thread : 1;
+    j.outs.resize((size_t)j.ns);
+    set_copy_schedule(j);
+    std::vector<double> th_begin((size_t)nt, 0.0), th_end((size_t)nt, 0.0);
+    std::atomic<int> next_slice{0};
+    // the copies below are issued from worker threads: a new thread's current device is 0, so each worker adopts the CALLER's device
+    // first (a rank of a multi-GPU job is bound to another one, and dev_codes / stream belong to it)
+    int caller_dev = -1;
+    if (dev_codes != nullptr && hipGetDevice(&caller_dev) != hipSuccess) caller_dev = -1;
+    g_last_file_node = (nt > 1 && caller_dev >= 0 && !idl::dev_env("numa")) ? file_numa_node(buf, size) : -1;
+    CpuBind bind = (nt > 1 && caller_dev >= 0) ? bind_for_device(caller_dev, nt, g_last_file_node) : CpuBind();
+    if (g_last_file_node >= 0 && bind.node != g_last_file_node) bind = bind_for_device(caller_dev, nt);       // (too few CPUs open there: the device's node)
+    g_last_bind_node = bind.node;
+    j.sparse_mask = idl::dev_env_int("sparse_mask", 1, INT32_MIN, INT32_MAX) != 0;
+    j.streams.assign(1, (hipStream_t)stream);
+    if (dev_codes != nullptr && nt > 1 && caller_dev >= 0 && !open_copy_streams(j, (hipStream_t)stream, caller_dev)) {
+        idl::set_error("fasta_parse_pack: hipStreamWaitEvent failed");
+        return IDL_ERR_HIP;
+    }
+
+    parallel_for(nt, [&](int t) {
+        if (j.timing) th_begin[(size_t)t] = now_ms();
+        if (t > 0 && caller_dev >= 0 && hipSetDevice(caller_dev) != hipSuccess) { j.outs[0].copy_failed = 1; return; }
+        for (int sl = next_slice.fetch_add(1); sl < j.ns; sl = next_slice.fetch_add(1)) one_pass_slice(j, t, sl);
+        if (j.timing) th_end[(size_t)t] = now_ms();
+    }, &bind);
+    // the caller's stream continues when the other copy streams have drained
+    for (size_t i = 1; i < j.streams.size(); ++i) {
+        if (hipEventRecord(j.cs->done[i - 1], j.streams[i]) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, j.cs->done[i - 1], 0) != hipSuccess)
+            j.outs[0].copy_failed = 1;
+    }
+    if (j.timing) report_timeline(j, t_0, th_begin, th_end, (hipStream_t)stream, bind.node);
+
+    for (const FastOut &o : j.outs) {
+        if (o.fallback) return IDL_FALLBACK;
+        if (o.copy_failed) { idl::set_error("fasta_parse_pack: hipMemcpyAsync failed: %s", hipGetErrorString(hipGetLastError())); return IDL_ERR_HIP; }
+        if (o.bad_kind != REC_OK) return report_bad_record(buf, o.bad_rec, o.bad_kind, o.bad_byte);      // the first failing record in file order decides
+    }
+    const size_t n = merge_slices(f.get(), j.outs, nt);
+    if (j.timing) fprintf(stderr, "idl_fasta_parse_pack: one pass %.1f ms (%d threads, %zu records)\n", now_ms() - t_0, nt, n);
+    *out = f.release();
     return IDL_OK;
 }
 
@@ -1345,28 +776,7 @@ int idl_fasta_export(const idl_fasta *f, uint8_t *names, int64_t *name_off, int6
     if (slot_off) memcpy(slot_off, soff.data(), (size_t)(n + 1) * sizeof(int64_t));
     if (!bytes && !codes) return IDL_OK;
     const int nt = (f->buf.size() > par_min_bytes() && n >= 2) ? n_threads() : 1;
-    const int64_t total = boff[(size_t)n];
-    parallel_for(nt, [&](int t) {
-        // balance by cleaned bases
-        const int64_t lo = total * t / nt, hi = total * (t + 1) / nt;
-        int64_t i0 = std::lower_bound(boff.begin(), boff.begin() + n, lo) - boff.begin();
-        int64_t i1 = (t == nt - 1) ? n : std::lower_bound(boff.begin(), boff.begin() + n, hi) - boff.begin();
-        if (t == 0) i0 = 0;
-        for (int64_t i = i0; i < i1; ++i) {
-            const Rec &r = f->recs[(size_t)i];
-            uint8_t bb = 0;
-            uint8_t *bdst = bytes ? bytes + boff[(size_t)i] : nullptr;
-            if (codes) {
-                Packer pk{(uint32_t *)(codes + soff[(size_t)i] * 16), (uint32_t *)(mask + soff[(size_t)i] * 8)};
-                if (f->check) walk_record_pack(buf, r, pk, bdst);
-                else if (bdst) (void)walk_record(buf, r, f->check, [&](uint8_t c) { *bdst++ = c; pk.push(T.code[c]); }, &bb);
-                else (void)walk_record(buf, r, f->check, [&](uint8_t c) { pk.push(T.code[c]); }, &bb);
-                pk.finish((r.len + 63) / 64);
-            } else {
-                (void)walk_record(buf, r, f->check, [&](uint8_t c) { *bdst++ = c; }, &bb);
-            }
-        }
-    });
+    pack_records(f, 0, n, boff.data(), soff.data(), nt, bytes, codes, mask);
     return IDL_OK;
 }
 
@@ -1379,11 +789,11 @@ int idl_ingest_file_node(void) { return g_last_file_node; }
 int idl_ingest_probe_file_node(const char *path)
 {
     if (path == nullptr) return -1;
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return -1;
     struct stat st;
+    const int fd = open_regular(path, &st);
+    if (fd < 0) return -1;
     int node = -1;
-    if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+    if (st.st_size > 0) {
         void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
         if (m != MAP_FAILED) { node = file_numa_node((const uint8_t *)m, (size_t)st.st_size); munmap(m, (size_t)st.st_size); }
     }
@@ -1412,7 +822,6 @@ int idl_fasta_pack_range(const idl_fasta *f, int64_t rec_lo, int64_t rec_hi, uin
     IDL_REQUIRE(rec_lo >= 0 && rec_lo <= rec_hi && rec_hi <= n, "record range outside the file");
     if (rec_lo == rec_hi) return IDL_OK;
     IDL_REQUIRE(codes && mask, "NULL buffer");
-    const uint8_t *buf = f->buf.data();
     // slot offset of rec_lo in the whole-file layout, then a local prefix over the range (balanced by cleaned bases)
     int64_t s0 = 0;
     for (int64_t i = 0; i < rec_lo; ++i) s0 += (f->recs[(size_t)i].len + 63) / 64;
@@ -1423,23 +832,8 @@ int idl_fasta_pack_range(const idl_fasta *f, int64_t rec_lo, int64_t rec_hi, uin
         boff[(size_t)i + 1] = boff[(size_t)i] + r.len;
         soff[(size_t)i + 1] = soff[(size_t)i] + (r.len + 63) / 64;
     }
-    const int64_t total = boff[(size_t)m];
-    const int nt = (total > (int64_t)par_min_bytes() && m >= 2) ? n_threads() : 1;
-    parallel_for(nt, [&](int t) {
-        const int64_t lo = total * t / nt, hi = total * (t + 1) / nt;
-        int64_t i0 = std::lower_bound(boff.begin(), boff.begin() + m, lo) - boff.begin();
-        int64_t i1 = (t == nt - 1) ? m : std::lower_bound(boff.begin(), boff.begin() + m, hi) - boff.begin();
-        if (t == 0) i0 = 0;
-        for (int64_t i = i0; i < i1; ++i) {
-            const Rec &r = f->recs[(size_t)(rec_lo + i)];
-            uint8_t bb = 0;
-            uint8_t *bdst = nullptr;
-            Packer pk{(uint32_t *)(codes + soff[(size_t)i] * 16), (uint32_t *)(mask + soff[(size_t)i] * 8)};
-            if (f->check) walk_record_pack(buf, r, pk, bdst);
-            else (void)walk_record(buf, r, f->check, [&](uint8_t c) { pk.push(T.code[c]); }, &bb);
-            pk.finish((r.len + 63) / 64);
-        }
-    });
+    const int nt = (boff[(size_t)m] > (int64_t)par_min_bytes() && m >= 2) ? n_threads() : 1;
+    pack_records(f, rec_lo, m, boff.data(), soff.data(), nt, nullptr, codes, mask);
     return IDL_OK;
 }
 

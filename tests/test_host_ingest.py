@@ -188,12 +188,9 @@ def test_threaded_reader_equals_oracle(tmp_path, monkeypatch, threads):
             assert np.array_equal(ff.codes[a * 16:b * 16], codes) and np.array_equal(ff.mask[a * 8:b * 8], mask), i
 
 
-@pytest.mark.parametrize("width", [0, 70, 33, 16, 64, 128, 200])
-def test_reader_fast_paths_equal_oracle(tmp_path, width):
-    """Long runs of upper-case A/C/G/T take the 64-base (AVX-512, at slot boundaries) / 32-base (AVX2) / 8-base (SWAR) paths of the reader; mixed with N runs, lower case,
-    IUPAC codes and gaps at every alignment they must give exactly the bytes, lengths, codes and masks of the byte-wise walk."""
+def _fast_path_fasta(p, width):
+    """40 records of up to 4 000 bases in lines of `width` (0: one line), long clean runs with short exceptional stretches at random offsets."""
     rng = np.random.default_rng(100 + width)
-    p = str(tmp_path / "fast.fas")
     with open(p, "wb") as f:
         for r in range(40):
             L = int(rng.integers(0, 4000))
@@ -207,6 +204,17 @@ def test_reader_fast_paths_equal_oracle(tmp_path, width):
             if width == 0: f.write(raw + b"\n")
             else:
                 for a in range(0, len(raw), width): f.write(raw[a:a + width] + b"\n")
+
+
+FAST_PATH_WIDTHS = [0, 70, 33, 16, 64, 128, 200]
+
+
+@pytest.mark.parametrize("width", FAST_PATH_WIDTHS)
+def test_reader_fast_paths_equal_oracle(tmp_path, width):
+    """Long runs of upper-case A/C/G/T take the 64-base (AVX-512, at slot boundaries) / 32-base (AVX2) / 8-base (SWAR) paths of the reader; mixed with N runs, lower case,
+    IUPAC codes and gaps at every alignment they must give exactly the bytes, lengths, codes and masks of the byte-wise walk."""
+    p = str(tmp_path / "fast.fas")
+    _fast_path_fasta(p, width)
     ff = U.FastaFile(p, check=True, keep_bytes=True)
     recs = list(O.fasta_records(p, check=True))
     assert ff.lengths.tolist() == [len(r[1]) for r in recs]
@@ -317,6 +325,26 @@ def test_one_pass_reader_equals_general_reader(tmp_path, monkeypatch, threads):
             assert np.array_equal(mask[s * 8:(s + b - a) * 8], whole.mask[a * 8:b * 8]), i
         starts = ff.slot_off[:-1]
         assert np.all(np.diff(starts) >= (whole.slot_off[1:-1] - whole.slot_off[:-2]))        # never overlapping, in file order
+
+
+@pytest.mark.parametrize("width", FAST_PATH_WIDTHS)
+def test_one_pass_reader_fast_paths_equal_oracle(tmp_path, monkeypatch, width):
+    """The same files as test_reader_fast_paths_equal_oracle through the one-pass reader (host arenas, one thread and three): its walk over a record's
+    lines and its 64 / 32 / 16-base paths give the names, the lengths and, at the slots it reports, the codes and masks of the oracle.  None of these
+    files has a layout the one-pass reader may leave to the general one, so a fallback is a failure."""
+    p = str(tmp_path / "fast.fas")
+    _fast_path_fasta(p, width)
+    recs = [(name, O.pack(s), len(s)) for name, s in O.fasta_records(p, check=True)]
+    dev_env(monkeypatch, par_min="0")
+    for threads in ("1", "3"):
+        monkeypatch.setenv("IDELUCS_THREADS", threads)
+        got = _one_pass(p)
+        assert got is not None, "the one-pass reader declined a file it should take"
+        ff, codes, mask = got
+        assert ff.names == [r[0] for r in recs] and ff.lengths.tolist() == [r[2] for r in recs]
+        for i, (_, (c, m), _) in enumerate(recs):
+            a = int(ff.slot_off[i])
+            assert np.array_equal(codes[a * 16:a * 16 + c.size], c) and np.array_equal(mask[a * 8:a * 8 + m.size], m), (threads, i)
 
 
 @pytest.mark.parametrize("content", [
