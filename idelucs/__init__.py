@@ -8,10 +8,10 @@ import idelucs_amd
 from idelucs_amd import *                                    # noqa: F401,F403  (the reference's __all__ = the sub-modules)
 from idelucs_amd import (IID_loss, IID_model, AugmentFasta, SequenceDataset, SummaryFasta, cgr, cgrFasta, check_sequence,  # noqa: F401
                          cluster_acc, create_dataloader, iDeLUCS_cluster, info_nce_loss, kmer_counts, kmer_rev_comp, kmersFasta,
-                         reverse_complement)
+                         reverse_complement, FittedEnsemble)
 from idelucs_amd import LossFunctions, PytorchUtils, cluster, kmers, models, utils   # noqa: F401
 
 __version__ = idelucs_amd.__version__
 __all__ = idelucs_amd.__all__
-for _name in ("utils", "kmers", "models", "cluster", "LossFunctions", "PytorchUtils", "posthoc", "dist", "fused", "training"):
+for _name in ("utils", "kmers", "models", "cluster", "LossFunctions", "PytorchUtils", "posthoc", "dist", "fused", "training", "ensemble"):
     sys.modules[f"{__name__}.{_name}"] = importlib.import_module(f"idelucs_amd.{_name}")

@@ -20,5 +20,8 @@ SequenceDataset, create_dataloader, cluster_acc = utils.SequenceDataset, utils.c
 IID_model = models.IID_model
 IID_loss, info_nce_loss = LossFunctions.IID_loss, LossFunctions.info_nce_loss
 iDeLUCS_cluster = cluster.iDeLUCS_cluster
+# a trained ensemble kept and applied to new sequences (not in the reference)
+from . import ensemble  # noqa: E402,F401
+FittedEnsemble = ensemble.FittedEnsemble
 
 __all__ = ["utils", "kmers", "models", "cluster", "LossFunctions"]

@@ -25,6 +25,40 @@ def save_results_in_file(dataset_name, model_name, model_parameters, results, ti
         w.writerow([dataset_name, model_name, model_parameters] + list(results.values()) + [time_, memory])
 
 
+def _results_dir(sequence_file):
+    """./Results/<stem of the file>/<time stamp> (reference __main__.py:60-73)."""
+    stamp = time.asctime().split(" ")
+    stamp = [s for s in stamp if s]
+    stamp[3] = "-".join(stamp[3].split(":"))
+    time_stamp = "_".join(stamp[1:-1])
+    results_folder = os.path.join(os.getcwd(), "Results", os.path.basename(sequence_file).split(".")[0])
+    return os.path.join(results_folder, time_stamp)
+
+
+def _write_assignments(out_dir, names, y_pred, probabilities):
+    import pandas as pd
+    names = np.array(names)
+    data = np.concatenate((names[:, np.newaxis], y_pred[:, np.newaxis], probabilities[:, np.newaxis]), axis=1)
+    pd.DataFrame(data, columns=["sequence_id", "assignment", "confidence_score"]).to_csv(
+        os.path.join(out_dir, "assignments.tsv"), sep="\t")
+
+
+def run_assign(args):
+    """--assign FASTA --model DIR: no training -- the saved ensemble of an earlier run (--save_model) labels the sequences of another
+    file; ./Results/<stem of FASTA>/<time stamp>/assignments.tsv with the training run's three columns."""
+    from .ensemble import FittedEnsemble
+    ens = FittedEnsemble.load(args["model"])
+    out_dir = _results_dir(args["assign"])
+    os.makedirs(out_dir, exist_ok=False)
+    names, y_pred, probabilities = ens.assign(args["assign"])
+    _write_assignments(out_dir, names, y_pred, probabilities)
+    print(f"No. Sequences: \t {len(names):,}")
+    for c, n_c in zip(*np.unique(y_pred, return_counts=True)):
+        print(f"Cluster {c}: \t {n_c:,}")
+    print(f"Assignments: \t {os.path.join(out_dir, 'assignments.tsv')}")
+    return out_dir
+
+
 def run(args):
     import pandas as pd
     import torch
@@ -43,12 +77,15 @@ def run(args):
 
     # the output folder first (reference __main__.py:60-73), BEFORE any collective exists: a rank 0 that cannot create it fails
     # here, alone, instead of leaving the other ranks waiting in a collective
-    stamp = time.asctime().split(" ")
-    stamp = [s for s in stamp if s]
-    stamp[3] = "-".join(stamp[3].split(":"))
-    time_stamp = "_".join(stamp[1:-1])
-    results_folder = os.path.join(os.getcwd(), "Results", os.path.basename(args["sequence_file"]).split(".")[0])
-    out_dir = os.path.join(results_folder, time_stamp)
+    # --save_model DIR: what the run learns is kept (ensemble.FittedEnsemble); its limits and an existing file are refused before any work
+    save_dir = args.pop("save_model", None)
+    capture = None
+    if save_dir is not None:
+        from . import ensemble
+        ensemble.check_scope(args["k"], args["model_size"])
+        ensemble.check_not_saved(save_dir)
+        capture = ensemble.VoterCapture(only=args["n_voters"] - 1 if args["n_clusters"] == 0 else None)
+    out_dir = _results_dir(args["sequence_file"])
     if rank == 0:
         os.makedirs(out_dir, exist_ok=False)
 
@@ -78,11 +115,15 @@ def run(args):
         print(f"Avg. Length: \t {round(np.mean(model.lengths), 2):,}")
     n = len(model.names)
 
-    local_preds, curves, latent = {}, {}, None
+    local_preds, curves, latent, raw_votes = {}, {}, None, {}
     # this rank's voters, several at a time on their own HIP streams (training.train_voters)
-    trained = train_voters(model, D.voters_of_rank(args["n_voters"], rank, world), args["n_epochs"], args["n_voters"], progress=rank == 0)
+    trained = train_voters(model, D.voters_of_rank(args["n_voters"], rank, world), args["n_epochs"], args["n_voters"], progress=rank == 0,
+                           on_voter=capture)
+    n_units = args["n_clusters"]
     for voter, (curve, y_pred, probabilities, lat) in trained.items():
         curves[voter] = curve
+        if capture is not None:
+            raw_votes[voter] = y_pred
         if voter == args["n_voters"] - 1:
             latent = lat                                          # the reference scores/clusters the LAST voter's latent
         local_preds[voter] = torch.from_numpy(posthoc.relabel_first_occurrence(y_pred)).to(model.device)
@@ -184,14 +225,21 @@ def run(args):
     memory = info.ru_maxrss / 1e6
     print(f"training took: {hh}:{mm}:{round(ss)} (hh:mm:ss) and {memory} (GB)")
 
-    names = np.array(model.names)
-    data = np.concatenate((names[:, np.newaxis], y_pred[:, np.newaxis], probabilities[:, np.newaxis]), axis=1)
-    pd.DataFrame(data, columns=["sequence_id", "assignment", "confidence_score"]).to_csv(
-        os.path.join(out_dir, "assignments.tsv"), sep="\t")
+    _write_assignments(out_dir, model.names, y_pred, probabilities)
     pd.Series(results, name="Value").to_csv(os.path.join(out_dir, "metrics.tsv"), sep="\t")
     save_results_in_file(dataset_name, "iDeLUCS", params, results, f"{hh}:{mm}:{round(ss)}", memory,
                          os.path.join(os.getcwd(), "ALL_RESULTS.tsv"))
     mark("tables")
+    if capture is not None:
+        order = sorted(capture.states)
+        if use_hdbscan:
+            ens = ensemble.FittedEnsemble.from_latent(args["sequence_file"], args["k"], args["model_size"], capture.states[order[-1]], latent,
+                                                      y_pred, probabilities, device=model.device)
+        else:
+            ens = ensemble.FittedEnsemble.from_votes(args["sequence_file"], args["k"], args["model_size"], [capture.states[v] for v in order],
+                                                     [raw_votes[v] for v in order], preds, y_pred, n_units, device=model.device)
+        print(f"Saved model: \t {ens.save(save_dir)}")
+        mark("saved ensemble")
     if os.environ.get("IDELUCS_TIMING"):
         print("stages: " + ", ".join(f"{name} {t1 - t0:.1f} s" for (_, t0), (name, t1) in zip(marks[:-1], marks[1:])))
 
@@ -254,11 +302,25 @@ def build_parser():
                    help="where the training rows live: the [views, N, 4^k] feature store resident in HBM (the default), or streamed -- every batch "
                         "vectorised from the packed bases when it is needed, predict in row chunks: no N x 4^k buffer in the run "
                         "(model_size='linear', 4 <= k <= 9, --rng philox)")
+    p.add_argument("--save_model", action="store", type=str, default=argparse.SUPPRESS, metavar="DIR",
+                   help="a training run: keep the voters' weights, the predict scaler and the ensemble's vote tables (n_clusters = 0: the last "
+                        "voter's latent with its clusters) in DIR/ensemble.pt, for --assign")
+    p.add_argument("--assign", action="store", type=str, default=argparse.SUPPRESS, metavar="FASTA",
+                   help="no training: assign the sequences of FASTA to the clusters of the run saved in --model DIR")
+    p.add_argument("--model", action="store", type=str, default=argparse.SUPPRESS, metavar="DIR",
+                   help="the directory of an earlier run's --save_model, for --assign")
     return p
 
 
 def main(argv=None):
-    args = vars(build_parser().parse_args(argv))
+    parser = build_parser()
+    args = vars(parser.parse_args(argv))
+    if "assign" in args or "model" in args:
+        if not ("assign" in args and "model" in args):
+            parser.error("--assign FASTA and --model DIR go together")
+        if "save_model" in args:
+            parser.error("--save_model belongs to a training run, not to --assign")
+        return run_assign(args)
     if args["small_step"] is None:          # (absent: the printed parameters and the results table stay as they were)
         del args["small_step"]
     if int(os.environ.get("RANK", "0")) == 0:

@@ -151,6 +151,8 @@ SIGNATURES = {
     "idl_knn_window": (_int, [_vp, _i64, _int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "idl_knn_select": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
     "idl_knn_graph": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _i64, _i64, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "idl_nn_rows": (_int, [_vp, _i64, _vp, _i64, _int, _i64, _vp, _vp, _vp]),
+    "idl_nn_rows_slices": (_int, [_i64, _i64]),
     "idl_umap_smooth_knn": (_int, [_vp, _vp, _i64, _int, _c.c_double, _vp, _vp, _vp, _vp]),
     "idl_umap_layout_epoch": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _c.c_float, _c.c_uint64, _vp]),
     "idl_umap_draws": (_int, [_c.c_uint64, _i64, _i64, _int, _int, _i64, _vp, _vp]),

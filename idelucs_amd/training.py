@@ -16,8 +16,9 @@ def prepare_model(args):
     return model
 
 
-def train_voter(model, n_epochs, voter=0, n_voters=1, progress=True):
-    """One voter: fresh Kaiming init, n_epochs epochs, predict.  -> (loss curve, y_pred, probabilities, latent)."""
+def train_voter(model, n_epochs, voter=0, n_voters=1, progress=True, on_voter=None):
+    """One voter: fresh Kaiming init, n_epochs epochs, predict.  -> (loss curve, y_pred, probabilities, latent).
+    on_voter(voter, net): called right after the voter's predict, while `net` still holds its weights (the next voter re-initialises it)."""
     if progress:
         sys.stdout.write(f"\r........... Training Model ({voter + 1}/{n_voters})................")
         sys.stdout.flush()
@@ -25,7 +26,10 @@ def train_voter(model, n_epochs, voter=0, n_voters=1, progress=True):
         model.begin_voter(voter)
         try:
             curve = [model.contrastive_training_epoch() for _ in range(n_epochs)]
-            return (curve,) + tuple(model.predict())
+            res = (curve,) + tuple(model.predict())
+            if on_voter is not None:
+                on_voter(voter, model.net)
+            return res
         except models.PlanesOverflow as err:
             # the data (or a diverging run) does not fit the fp16 planes: the fp32 tiles for the rest of this process, and this voter again from
             # its start -- begin_voter re-seeds every stream it draws from, so the rerun is exactly the IDELUCS_PLANES=0 run
@@ -110,12 +114,14 @@ def can_batch(model):
     return bool(model.n_clusters <= 48 or lockstep_rows_applies(model))
 
 
-def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=True):
+def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=True, on_voter=None):
     """The voters this rank owns -> {voter: (loss curve, y_pred, probabilities, latent)}.  Every voter draws from its own RNG
     streams and starts from fresh optimizer state (IID_model.begin_voter), so when and beside whom it trains does not change
     what it is.  Voters run `lanes` at a time in lockstep (fused.BatchedLinearTrainer: one launch sequence for the whole batch of
     voters, each on its own network / permutation / dropout stream / optimizer state; IID_model.lane()); nothing waits on the
-    host until a batch's predicts."""
+    host until a batch's predicts.
+    on_voter(voter, net): called right after every voter's predict with the network that holds its weights -- in lockstep the lane's, before the
+    next wave of voters reuses it (ensemble.FittedEnsemble keeps the weights this way)."""
     from .fused import BatchedLinearTrainer
     voters = list(voters)
     n_voters = n_voters if n_voters is not None else len(voters)
@@ -127,13 +133,13 @@ def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=Tr
                              "run without a launcher, or leave the default (independent voters)")
         lanes = 1
     if lanes <= 1 or not can_batch(model):
-        return {v: train_voter(model, n_epochs, v, n_voters, progress) for v in voters}
+        return {v: train_voter(model, n_epochs, v, n_voters, progress, on_voter) for v in voters}
     out = {}
     lane_models, batched = None, None
     for w in range(0, len(voters), lanes):
         wave = voters[w:w + lanes]
         if len(wave) == 1:                                   # a last voter on its own: the single-voter path
-            out[wave[0]] = train_voter(model, n_epochs, wave[0], n_voters, progress)
+            out[wave[0]] = train_voter(model, n_epochs, wave[0], n_voters, progress, on_voter)
             continue
         if batched is None or batched.L != len(wave):
             lane_models = [model.lane() for _ in wave]
@@ -163,6 +169,8 @@ def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=Tr
                             m._check_planes()
                 for m, v in zip(lane_models, wave):
                     out[v] = ([float(x) for x in curves[v]],) + tuple(m.predict())
+                    if on_voter is not None:
+                        on_voter(v, m.net)
                 break
             except models.PlanesOverflow as err:     # (as train_voter: the fp32 form, and the whole batch of voters again)
                 if attempt or not _leave_planes(lane_models + [model], err):
@@ -172,7 +180,7 @@ def train_voters(model, voters, n_epochs, n_voters=None, lanes=None, progress=Tr
                     # beyond 48 classes there is no fp32 form to record: this batch's voters and the remaining ones one after the other on the
                     # fp32 tiles, which is the IDELUCS_PLANES=0 run
                     for v in voters[w:]:
-                        out[v] = train_voter(model, n_epochs, v, n_voters, progress)
+                        out[v] = train_voter(model, n_epochs, v, n_voters, progress, on_voter)
                     return out
     # the caller goes on with `model`: leave it holding the LAST voter's weights, as after a sequential run
     if lane_models is not None and len(voters) % lanes != 1:

@@ -864,8 +864,45 @@ def predict_feature_chunks(sequence_file, k=6, reduce=False, device=None, rows=N
         ff.close()
 
 
-def feature_chunks_of_input(din, k, reduce=False, rows=None, chunk_rows=None, padded=False):
-    """predict_feature_chunks on packed bases that are on the device already (a _DeviceInput or its like)."""
+def _predict_scaler_pass(din, k, reduce, chunk_rows, counts=None):
+    """Pass 1 of feature_chunks_of_input -> (mean, scale, totals [n]); counts: its [chunk rows, F] int32 buffer, when the caller has one."""
+    mode = _lib.MODE_CANONICAL if reduce else _lib.MODE_KMER
+    f = int(_L.idl_row_len(mode, k))
+    dev = din.codes.device
+    n = din.n
+    cr = min(predict_chunk_rows(f, chunk_rows), n)
+    if counts is None:
+        counts = torch.empty((cr, f), dtype=torch.int32, device=dev)
+    totals = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(_L.idl_counts_stream_workspace(n, f), 8), dtype=torch.uint8, device=dev)
+    for a in range(0, n, cr):
+        b = min(a + cr, n)
+        _vectorise(_RowRange(din, a, b), k, mode, _lib.INIT_ONE, _lib.OUT_COUNTS_I32, out=counts[:b - a].unsqueeze(0))
+        _lib.check(_L.idl_row_totals_i32(_ptr(counts), b - a, f, _ptr(totals[a:b]), _stream_ptr()))
+        _lib.check(_L.idl_counts_stream_stats(_ptr(counts), _ptr(totals[a:b]), a, b - a, n, f, _ptr(ws), _stream_ptr()))
+    mean = torch.empty(f, dtype=torch.float64, device=dev)
+    scale = torch.empty(f, dtype=torch.float64, device=dev)
+    _lib.check(_L.idl_counts_stream_finish(n, f, _ptr(ws), _ptr(mean), _ptr(scale), _stream_ptr()))
+    return mean, scale, totals
+
+
+def predict_scaler(din, k, reduce=False, chunk_rows=None):
+    """The StandardScaler statistics behind the predict inputs of the file in `din` (a _DeviceInput or its like) -> (mean, scale), float64 [F]
+    on the device: pass 1 of feature_chunks_of_input alone, and predict_features' statistics bit for bit.  Kept by a saved ensemble
+    (ensemble.FittedEnsemble) and handed back as feature_chunks_of_input(stats=...): new rows are standardised with the TRAINING file's
+    statistics, not their own."""
+    if not stream_route_ok(k, reduce):
+        raise ValueError(f"predict_scaler: k={k}, reduce={reduce} gives no row length that is a multiple of 4")
+    if din.n < 1:
+        raise ValueError("predict_scaler needs at least one sequence")
+    mean, scale, _ = _predict_scaler_pass(din, k, reduce, chunk_rows)
+    return mean, scale
+
+
+def feature_chunks_of_input(din, k, reduce=False, rows=None, chunk_rows=None, padded=False, stats=None):
+    """predict_feature_chunks on packed bases that are on the device already (a _DeviceInput or its like).
+    stats=(mean, scale), float64 [F] on the device (predict_scaler of another file): pass 1 is skipped -- pass 2 computes every chunk's row
+    totals itself and standardises with the given statistics."""
     mode = _lib.MODE_CANONICAL if reduce else _lib.MODE_KMER
     f = int(_L.idl_row_len(mode, k))
     dev = din.codes.device
@@ -877,23 +914,22 @@ def feature_chunks_of_input(din, k, reduce=False, rows=None, chunk_rows=None, pa
         return
     cr = min(predict_chunk_rows(f, chunk_rows), n)
     counts = torch.empty((cr, f), dtype=torch.int32, device=dev)
-    totals = torch.empty(n, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(_L.idl_counts_stream_workspace(n, f), 8), dtype=torch.uint8, device=dev)
-    for a in range(0, n, cr):
-        b = min(a + cr, n)
-        _vectorise(_RowRange(din, a, b), k, mode, _lib.INIT_ONE, _lib.OUT_COUNTS_I32, out=counts[:b - a].unsqueeze(0))
-        _lib.check(_L.idl_row_totals_i32(_ptr(counts), b - a, f, _ptr(totals[a:b]), _stream_ptr()))
-        _lib.check(_L.idl_counts_stream_stats(_ptr(counts), _ptr(totals[a:b]), a, b - a, n, f, _ptr(ws), _stream_ptr()))
-    mean = torch.empty(f, dtype=torch.float64, device=dev)
-    scale = torch.empty(f, dtype=torch.float64, device=dev)
-    _lib.check(_L.idl_counts_stream_finish(n, f, _ptr(ws), _ptr(mean), _ptr(scale), _stream_ptr()))
-    del ws
+    if stats is None:
+        mean, scale, totals = _predict_scaler_pass(din, k, reduce, chunk_rows, counts)
+    else:
+        mean, scale = stats
+        for t in (mean, scale):
+            if not (t.dtype == torch.float64 and t.numel() == f and t.is_contiguous() and t.device == dev):
+                raise ValueError(f"stats must be contiguous float64 [{f}] tensors on {dev}")
+        totals = torch.empty(n, dtype=torch.int32, device=dev)
     # pass 2 on the chunk grid of pass 1 (multiples of cr from row 0), each row at its place in its grid chunk: a row range asked for
     # alone is cut where the whole file is cut
     out = (torch.zeros if padded else torch.empty)((cr, f), dtype=torch.float32, device=dev)
     for g in range(lo // cr * cr, hi, cr):
         a, b = max(g, lo), min(g + cr, hi)
         _vectorise(_RowRange(din, a, b), k, mode, _lib.INIT_ONE, _lib.OUT_COUNTS_I32, out=counts[:b - a].unsqueeze(0))
+        if stats is not None:
+            _lib.check(_L.idl_row_totals_i32(_ptr(counts), b - a, f, _ptr(totals[a:b]), _stream_ptr()))
         _lib.check(_L.idl_counts_standardise(_ptr(counts), _ptr(totals[a:b]), b - a, f, _ptr(mean), _ptr(scale), _ptr(out[a - g:]), _stream_ptr()))
         if padded:
             yield a, b, out, a - g
