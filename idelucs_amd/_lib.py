@@ -40,6 +40,13 @@ class idl_opt_tail_t(_c.Structure):
                 ("wg_n_out", _int), ("wg_n_in", _int), ("wg_grad", _vp), ("batch_advance", _i64)]
 
 
+class idl_vectorise_plan_t(_c.Structure):
+    """What idl_vectorise would launch (include/idelucs_hip.h): kernel is one of VEC_*; redo != 0: a second pass on v2 follows."""
+    _fields_ = [(name, _int) for name in ("kernel", "copies_log2", "other_modes", "diag", "threads", "lds_bytes", "wg_per_cu", "grid", "waves", "sc_slots",
+                                          "v3_sc", "ecap", "lcap", "chunk", "ablate", "redo", "redo_sc_slots", "redo_v3_sc", "redo_lds_bytes", "redo_grid")]
+
+
+VEC_V1, VEC_V2, VEC_V2_B16, VEC_V3, VEC_V4, VEC_SLICES = 1, 2, 3, 4, 5, 6
 _nb, _tail = _c.POINTER(idl_next_batch_t), _c.POINTER(idl_opt_tail_t)
 
 # name -> (restype, argtypes); kept in one table so tests can check every symbol the header declares
@@ -166,6 +173,7 @@ SIGNATURES = {
     "idl_vectorise_ranges": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _i64, _i64, _vp]),
     "idl_vectorise_slices_lds": (_int, []),
     "idl_vectorise_slices_per_cu": (_int, []),
+    "idl_vectorise_plan": (_int, [_int, _int, _int, _int, _int, _int, _i64, _i64, _c.POINTER(idl_vectorise_plan_t)]),
     "idl_plan_bytes": (_i64, []),
     "idl_plan_begin": (_int, [_vp]),
     "idl_plan_end": (_int, []),

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "scaler_device.h"
+#include "vectorise_plan.h"     // the launch policy; vectorise_layout.h: the kernels' LDS constants and sizes
 
 namespace {
 
@@ -56,7 +57,6 @@ __device__ __forceinline__ int64_t eo_begin(const VecArgs &a, int64_t it) { retu
 __device__ __forceinline__ int64_t eo_end(const VecArgs &a, int64_t it) { return a.edit_off[(it << a.eo_shift) + 1]; }
 
 
-constexpr int STAGE_DWORDS = 256 + 128;  // 64 lanes x (4 code words + 2 mask words)
 constexpr int V3_REDO_CAP = 1023;        // sequences the v3 kernel can list for the second pass on v2 (beyond that the second pass scans)
 
 __device__ __forceinline__ uint32_t spread_bits(uint32_t x)
@@ -304,19 +304,17 @@ __global__ __launch_bounds__(64) void vectorise_kernel(VecArgs a)
 // multiplying with the row's correctly rounded reciprocal plus one FMA correction (Markstein; verified
 // bit-identical to float32(float64 division) for all 1 <= c <= S < 2^24 by tools/markstein_check.c).
 // =====================================================================================================
-constexpr int V2_LIST_CAP = 768;   // (edit, window) pairs recorded per view for a replay-undo
-constexpr int V2_EDIT_CAP = 192;   // edits of a view preloaded into LDS
-constexpr int V2_WAVES = 4;        // wavefronts per sequence
+// (V2_LIST_CAP, V2_EDIT_CAP, V2_WAVES and the LDS size: vectorise_layout.h)
 
 // B16: two 16-bit bins per LDS word (valid while every count stays < 65536, i.e. sequences shorter than ~65 kbp):
 // half the histogram footprint -> more sequences resident per CU.
 template <int K, bool B16>
 struct V2 {
     static constexpr int NT = 64 * V2_WAVES;   // threads (V2_WAVES wavefronts) that share one sequence and one LDS histogram
-    static constexpr int F = 1 << (2 * K);
+    static constexpr int F = vec_bins(K);
     static constexpr uint32_t KM = (1u << (2 * K)) - 1u;
     static constexpr uint32_t VM = (1u << K) - 1u;
-    static constexpr int HD = B16 ? (F / 2 + 4) & ~3 : F + 4;      // histogram words incl. 4 garbage bins (kept a multiple of 4)
+    static constexpr int HD = v2_hist_words(K, B16);               // histogram words incl. 4 garbage bins (kept a multiple of 4)
 
     static __device__ __forceinline__ void bump(uint32_t *hist, uint32_t bin, uint32_t sign)   // sign = 1 or 0xFFFFFFFF (-1)
     {
@@ -720,10 +718,7 @@ __global__ __launch_bounds__(64 * V2_WAVES, B16 ? 8 : 6) void vectorise2_kernel(
 //   * 9 barriers per sequence instead of 40; window counts travel through LDS counters instead of block reductions.
 // A sequence whose edits / pairs do not fit the LDS tables takes a slower in-kernel path (per-view pair passes, like v2).
 // =====================================================================================================
-constexpr int V3_MAXV = 8;                      // views
-constexpr int V3_META = 8 + 4 * V3_MAXV;        // dwords of a meta ring entry: slot_off[s], slot_off[s+1], lengths[s], pad; per view edit_off[v*n+s], [..+1]
-constexpr int V3_VT = 4;                        // dwords of a view-table row: edits, first edit's index in LDS, first pair's index in the list, spare
-constexpr int V3_VTAB = (V3_MAXV + 1) * V3_VT;  // row 0 = header: flags (1 fast, 2 edits staged), total pairs, staged slots, clamped length
+// (V3_MAXV, V3_META, V3_VT, V3_VTAB and the LDS size: vectorise_layout.h)
 
 __device__ __forceinline__ uint32_t lds_addr(const void *p) { return (uint32_t)(uintptr_t)p; }   // LDS byte offset = low half of the flat address
 
@@ -770,8 +765,8 @@ __device__ __forceinline__ void vm_wait_at_most(int younger)
 template <int K, int RL = 0>
 struct V3 {
     using T = V2<K, false>;
-    static constexpr int F = T::F, HC = RL ? (F + 4) << RL : 0;           // words of the copies (F bins + 4 garbage bins each)
-    static constexpr int HD = HC + T::HD;                                  // ... followed by the histogram proper: F bins + 4 garbage bins
+    static constexpr int F = T::F, HC = v3_copy_words(K, RL);             // words of the copies (F bins + 4 garbage bins each)
+    static constexpr int HD = v3_hist_words(K, RL);                                // ... followed by the histogram proper: F bins + 4 garbage bins
     static constexpr uint32_t KM = T::KM, VM = T::VM;
     static_assert(RL == 0 || (F + 4) * 4 < 65536, "bin byte offsets travel as 16 bits");
     // byte offset of bin (given as its byte offset in ONE copy) in the copy of the lane whose offset is lo = (lane mod 2^RL) * 4
@@ -901,9 +896,7 @@ struct V3 {
 // registers between two barriers, then converts and stores while the compute waves are already moving the histogram to the
 // next view).  A full store queue -- the chip's write stream is the bound of this kernel -- therefore stalls only the wave that
 // has nothing else to do, and the DMA waits of that wave never queue behind another wave's work.
-constexpr int V3_NC = 384;                      // compute threads (6 waves)
-constexpr int V3_MW = 2;                        // memory waves, each holding 1 / V3_MW of a row
-constexpr int V3_NT = V3_NC + 64 * V3_MW;
+// (V3_NC compute threads, V3_MW memory waves, V3_NT: vectorise_layout.h)
 
 template <int K, bool DIAG, int RL>
 __global__ __launch_bounds__(V3_NT, 8) void vectorise3_kernel(VecArgs a)
@@ -917,7 +910,7 @@ __global__ __launch_bounds__(V3_NT, 8) void vectorise3_kernel(VecArgs a)
     static_assert(RL == 0 || (RL >= 2 && RL <= 5), "2^RL copies of the histogram: 4 .. 32");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int SC = a.sc_slots, P = a.n_views;
-    const int SET = (SC + 1) * 6 + a.ecap;                  // words of one staging set
+    const int SET = v3_set_words(SC, a.ecap);               // words of one staging set
     uint32_t *copies = lds;                                 // RL > 0: 2^RL copies of (F bins + 4 garbage bins), the COUNT's target
     uint32_t *hist = lds + HC;                              // F bins + 4 garbage bins
     uint32_t *sets = lds + HD;                              // two staging sets (sequence it lives in set it & 1), each:
@@ -1219,9 +1212,7 @@ __global__ __launch_bounds__(V3_NT, 8) void vectorise3_kernel(VecArgs a)
 // Sequences are dealt round-robin over the launch's waves.  A sequence that does not fit the slice (v3's predicate: edits, pairs,
 // slots) is listed for the second pass on v2, as v3 does.
 // =====================================================================================================
-constexpr int V4_MAX_WAVES = 12;                // waves of a workgroup: as many as the slices of LDS allow (the launcher decides)
-constexpr int V4_SR = 3;                        // rounds of 64 slots a sequence may take (12 288 bases); longer inputs stay on v3 / v2
-constexpr int V4_FR = 10;                       // rounds of 64 edits (ALL views of a sequence, one after the other) prefetched into registers; more: second pass
+// (V4_MAX_WAVES, V4_SR, V4_FR and the slice's size: vectorise_layout.h)
 
 // OM ("other modes"): the CGR and canonical rows (reference utils.py:279-317, 208-221 -- round 6) as epilogues over the finished histogram, in an
 // instance of their own so that their registers (a lane's 4^k / 64 collapsed bins) do not count against the plain rows'.
@@ -1235,7 +1226,7 @@ __global__ __launch_bounds__(64 * V4_MAX_WAVES) void vectorise4_kernel(VecArgs a
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int P = a.n_views, SC = a.v3_sc;
-    const int slice = (HC + (F + 4) + (SC + 1) * 6 + a.ecap + 3) & ~3;
+    const int slice = (HC + (F + 4) + (SC + 1) * 6 + a.ecap + 3) & ~3;        // (= v4_slice_words(K, RL, SC, a.ecap), vectorise_layout.h; calling it here changes the generated code)
     uint32_t *copies = lds + (size_t)wv * slice, *hist = copies + HC, *cod = hist + F + 4, *msk = cod + (SC + 1) * 4, *E = msk + (SC + 1) * 2;
     const uint32_t iv = (a.init == IDL_INIT_ONE) ? 1u : 0u;
     const uint32_t garbage = ((uint32_t)F + (lane & 3)) << 2;
@@ -1538,22 +1529,85 @@ int *redo_counter(hipStream_t st)
     return p;
 }
 
+#include "vectorise_slices.h"   // k = 8, 9: the histogram exceeds one CU's LDS
+#include "vectorise_pairs.h"    // a training batch's rows straight from the packed bases (idl_vectorise_pairs_at)
+
+// ---------------------------------------------------------------- the launcher: what plan_vectorise (vectorise_plan.h) says, launched
+// plan -> the kernel's template instance; the only place that names the instances (nullptr: the plan never asks for that one)
 template <int K, int RL>
-int launch_vectorise3_k(VecArgs &a, const idl::DeviceInfo &di, hipStream_t st, size_t lds, int per_cu)
+const void *v4_instance(bool om) { return om ? (const void *)vectorise4_kernel<K, RL, true> : (const void *)vectorise4_kernel<K, RL, K == 6>; }
+template <int K, int RL>
+const void *v3_instance(bool diag) { return diag ? (const void *)vectorise3_kernel<K, true, RL> : (const void *)vectorise3_kernel<K, false, RL>; }
+
+template <int K>
+const void *vec_instance_k(int kernel, int rl, bool om, bool diag)
 {
-    const bool dbg = idl::dev_env("vec_dbg") != nullptr;
-    const void *fn = dbg ? (const void *)vectorise3_kernel<K, true, RL> : (const void *)vectorise3_kernel<K, false, RL>;
-    if (lds > 64 * 1024) IDL_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int64_t grid = (int64_t)di.cus * per_cu;
-    if (grid > a.n) grid = a.n;
-    a.redo_count = redo_counter(st);
-    if (a.redo_count == nullptr) { idl::set_error("cannot allocate the v3 hand-over word"); return IDL_ERR_HIP; }
-    IDL_HIP_TRY(hipMemsetAsync(a.redo_count, 0, 2 * sizeof(int), st));      // [0] sequences left to the second pass, [1] head of the sequence queue
-    if (dbg) { IDL_HIP_TRY(hipMalloc((void **)&a.dbg, (size_t)grid * 20 * 8)); IDL_HIP_TRY(hipMemset(a.dbg, 0, (size_t)grid * 20 * 8)); }
-    if (dbg) hipLaunchKernelGGL((vectorise3_kernel<K, true, RL>), dim3((unsigned)grid), dim3(V3_NT), lds, st, a);
-    else hipLaunchKernelGGL((vectorise3_kernel<K, false, RL>), dim3((unsigned)grid), dim3(V3_NT), lds, st, a);
-    IDL_HIP_TRY(hipGetLastError());
-    if (dbg) {          // diagnostic only: synchronises, prints the mean cycles per sequence of each phase for compute wave 0 and the memory wave
+    if constexpr (K >= 8) return kernel == IDL_VEC_SLICES ? (const void *)vectorise_slices_kernel<K> : nullptr;
+    else {
+        if constexpr (K == 4) {
+            if (kernel == IDL_VEC_V4) return rl == 4 ? v4_instance<K, 4>(om) : (rl == 2 ? v4_instance<K, 2>(om) : (rl == 0 ? v4_instance<K, 0>(om) : (rl == 3 ? v4_instance<K, 3>(om) : nullptr)));
+            if (kernel == IDL_VEC_V3) return rl == 5 ? v3_instance<K, 5>(diag) : (rl == 4 ? v3_instance<K, 4>(diag) : (rl == 3 ? v3_instance<K, 3>(diag) : nullptr));
+        } else if constexpr (K == 5 || K == 6) {
+            if (kernel == IDL_VEC_V4) return rl == 0 ? v4_instance<K, 0>(om || K == 6) : nullptr;
+            if (kernel == IDL_VEC_V3) return rl == 0 ? v3_instance<K, 0>(diag) : nullptr;
+        }
+        return kernel == IDL_VEC_V1 ? (const void *)vectorise_kernel<K>
+                                    : (kernel == IDL_VEC_V2_B16 ? (const void *)vectorise2_kernel<K, true> : (kernel == IDL_VEC_V2 ? (const void *)vectorise2_kernel<K, false> : nullptr));
+    }
+}
+
+const void *vec_instance(int k, int kernel, int rl = 0, bool om = false, bool diag = false)
+{
+    static const void *(*const by_k[IDL_MAX_K])(int, int, bool, bool) = {vec_instance_k<1>, vec_instance_k<2>, vec_instance_k<3>, vec_instance_k<4>, vec_instance_k<5>,
+                                                                         vec_instance_k<6>, vec_instance_k<7>, vec_instance_k<8>, vec_instance_k<9>};
+    return k >= 1 && k <= IDL_MAX_K ? by_k[k - 1](kernel, rl, om, diag) : nullptr;
+}
+
+// the plan of one call on the current device under the current IDELUCS_DEV; v1 / v2: finished by the runtime's occupancy answer
+int make_plan(const VecShape &s, VecPlan *p)
+{
+    if (s.k < 1 || s.k > IDL_MAX_K) { idl::set_error("k=%d outside 1..%d", s.k, IDL_MAX_K); return IDL_ERR_ARG; }
+    idl::DeviceInfo di;
+    const int rc = idl::device_info(&di);
+    if (rc != IDL_OK) return rc;
+    const VecDevice d{di.cus, di.lds_per_cu, di.max_dyn_lds};
+    *p = plan_vectorise(s, d, read_vec_knobs());
+    if (p->lds_bytes > d.max_dyn_lds) {
+        idl::set_error("k=%d needs %zu bytes of LDS per %s; device allows %d", s.k, (size_t)p->lds_bytes, p->kernel == IDL_VEC_SLICES ? "workgroup" : "wavefront", d.max_dyn_lds);
+        return IDL_ERR_ARG;
+    }
+    if (p->wg_per_cu == 0) {
+        const void *fn = vec_instance(s.k, p->kernel);
+        if (p->lds_bytes > 64 * 1024) IDL_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p->lds_bytes));
+        int per_cu = 0;
+        IDL_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, p->threads, (size_t)p->lds_bytes));
+        vec_plan_occupancy(*p, s, d, per_cu);
+    }
+    return IDL_OK;
+}
+
+int launch_plan(int k, VecArgs a, const VecPlan &p, hipStream_t st)
+{
+    if (getenv("IDELUCS_DEBUG")) { char line[256]; vec_plan_line(line, sizeof(line), k, p); fprintf(stderr, "%s\n", line); }
+    const void *fn = vec_instance(k, p.kernel, p.copies_log2, p.other_modes != 0, p.diag != 0);
+    if (fn == nullptr) { idl::set_error("k=%d: the plan names a kernel instance that is not built", k); return IDL_ERR_ARG; }
+    if (p.lds_bytes > 64 * 1024) IDL_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes));
+    a.sc_slots = p.sc_slots; a.v3_sc = p.v3_sc; a.ecap = p.ecap; a.lcap = p.lcap; a.chunk = p.chunk; a.ablate = p.ablate;
+    const int32_t *tab = nullptr;                  // k = 8, 9, canonical rows: the rank table
+    if (p.kernel == IDL_VEC_SLICES && a.mode == IDL_MODE_CANONICAL) {
+        tab = k == 8 ? slices_rank_table<8>() : slices_rank_table<9>();
+        if (tab == nullptr) { idl::set_error("k=%d: could not build the canonical rank table", k); return IDL_ERR_HIP; }
+    }
+    if (p.redo) {
+        a.redo_count = redo_counter(st);
+        if (a.redo_count == nullptr) { idl::set_error("cannot allocate the v3 hand-over word"); return IDL_ERR_HIP; }
+        IDL_HIP_TRY(hipMemsetAsync(a.redo_count, 0, 2 * sizeof(int), st));      // [0] sequences left to the second pass, [1] head of the sequence queue
+    }
+    const int64_t grid = p.grid;
+    if (p.diag) { IDL_HIP_TRY(hipMalloc((void **)&a.dbg, (size_t)grid * 20 * 8)); IDL_HIP_TRY(hipMemset(a.dbg, 0, (size_t)grid * 20 * 8)); }
+    void *args[] = {&a, &tab};                     // (the slice kernel alone takes the second)
+    IDL_HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3((unsigned)p.threads), args, (size_t)p.lds_bytes, st));
+    if (p.diag) {       // diagnostic only (v3): synchronises, prints the mean cycles per sequence of each phase for compute wave 0 and the memory wave
         std::vector<unsigned long long> h((size_t)grid * 20);
         IDL_HIP_TRY(hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost));
         (void)hipFree(a.dbg);
@@ -1562,235 +1616,27 @@ int launch_vectorise3_k(VecArgs &a, const idl::DeviceInfo &di, hipStream_t st, s
         for (int w = 0; w < 2; ++w) {
             fprintf(stderr, "[idl] v3 cycles per sequence, %s wave:", w ? "memory" : "compute");
             double tot = 0;
-            for (int k = 0; k < 8; ++k) { double sum = 0; for (int64_t b = 0; b < grid; ++b) sum += (double)h[(size_t)(b * 2 + w) * 10 + k]; fprintf(stderr, " %s %.0f", nm[k], sum / (double)a.n); tot += sum / (double)a.n; }
+            for (int ph = 0; ph < 8; ++ph) { double sum = 0; for (int64_t b = 0; b < grid; ++b) sum += (double)h[(size_t)(b * 2 + w) * 10 + ph]; fprintf(stderr, " %s %.0f", nm[ph], sum / (double)a.n); tot += sum / (double)a.n; }
             fprintf(stderr, " | total %.0f\n", tot);
         }
     }
-    // second pass: the v2 kernel on the sequences v3 left alone (their edits / pairs exceed the LDS tables); exits at once when there are none
-    {
+    if (p.redo) {       // second pass: v2 on the sequences the first left alone (their edits / pairs / slots exceed its LDS tables); exits at once when there are none
         VecArgs b = a;
-        b.redo = 1;
-        b.v3_sc = a.sc_slots;
-        b.sc_slots = 160;
-        const size_t lds2 = (size_t)((1 << (2 * K)) + 4 + (b.sc_slots + 1) * 6 + V2_EDIT_CAP + V2_LIST_CAP + 2 * V2_WAVES + 4 * b.n_views) * 4;
-        int64_t g2 = (int64_t)di.cus * 4;
-        if (g2 > a.n) g2 = a.n;
-        hipLaunchKernelGGL((vectorise2_kernel<K, false>), dim3((unsigned)g2), dim3(64 * V2_WAVES), lds2, st, b);
-        IDL_HIP_TRY(hipGetLastError());
+        b.redo = p.redo;
+        b.v3_sc = p.redo_v3_sc;
+        b.sc_slots = p.redo_sc_slots;
+        void *args2[] = {&b};
+        IDL_HIP_TRY(hipLaunchKernel(vec_instance(k, IDL_VEC_V2), dim3((unsigned)p.redo_grid), dim3(64 * V2_WAVES), args2, (size_t)p.redo_lds_bytes, st));
     }
     return IDL_OK;
 }
-
-// v3 takes the hot shape only: plain k-mer rows (float32 or int32), k = 4..6, <= 8 views, every sequence within one staged
-// super-chunk (the host's length bound says so), fresh histograms.  Everything else stays on v2 / v1.  k = 4 counts into 2^RL
-// copies of its 1 KB histogram (V3<K, RL>): RL = 5 is conflict-free and fits three workgroups per CU at 10 kbp, RL = 4 four.
-template <int K, int RL>
-int launch_vectorise3_rl(const VecArgs &a_in, const idl::DeviceInfo &di, hipStream_t st, bool *done)
-{
-    {
-        constexpr int HW = V3<K, RL>::HD;                          // histogram words (k = 4: the copies + the histogram proper)
-        VecArgs a = a_in;
-        int want = 3;
-        if (const char *e = idl::dev_env("vec")) want = atoi(e);
-        if (want != 3 || a.mode != IDL_MODE_KMER || a.init == IDL_INIT_FROM_OUT || a.out_kind == IDL_OUT_FREQ_F64 ||
-            a.n_views > V3_MAXV || a.max_len <= 0 || a.max_len > 64 * 2048 || a.n > 0x7F000000ll)
-            return IDL_OK;
-        a.sc_slots = (int)((a.max_len + 63) / 64);
-        // LDS tables for the edits of all views and their K windows each: at least 3.5 % of the bases + slack, and whatever else
-        // fits at four workgroups per CU (an edit costs 2 + K words: two staging sets and the list); IDELUCS_DEV=v3_ec / _LC override
-        int ec = (int)(a.max_len * 35 / 1000) + 64, lc;
-        {
-            const int fixed = HW + 2 * (a.sc_slots + 1) * 6 + 3 * V3_META + 2 * V3_VTAB + 16 + 4;
-            int wgs = 4;                                  // workgroups per CU the tables are sized for: four, or as many as the fixed part + the minimum leaves
-            while (wgs > 2 && ((di.lds_per_cu / wgs - 1024) / 4 - fixed) / (2 + K) < ec) --wgs;
-            const int fit = ((di.lds_per_cu / wgs - 1024) / 4 - fixed) / (2 + K);
-            if (fit > ec) ec = fit > 4096 ? 4096 : fit;
-        }
-        if (const char *e = idl::dev_env("v3_ec")) { const int t = atoi(e); if (t >= 0 && t <= 16384) ec = t; }
-        ec &= ~7;
-        lc = ec * K;
-        if (const char *e = idl::dev_env("v3_lc")) { const int t = atoi(e); if (t >= 0 && t <= 65536) lc = t; }
-        if (a.edits == nullptr) { ec = 0; lc = 0; }
-        a.ecap = ec; a.lcap = lc;
-        a.chunk = 2;
-        if (const char *e = idl::dev_env("v3_chunk")) { const int t = atoi(e); if (t >= 1 && t <= 4096) a.chunk = t; }
-        if (const char *e = idl::dev_env("vec_ablate")) a.ablate = atoi(e);
-        const size_t lds = (size_t)(HW + 2 * ((a.sc_slots + 1) * 6 + ec) + lc + 3 * V3_META + 2 * V3_VTAB + 16 + 4) * 4;
-        if ((int)lds > di.max_dyn_lds || lds > 80 * 1024) return IDL_OK;                 // (fewer than two workgroups per CU: v2's chunked staging is the better fit)
-        // workgroups per CU by LDS, with 1 KB of slack each (measured: five 32 032-byte workgroups do NOT become resident
-        // together although 5 x 32 032 < 160 KB and the occupancy query says 5 -- the fifth ran after the others)
-        int per_cu = (int)((size_t)di.lds_per_cu / (lds + 1024));
-        if (per_cu > 4) per_cu = 4;                   // 8 waves per workgroup, <= 64 registers: 32 waves per CU
-        if (const char *e = idl::dev_env("wg_per_cu")) { const int t = atoi(e); if (t >= 1 && t <= 32) per_cu = t; }
-        if (per_cu < 1) per_cu = 1;
-        if (getenv("IDELUCS_DEBUG"))
-            fprintf(stderr, "[idl] vectorise k=%d v3 lds=%zu B (histogram copies %d, staged slots %d, edits %d, pairs %d) -> %d workgroups/CU\n", K, lds, 1 << RL, a.sc_slots, ec, lc, per_cu);
-        const int rc = launch_vectorise3_k<K, RL>(a, di, st, lds, per_cu);
-        if (rc != IDL_OK) return rc;
-        *done = true;
-    }
-    return IDL_OK;
-}
-
-// v4 takes what v3 takes at k = 4 / 5 when every sequence fits its wave's slice of LDS (<= 12 288 bases); IDELUCS_DEV=vec=3 keeps v3 (the cross-check tests)
-template <int K, int RL>
-int launch_vectorise4(const VecArgs &a_in, const idl::DeviceInfo &di, hipStream_t st, bool *done)
-{
-    VecArgs a = a_in;
-    int want = 4;
-    if (const char *e = idl::dev_env("vec")) want = atoi(e);
-    const bool om = a.mode == IDL_MODE_CGR || a.mode == IDL_MODE_CANONICAL;
-    if (K == 6 && !om) return IDL_OK;                        // (plain rows at k = 6 are v3's: bound by the write stream there)
-    // (k = 6, CGR / canonical: 2.29 / 4.99 ms at 100 000 x 10 kbp x 4 views against v2's 3.05 / 7.53.  The collapse is latency-bound -- 4096 bins x 4 views a sequence walked by
-    //  one wave in 64 turns, twice --, not bank- or instruction-bound: summing the pairs in place in a skewed, conflict-free order (lane l of
-    //  turn t takes b = l | ((l + t) mod 64) << 6) and restoring them by a third walk was built and measured: 6.0 ms at k = 6, no change at k = 4 / 5; rc(b) from per-lane and per-turn
-    //  halves (no bit reversal in the loop) measured too: 5.1 ms -- a walk costs ~1.3 ms whatever its body: 64 dependent turns of LDS latency at two waves a SIMD)
-    if (want != 4 || (a.mode != IDL_MODE_KMER && !om) || a.init == IDL_INIT_FROM_OUT || a.out_kind == IDL_OUT_FREQ_F64 || a.n_views > V3_MAXV || a.max_len <= 0 ||
-        a.max_len > 64 * 64 * V4_SR || a.n > 0x7F000000ll)
-        return IDL_OK;
-    using W = V3<K, RL>;
-    a.v3_sc = (int)((a.max_len + 63) / 64);
-    a.sc_slots = a.v3_sc;
-    int ec = a.edits == nullptr ? 0 : (((int)(a.max_len * 35 / 1000) + 64) * a.n_views / 4 + 7) & ~7;      // edits of all views: 3.5 % of the bases + slack for four views, scaled
-    if (ec > 64 * V4_FR) ec = 64 * V4_FR;
-    if (const char *e = idl::dev_env("v3_ec")) { const int t = atoi(e); if (t >= 0 && t <= 64 * V4_FR) ec = t & ~7; }
-    a.ecap = ec; a.lcap = 0;
-    const int slice = (W::HC + (W::F + 4) + (a.v3_sc + 1) * 6 + ec + 3) & ~3;
-    // as many waves a workgroup as its CU's LDS holds slices (one workgroup per CU: nothing is shared between the waves but the CU)
-    int waves = (di.lds_per_cu - 2048) / (slice * 4);
-    if (waves > V4_MAX_WAVES) waves = V4_MAX_WAVES;
-    if (const char *e = idl::dev_env("v4_waves")) { const int t = atoi(e); if (t >= 1 && t <= waves) waves = t; }
-    if (waves < 4) return IDL_OK;                            // (long sequences: v3 / v2)
-    const size_t lds = (size_t)slice * 4 * waves;
-    if ((int)lds > di.max_dyn_lds) return IDL_OK;
-    const void *fn = (om || K == 6) ? (const void *)vectorise4_kernel<K, RL, true> : (const void *)vectorise4_kernel<K, RL, K == 6>;
-    if (lds > 64 * 1024) IDL_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int per_cu = 1, lc = 0;
-    int64_t grid = (int64_t)di.cus * per_cu;
-    if (grid * waves > a.n) grid = (a.n + waves - 1) / waves;
-    a.redo_count = redo_counter(st);
-    if (a.redo_count == nullptr) { idl::set_error("cannot allocate the v3 hand-over word"); return IDL_ERR_HIP; }
-    IDL_HIP_TRY(hipMemsetAsync(a.redo_count, 0, 2 * sizeof(int), st));
-    if (getenv("IDELUCS_DEBUG"))
-        fprintf(stderr, "[idl] vectorise k=%d v4 (a wave per sequence) lds=%zu B a workgroup of %d waves (copies %d, staged slots %d, edits %d, pairs %d) -> %d workgroups/CU\n",
-                K, lds, waves, 1 << RL, a.v3_sc, ec, lc, per_cu);
-    if (om || K == 6) hipLaunchKernelGGL((vectorise4_kernel<K, RL, true>), dim3((unsigned)grid), dim3(64 * waves), lds, st, a);
-    else hipLaunchKernelGGL((vectorise4_kernel<K, RL, K == 6>), dim3((unsigned)grid), dim3(64 * waves), lds, st, a);
-    IDL_HIP_TRY(hipGetLastError());
-    {       // second pass: v2 on the sequences v4 left alone; exits at once when there are none
-        VecArgs b = a;
-        b.redo = 2;
-        b.sc_slots = 160;
-        const size_t lds2 = (size_t)((1 << (2 * K)) + 4 + (b.sc_slots + 1) * 6 + V2_EDIT_CAP + V2_LIST_CAP + 2 * V2_WAVES + 4 * b.n_views) * 4;
-        int64_t g2 = (int64_t)di.cus * 4;
-        if (g2 > a.n) g2 = a.n;
-        hipLaunchKernelGGL((vectorise2_kernel<K, false>), dim3((unsigned)g2), dim3(64 * V2_WAVES), lds2, st, b);
-        IDL_HIP_TRY(hipGetLastError());
-    }
-    *done = true;
-    return IDL_OK;
-}
-
-template <int K>
-int launch_vectorise3(const VecArgs &a_in, const idl::DeviceInfo &di, hipStream_t st, bool *done)
-{
-    *done = false;
-    if constexpr (K == 4 || K == 5 || K == 6) {
-        int rc;
-        if constexpr (K == 4) {
-            // copies of the histogram a wave counts into: 4 -- measured at 100 000 x 10 kbp, 4 views, one box (gpurun_out r06): no edits / philox edits
-            // 0.351 / 0.649 ms with 4, 0.349 / 0.738 with 8, 0.453 / 1.025 with 16 (fewer waves fit); v3 on the same box: 0.621 / 0.725
-            int rl = 2;
-            if (const char *e = idl::dev_env("v4_copies")) { const int t = atoi(e); rl = t == 16 ? 4 : (t == 8 ? 3 : (t == 1 ? 0 : 2)); }
-            rc = rl == 4 ? launch_vectorise4<K, 4>(a_in, di, st, done) : (rl == 2 ? launch_vectorise4<K, 2>(a_in, di, st, done) :
-                 (rl == 0 ? launch_vectorise4<K, 0>(a_in, di, st, done) : launch_vectorise4<K, 3>(a_in, di, st, done)));
-        } else rc = launch_vectorise4<K, 0>(a_in, di, st, done);
-        if (rc != IDL_OK || *done) return rc;
-    }
-    if constexpr (K == 4) {
-        // copies of the histogram the count goes to: 16 by default -- measured at 100 000 x 10 kbp, 4 views (gpurun_out/r05_e): 0.708 ms
-        // with 16 (four workgroups per CU), 0.714 with 8, 0.844 with 32 (conflict-free, but 41 KB of LDS: three per CU); v2: 1.393
-        int rl = 4;
-        if (const char *e = idl::dev_env("v3_copies")) { const int t = atoi(e); rl = t == 32 ? 5 : (t == 8 ? 3 : 4); }
-        if (rl == 5) return launch_vectorise3_rl<K, 5>(a_in, di, st, done);
-        if (rl == 4) return launch_vectorise3_rl<K, 4>(a_in, di, st, done);
-        return launch_vectorise3_rl<K, 3>(a_in, di, st, done);
-    } else if constexpr (K >= 5 && K <= 6) {
-        // (k = 5 with the count in 4 / 8 copies was measured too, gpurun_out/r05_s: 0.904 / 1.139 ms against 0.804 without -- folding
-        //  1024 bins x copies costs more than the conflicts it saves; bit-identical rows)
-        return launch_vectorise3_rl<K, 0>(a_in, di, st, done);
-    }
-    return IDL_OK;
-}
-
-template <int K>
-int launch_vectorise(const VecArgs &a_in, const idl::DeviceInfo &di, hipStream_t st)
-{
-    constexpr int F = 1 << (2 * K);
-    {
-        bool done = false;
-        const int rc = launch_vectorise3<K>(a_in, di, st, &done);
-        if (rc != IDL_OK || done) return rc;
-    }
-    VecArgs a = a_in;
-    bool v1 = (a.init == IDL_INIT_FROM_OUT);            // accumulate-on-top needs a per-view start: single-pass kernel
-    if (const char *e = idl::dev_env("vec")) { if (atoi(e) == 1) v1 = true; }   // force the v1 kernel (cross-check tests)
-    int sc = 160;                                       // 10240 bases staged at a time (cfg2's 10 kbp in one super-chunk)
-    if (const char *e = idl::dev_env("sc_slots")) { const int t = atoi(e); if (t >= 1 && t <= 4096) sc = t; }
-    a.sc_slots = sc;
-    if (const char *e = idl::dev_env("vec_ablate")) a.ablate = atoi(e);
-    // 16-bit bins are possible while no count can reach 65536 (count <= max_len + 1).  Measured on MI355X (cfg2): 8
-    // workgroups/CU with 16-bit bins (64 VGPRs, 80 B/lane of spill) run 2.16 ms, 6 workgroups/CU with 32-bit bins
-    // (79 VGPRs) 1.98 ms -- so 32-bit is the default and 16-bit an opt-in experiment (IDELUCS_DEV=bins=16).
-    bool b16 = false;
-    if (const char *e = idl::dev_env("bins")) b16 = atoi(e) == 16 && !v1 && a.max_len > 0 && a.max_len <= 65000;
-    const int hd = b16 ? (F / 2 + 4) & ~3 : F + 4;
-    const size_t lds = v1 ? (size_t)(F + STAGE_DWORDS) * 4
-                          : (size_t)(hd + (sc + 1) * 6 + V2_EDIT_CAP + V2_LIST_CAP + 2 * V2_WAVES + 4 * a.n_views) * 4;
-    if ((int)lds > di.max_dyn_lds) {
-        idl::set_error("k=%d needs %zu bytes of LDS per wavefront; device allows %d", K, lds, di.max_dyn_lds);
-        return IDL_ERR_ARG;
-    }
-    const void *fn = v1 ? (const void *)vectorise_kernel<K>
-                        : (b16 ? (const void *)vectorise2_kernel<K, true> : (const void *)vectorise2_kernel<K, false>);
-    if (lds > 64 * 1024) IDL_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int per_cu = 0;
-    IDL_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, v1 ? 64 : 64 * V2_WAVES, lds));
-    if (const char *e = idl::dev_env("wg_per_cu")) { const int t = atoi(e); if (t >= 1 && t <= 32) per_cu = t; }
-    if (per_cu > 16) per_cu = 16;
-    if (per_cu < 1) per_cu = 1;
-    if (getenv("IDELUCS_DEBUG"))
-        fprintf(stderr, "[idl] vectorise k=%d %s lds=%zu B -> %d workgroups/CU\n", K, v1 ? "v1" : (b16 ? "v2/16-bit bins" : "v2/32-bit bins"), lds, per_cu);
-    int64_t grid = (int64_t)di.cus * per_cu;
-    if (grid > a.n) grid = a.n;
-    if (v1) hipLaunchKernelGGL(vectorise_kernel<K>, dim3((unsigned)grid), dim3(64), lds, st, a);
-    else if (b16) hipLaunchKernelGGL((vectorise2_kernel<K, true>), dim3((unsigned)grid), dim3(64 * V2_WAVES), lds, st, a);
-    else hipLaunchKernelGGL((vectorise2_kernel<K, false>), dim3((unsigned)grid), dim3(64 * V2_WAVES), lds, st, a);
-    IDL_HIP_TRY(hipGetLastError());
-    return IDL_OK;
-}
-
-#include "vectorise_slices.h"   // k = 8, 9: the histogram exceeds one CU's LDS
-#include "vectorise_pairs.h"    // a training batch's rows straight from the packed bases (idl_vectorise_pairs_at)
 
 int dispatch_vectorise(int k, const VecArgs &a, hipStream_t st)
 {
-    idl::DeviceInfo di;
-    int rc = idl::device_info(&di);
-    if (rc != IDL_OK) return rc;
-    switch (k) {
-    case 1: return launch_vectorise<1>(a, di, st);
-    case 2: return launch_vectorise<2>(a, di, st);
-    case 3: return launch_vectorise<3>(a, di, st);
-    case 4: return launch_vectorise<4>(a, di, st);
-    case 5: return launch_vectorise<5>(a, di, st);
-    case 6: return launch_vectorise<6>(a, di, st);
-    case 7: return launch_vectorise<7>(a, di, st);
-    case 8: return launch_vectorise_slices<8>(a, di, st);
-    case 9: return launch_vectorise_slices<9>(a, di, st);
-    }
-    idl::set_error("k=%d outside 1..%d", k, IDL_MAX_K);
-    return IDL_ERR_ARG;
+    const VecShape s{k, a.mode, a.init, a.out_kind, a.n_views, a.edits != nullptr, a.n, a.max_len};
+    VecPlan p;
+    const int rc = make_plan(s, &p);
+    return rc != IDL_OK ? rc : launch_plan(k, a, p, st);
 }
 
 struct DevBuf {  // RAII for the scalar host-pointer entry points
@@ -1914,10 +1760,8 @@ int idl_mask_from_lengths(void *mask, const int64_t *slot_off, const int64_t *le
     return IDL_OK;
 }
 
-static int vectorise_impl(const void *codes, const void *mask, const int64_t *slot_off, const int64_t *lengths,
-                  int64_t n, int k, int mode, int init, int out_kind,
-                  int n_views, const uint32_t *edits, const int64_t *edit_off, int eo_shift,
-                  void *out, int64_t view_stride, int64_t max_len, void *stream)
+// what idl_vectorise and idl_vectorise_plan accept
+static int vectorise_shape_ok(int64_t n, int k, int mode, int init, int out_kind, int n_views)
 {
     IDL_REQUIRE(k >= 1 && k <= IDL_MAX_K, "k outside 1..IDL_MAX_K");
     IDL_REQUIRE(n >= 0 && n_views >= 1 && n_views <= 64, "n < 0 or n_views outside 1..64");
@@ -1927,6 +1771,26 @@ static int vectorise_impl(const void *codes, const void *mask, const int64_t *sl
                 "unknown out_kind");
     IDL_REQUIRE(!(init == IDL_INIT_FROM_OUT && (out_kind != IDL_OUT_COUNTS_I32 || mode == IDL_MODE_CANONICAL)),
                 "IDL_INIT_FROM_OUT needs IDL_OUT_COUNTS_I32 and a non-canonical mode");
+    return IDL_OK;
+}
+
+int idl_vectorise_plan(int k, int mode, int init, int out_kind, int n_views, int has_edits, int64_t n, int64_t max_len, idl_vectorise_plan_t *out)
+{
+    IDL_REQUIRE(out != nullptr, "NULL plan");
+    const int ok = vectorise_shape_ok(n, k, mode, init, out_kind, n_views);
+    if (ok != IDL_OK) return ok;
+    *out = idl_vectorise_plan_t{};
+    if (n == 0) return IDL_OK;
+    return make_plan(VecShape{k, mode, init, out_kind, n_views, has_edits != 0, n, max_len}, out);
+}
+
+static int vectorise_impl(const void *codes, const void *mask, const int64_t *slot_off, const int64_t *lengths,
+                  int64_t n, int k, int mode, int init, int out_kind,
+                  int n_views, const uint32_t *edits, const int64_t *edit_off, int eo_shift,
+                  void *out, int64_t view_stride, int64_t max_len, void *stream)
+{
+    const int ok = vectorise_shape_ok(n, k, mode, init, out_kind, n_views);
+    if (ok != IDL_OK) return ok;
     IDL_REQUIRE((edits == nullptr) == (edit_off == nullptr), "edits and edit_off must both be given or both NULL");
     IDL_REQUIRE(view_stride >= n * idl_row_len(mode, k) || n_views == 1, "view_stride smaller than one view");
     if (n == 0) return IDL_OK;

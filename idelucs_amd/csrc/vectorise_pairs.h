@@ -66,7 +66,7 @@ __device__ __forceinline__ float4 standardise4(const PairArgs &p, float4 v, int6
 constexpr int VP_SC = 160;      // slots staged at a time (10 240 bases, as the whole-store v2 launch)
 
 template <int K>
-constexpr int vp_lds_words() { return V2<K, false>::HD + (VP_SC + 1) * 6 + V2_EDIT_CAP + V2_LIST_CAP + 2 * V2_WAVES; }
+constexpr int vp_lds_words() { return v2_lds_words(K, false, VP_SC, 0); }     // v2's layout without the views' edit ranges
 
 // second launch-bound argument = waves per SIMD wanted: four workgroups a CU (a batch of 512 pairs puts two on each), which leaves the
 // float64 standardisation of the epilogue its registers (six, as vectorise2_kernel asks for, spilled 44 bytes a lane at k = 6)

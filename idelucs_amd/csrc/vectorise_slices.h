@@ -16,12 +16,7 @@
 // is h / 2 (a palindrome: h); the output position of bin b is rank_tab[b / 64] (canonical k-mers below that group, a table built
 // once per k on the host) plus a ballot prefix.
 
-constexpr int SL_BITS = 14;                 // log2 of the bins of a slice
-constexpr int SL_BINS = 1 << SL_BITS;       // 64 KiB of uint32 bins
-constexpr int SL_NT = 512;                  // threads of a workgroup (8 wavefronts)
-constexpr int SL_SC = 320;                  // slots (64 bases) staged at a time: 20 480 bases, 7.5 KiB
-constexpr int SL_LDS_WORDS = SL_BINS + (SL_SC + 1) * 6 + 2 * (SL_NT / 64);
-constexpr int SL_WG_PER_CU = 2;             // residency the launcher assumes: 2 x 73 KiB of the CU's 160 KiB
+// (SL_BITS, SL_BINS, SL_NT, SL_SC, SL_LDS_WORDS, SL_WG_PER_CU: vectorise_layout.h)
 
 // even bits of x packed into the low half (inverse of spread_bits, for up to 16 pairs)
 __device__ __forceinline__ uint32_t squeeze_bits(uint32_t x)
@@ -288,29 +283,4 @@ const int32_t *slices_rank_table()
         p = nullptr;
     }
     return p;
-}
-
-template <int K>
-int launch_vectorise_slices(const VecArgs &a, const idl::DeviceInfo &di, hipStream_t st)
-{
-    const size_t lds = (size_t)SL_LDS_WORDS * 4;
-    if ((int)lds > di.max_dyn_lds) {
-        idl::set_error("k=%d needs %zu bytes of LDS per workgroup; device allows %d", K, lds, di.max_dyn_lds);
-        return IDL_ERR_ARG;
-    }
-    const int32_t *tab = nullptr;
-    if (a.mode == IDL_MODE_CANONICAL) {
-        tab = slices_rank_table<K>();
-        if (tab == nullptr) { idl::set_error("k=%d: could not build the canonical rank table", K); return IDL_ERR_HIP; }
-    }
-    const void *fn = (const void *)vectorise_slices_kernel<K>;
-    IDL_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int64_t grid = (int64_t)di.cus * SL_WG_PER_CU;
-    const int64_t items = a.n * a.n_views;
-    if (grid > items) grid = items;
-    if (getenv("IDELUCS_DEBUG"))
-        fprintf(stderr, "[idl] vectorise k=%d slices lds=%zu B, %lld workgroups\n", K, lds, (long long)grid);
-    hipLaunchKernelGGL(vectorise_slices_kernel<K>, dim3((unsigned)grid), dim3(SL_NT), lds, st, a, tab);
-    IDL_HIP_TRY(hipGetLastError());
-    return IDL_OK;
 }

@@ -384,6 +384,14 @@ def _vectorise(dev_in, k, mode, init, out_kind, n_views=1, edits=None, edit_off=
     return out
 
 
+def _vectorise_plan(dev_in, k, mode, init, out_kind, n_views=1, edits=None):
+    """What _vectorise would launch for these arguments now (current device, current IDELUCS_DEV), without launching: _lib.idl_vectorise_plan_t."""
+    plan = _lib.idl_vectorise_plan_t()
+    _lib.check(_L.idl_vectorise_plan(k, mode, init, out_kind, n_views, int(edits is not None), dev_in.n, int(getattr(dev_in, "max_len", 0) or 0),
+                                     ctypes.byref(plan)))
+    return plan
+
+
 def _compat_edits(ff, transforms):
     """Host-RNG mimic sites for every (view, record), in the reference's consumption order
     (pass-major, records in file order; survey D.2).  `transforms[v]` is None or a callable that

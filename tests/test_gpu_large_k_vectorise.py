@@ -85,6 +85,10 @@ def test_every_mode_init_and_out_kind_vs_oracle(gpu, k):
     for i, s in enumerate(seqs):
         O.kmer_counts(s, k, km0[i]); O.cgr(s, k, cg0[i])
     assert km0.max() > 65535 and km0[:, 0].max() > 65535 and km0[:, F - 1].max() > 65535
+    for mode, init, kind in ((_lib.MODE_KMER, _lib.INIT_ONE, _lib.OUT_FREQ_F32), (_lib.MODE_CGR, _lib.INIT_FROM_OUT, _lib.OUT_COUNTS_I32),
+                             (_lib.MODE_CANONICAL, _lib.INIT_ZERO, _lib.OUT_FREQ_F64)):
+        plan = U._vectorise_plan(din, k, mode, init, kind)          # the kernel under test is the one that runs
+        assert plan.kernel == _lib.VEC_SLICES and plan.redo == 0 and plan.lds_bytes == _lib.lib.idl_vectorise_slices_lds(), (k, mode, plan.kernel)
     with np.errstate(invalid="ignore", divide="ignore"):
         for mode, base in ((_lib.MODE_KMER, km0), (_lib.MODE_CGR, cg0)):
             for init, iv in ((_lib.INIT_ZERO, 0), (_lib.INIT_ONE, 1)):
@@ -130,6 +134,7 @@ def test_three_mbp_record_with_edits(gpu, k):
     F = 4 ** k
     want = np.zeros((2, F), np.int32)
     O.kmer_counts(s, k, want[0]); O.kmer_counts(mut, k, want[1])
+    assert U._vectorise_plan(din, k, _lib.MODE_KMER, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, 2, d_e).kernel == _lib.VEC_SLICES
     got = U._vectorise(din, k, _lib.MODE_KMER, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, 2, d_e, d_eo).cpu().numpy()
     assert np.array_equal(got[:, 0], want)
     cg = np.zeros(F, np.int32); O.cgr(mut, k, cg)

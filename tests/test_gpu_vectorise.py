@@ -17,6 +17,21 @@ pytestmark = pytest.mark.gpu
 KAT = json.load(open(os.path.join(GOLDEN, "kat.json")))
 
 
+def _routed(din, args, kernel, copies=None, second=None, **fields):
+    """The plan of U._vectorise(din, *args) under the present IDELUCS_DEV: the kernel (and histogram copies, second pass, plan fields) a cross-check
+    means to run is the one that runs -- a launcher that declined would leave the test comparing a kernel with itself."""
+    from idelucs_amd import _lib, utils as U
+    k, mode, init, out_kind = args[:4]
+    plan = U._vectorise_plan(din, k, mode, init, out_kind, args[4] if len(args) > 4 else 1, args[5] if len(args) > 5 else None)
+    ctx = (args[:5], os.environ.get("IDELUCS_DEV"), plan.kernel, plan.copies_log2, plan.redo)
+    assert plan.kernel == getattr(_lib, "VEC_" + kernel), ctx
+    assert copies is None or 1 << plan.copies_log2 == copies, ctx
+    assert second is None or (plan.redo != 0) == second, ctx
+    for name, value in fields.items():
+        assert getattr(plan, name) == value, (name, getattr(plan, name), ctx)
+    return plan
+
+
 @pytest.fixture(scope="module")
 def gpu():
     import torch
@@ -150,6 +165,9 @@ def test_random_batches_with_edits_vs_oracle(gpu, monkeypatch, sc_slots, bins):
         dev_env(monkeypatch, sc_slots=sc_slots)
     if bins is not None:
         dev_env(monkeypatch, bins=bins)          # opt-in 16-bit LDS bins (default: 32-bit)
+    if sc_slots is not None or bins is not None:
+        dev_env(monkeypatch, vec="2")            # both are v2's knobs: without this k = 4 and 6 go to v4 / v3, which read neither
+    v2 = None if sc_slots is None and bins is None else ("V2_B16" if bins == "16" else "V2")
     from idelucs_amd import _lib, utils as U
     rng = np.random.default_rng(2024)
     seqs = _random_batch(rng, 40, 0, 300) + _random_batch(rng, 12, 3900, 4300) + _random_batch(rng, 6, 8000, 13000, 0.0) \
@@ -172,11 +190,14 @@ def test_random_batches_with_edits_vs_oracle(gpu, monkeypatch, sc_slots, bins):
     d_e = torch.from_numpy(e_all.view(np.int32)).to(dev); d_eo = torch.from_numpy(edit_off).to(dev)
     for k in (3, 4, 6, 7):
         for mode, fn in ((_lib.MODE_KMER, O.kmer_counts), (_lib.MODE_CGR, O.cgr)):
+            if v2 is not None:
+                _routed(din, (k, mode, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, P, d_e), v2, second=False, sc_slots=int(sc_slots or 160))
             got = U._vectorise(din, k, mode, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, P, d_e, d_eo).cpu().numpy()
             for v in range(P):
                 for i in range(n):
                     want = np.zeros(4 ** k, np.int32); fn(mutated[v][i], k, want)
                     assert np.array_equal(got[v, i], want), (k, mode, v, i, len(seqs[i]))
+        _routed(din, (k, _lib.MODE_CANONICAL, _lib.INIT_ONE, _lib.OUT_FREQ_F64, P, d_e), v2 or "V2", second=False)      # (float64 rows are v2's at every k)
         got = U._vectorise(din, k, _lib.MODE_CANONICAL, _lib.INIT_ONE, _lib.OUT_FREQ_F64, P, d_e, d_eo).cpu().numpy()
         for v in (0, 3):
             for i in range(0, n, 7):
@@ -407,6 +428,11 @@ def test_cgr_and_canonical_rows_of_the_wave_per_sequence_kernel_are_v2s(gpu, mon
         outs = {}
         for which in ("2", "4"):
             dev_env(monkeypatch, vec=which)
+            for args in ((k, mode, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 4, edits), (k, mode, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, 4, edits), (k, mode, _lib.INIT_ONE, _lib.OUT_FREQ_F32)):
+                if which == "4":
+                    _routed(din, args, "V4", copies=4 if k == 4 else 1, second=True, other_modes=1)
+                else:
+                    _routed(din, args, "V2", second=False)
             outs[which] = (U._vectorise(din, k, mode, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 4, edits, edit_off).clone(),
                            U._vectorise(din, k, mode, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, 4, edits, edit_off).clone(),
                            U._vectorise(din, k, mode, _lib.INIT_ONE, _lib.OUT_FREQ_F32).clone())
@@ -415,6 +441,7 @@ def test_cgr_and_canonical_rows_of_the_wave_per_sequence_kernel_are_v2s(gpu, mon
         assert outs["4"][0].shape[-1] == int(_lib.lib.idl_row_len(mode, k))
         assert float(outs["4"][0][1:].sum(-1).sub(1).abs().max()) < 1e-5 and not torch.equal(outs["4"][0][0], outs["4"][0][1])
         dev_env(monkeypatch, vec="4"); dev_env(monkeypatch, v3_ec="320")
+        _routed(din, (k, mode, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 4, edits), "V4", second=True, other_modes=1, ecap=320)
         assert torch.equal(U._vectorise(din, k, mode, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 4, edits, edit_off), outs["2"][0]), (mode, k)
         dev_env(monkeypatch, v3_ec=None)
 
@@ -436,8 +463,17 @@ def test_full_size_v1_v2_v3_kernels_agree_bitwise(gpu, monkeypatch, k):
     specs = [t.spec() for t in U.mimic_transforms(3)]
     edits, edit_off = U._philox_edits(din, specs, 11)
     outs = {}
+    f32, i32 = (k, _lib.MODE_KMER, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 4, edits), (k, _lib.MODE_KMER, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, 4, edits)
     for which in ("4", "3", "2", "1"):                        # (4: round 6's wave-per-sequence kernel, the default at k = 4 / 5; it does not take k = 6: v3 runs)
-        dev_env(monkeypatch, vec=which)
+        # (k = 6: vec=4 keeps v3 out as well -- v2 ran, and "4" compared v2 with v2; the default route is what runs v3 behind a declining v4)
+        dev_env(monkeypatch, vec=None if (which == "4" and k == 6) else which)
+        for args in (f32, i32):
+            if which == "4" and k != 6:
+                _routed(din, args, "V4", copies=4 if k == 4 else 1, second=True, other_modes=0)
+            elif which in ("4", "3"):
+                _routed(din, args, "V3", copies=16 if k == 4 else 1, second=True)
+            else:
+                _routed(din, args, "V" + which, second=False)
         outs[which] = (U._vectorise(din, k, _lib.MODE_KMER, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 4, edits, edit_off).clone(),
                        U._vectorise(din, k, _lib.MODE_KMER, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, 4, edits, edit_off).clone())
     assert torch.equal(outs["1"][1], outs["2"][1]) and torch.equal(outs["1"][1], outs["3"][1]) and torch.equal(outs["1"][1], outs["4"][1])
@@ -445,16 +481,19 @@ def test_full_size_v1_v2_v3_kernels_agree_bitwise(gpu, monkeypatch, k):
     if k in (4, 5):     # ... also when its tables take only some of the sequences (the rest: the second pass on v2), and with other numbers of histogram copies
         for ec, lc in (("0", "0"), ("320", "1800")):
             dev_env(monkeypatch, vec="4"); dev_env(monkeypatch, v3_ec=ec); dev_env(monkeypatch, v3_lc=lc)
+            _routed(din, f32, "V4", second=True, ecap=int(ec))
             assert torch.equal(U._vectorise(din, k, _lib.MODE_KMER, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 4, edits, edit_off), outs["1"][0]), (ec, lc)
         dev_env(monkeypatch, v3_ec=None); dev_env(monkeypatch, v3_lc=None)
         if k == 4:
             for copies in ("16", "8", "1"):
                 dev_env(monkeypatch, vec="4"); dev_env(monkeypatch, v4_copies=copies)
+                _routed(din, i32, "V4", copies=int(copies), second=True)
                 assert torch.equal(U._vectorise(din, k, _lib.MODE_KMER, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, 4, edits, edit_off), outs["1"][1]), copies
             dev_env(monkeypatch, v4_copies=None)
     if k == 4:      # round 5: the count goes to 16 copies of the 4^4-bin histogram (lane l adds to copy l mod 16); 32 and 8 copies: the same rows
         for copies in ("32", "8"):
             dev_env(monkeypatch, vec="3"); dev_env(monkeypatch, v3_copies=copies)
+            _routed(din, f32, "V3", copies=int(copies), second=True); _routed(din, i32, "V3", copies=int(copies), second=True)
             assert torch.equal(U._vectorise(din, k, _lib.MODE_KMER, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 4, edits, edit_off), outs["1"][0]), copies
             assert torch.equal(U._vectorise(din, k, _lib.MODE_KMER, _lib.INIT_ZERO, _lib.OUT_COUNTS_I32, 4, edits, edit_off), outs["1"][1]), copies
         dev_env(monkeypatch, v3_copies=None)
@@ -462,6 +501,7 @@ def test_full_size_v1_v2_v3_kernels_agree_bitwise(gpu, monkeypatch, k):
     # (tables for no / half / nearly all of the sequences: the second pass scans, or walks the short list v3 left it)
     for ec, lc in (("0", "0"), ("320", "1800"), ("512", "1920"), ("448", "2304")):
         dev_env(monkeypatch, vec="3"); dev_env(monkeypatch, v3_ec=ec); dev_env(monkeypatch, v3_lc=lc)
+        _routed(din, f32, "V3", second=True, ecap=int(ec), lcap=int(lc))
         assert torch.equal(U._vectorise(din, k, _lib.MODE_KMER, _lib.INIT_ONE, _lib.OUT_FREQ_F32, 4, edits, edit_off), outs["1"][0]), (ec, lc)
     dev_env(monkeypatch, v3_ec=None); dev_env(monkeypatch, v3_lc=None)
     c = outs["2"][1]
@@ -623,6 +663,7 @@ def test_variant_n_synthetic_input_vs_oracle(gpu, monkeypatch):
     outs = {}
     for ver in ("1", "2", "3"):
         dev_env(monkeypatch, vec=ver)
+        _routed(din, (k, _lib.MODE_KMER, _lib.INIT_ONE, _lib.OUT_FREQ_F32, P, edits), "V" + ver, second=ver == "3")
         outs[ver] = U._vectorise(din, k, _lib.MODE_KMER, _lib.INIT_ONE, _lib.OUT_FREQ_F32, P, edits, edit_off)
     assert torch.equal(outs["1"], outs["2"]) and torch.equal(outs["1"], outs["3"])
     assert torch.allclose(outs["3"].double().sum(2), torch.ones((P, n), dtype=torch.float64, device=dev), atol=1e-6)
@@ -772,3 +813,58 @@ def test_mask_from_lengths_is_the_packers_padding(gpu):
             assert np.all(got[a:b] == 0x5A)
         else:
             assert np.array_equal(got[a:b], want[a:b]), (i, len(seqs[i]))
+
+
+def test_every_kernel_instance_of_the_launch_plan_vs_v1(gpu, monkeypatch):
+    """The launcher's switch from plan to template instance, instance by instance: cases of tests/vectorise_routes_parent.jsonl (the grid
+    tests/test_vectorise_plan.py replays on a CPU), the first one routed to each distinct (kernel, k, histogram copies, CGR / canonical instance), run on 64
+    sequences of 1, 63, 64, 65 and ~300 bases with four views (device-drawn edits where the case has edits) -- bit for bit the rows of the single-pass
+    kernel v1 under the same knobs; a case v1 takes itself (IDL_INIT_FROM_OUT, vec=1) against v2, k = 8 / 9 (no v1) against their own rows under vec=2.
+    (v3's DIAG instances, a timing build that synchronises and prints, are not in the grid.)"""
+    import torch
+    from idelucs_amd import _lib, utils as U
+    rng = np.random.default_rng(77)
+    seqs = []
+    for L in [1, 63, 64, 65] * 12 + list(range(290, 306)):
+        seqs += _random_batch(rng, 1, L, L)
+    dev = torch.device("cuda")
+    din = U._DeviceInput(_pack_batch(seqs), dev)
+    n, P, true_max = len(seqs), 4, din.max_len
+    assert n == 64 and sorted(set(int(x) for x in din.lengths.cpu()))[:4] == [1, 63, 64, 65]
+    edits, edit_off = U._philox_edits(din, [t.spec() for t in U.mimic_transforms(P - 1)], 5)
+    dtype = {_lib.OUT_COUNTS_I32: torch.int32, _lib.OUT_FREQ_F32: torch.float32, _lib.OUT_FREQ_F64: torch.float64}
+
+    def run(c, init, **knobs):
+        monkeypatch.setenv("IDELUCS_DEV", c["dev"])
+        dev_env(monkeypatch, **knobs)
+        e = (edits, edit_off) if c["has_edits"] else (None, None)
+        plan = U._vectorise_plan(din, c["k"], c["mode"], init, c["out_kind"], P, e[0])
+        out = torch.zeros((P, n, int(_lib.lib.idl_row_len(c["mode"], c["k"]))), dtype=dtype[c["out_kind"]], device=dev)
+        return plan, U._vectorise(din, c["k"], c["mode"], init, c["out_kind"], P, e[0], e[1], out=out)
+
+    picked = {}
+    for line in open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "vectorise_routes_parent.jsonl")):
+        c = json.loads(line)
+        if c["line"] is None:
+            continue
+        din.max_len = 0 if c["max_len"] == 0 else max(c["max_len"], true_max)      # the case's bound, where it bounds these sequences
+        monkeypatch.setenv("IDELUCS_DEV", c["dev"])
+        p = U._vectorise_plan(din, c["k"], c["mode"], c["init"], c["out_kind"], P, edits if c["has_edits"] else None)
+        picked.setdefault((p.kernel, c["k"], p.copies_log2, p.other_modes), (c, din.max_len))
+    want = {(kn, k, 0, 0) for kn in (_lib.VEC_V1, _lib.VEC_V2, _lib.VEC_V2_B16) for k in range(1, 8)} | {(_lib.VEC_SLICES, 8, 0, 0), (_lib.VEC_SLICES, 9, 0, 0)}
+    want |= {(_lib.VEC_V3, 4, rl, 0) for rl in (3, 4, 5)} | {(_lib.VEC_V3, 5, 0, 0), (_lib.VEC_V3, 6, 0, 0)}
+    want |= {(_lib.VEC_V4, 4, rl, om) for rl in (0, 2, 3, 4) for om in (0, 1)} | {(_lib.VEC_V4, 5, 0, 0), (_lib.VEC_V4, 5, 0, 1), (_lib.VEC_V4, 6, 0, 1)}
+    assert set(picked) == want, (want - set(picked), set(picked) - want)
+    for key, (c, max_len) in sorted(picked.items()):
+        din.max_len = max_len
+        plan, got = run(c, c["init"])
+        assert (plan.kernel, c["k"], plan.copies_log2, plan.other_modes) == key and (plan.redo != 0) == (plan.kernel in (_lib.VEC_V3, _lib.VEC_V4)), (key, c)
+        # the reference rows: v1; for a case that is v1's already: v2 (accumulating on the zeros `out` starts from = IDL_INIT_ZERO)
+        ref_init = _lib.INIT_ZERO if c["init"] == _lib.INIT_FROM_OUT else c["init"]
+        ref_vec = "2" if plan.kernel in (_lib.VEC_V1, _lib.VEC_SLICES) else "1"
+        ref_plan, ref = run(c, ref_init, vec=ref_vec)
+        assert ref_plan.kernel == {"1": _lib.VEC_V1, "2": _lib.VEC_V2}[ref_vec] or (c["k"] >= 8 and ref_plan.kernel == _lib.VEC_SLICES) \
+            or (ref_vec == "2" and ref_plan.kernel == _lib.VEC_V2_B16), (key, c, ref_plan.kernel)
+        bits = {torch.float64: torch.int64, torch.float32: torch.int32, torch.int32: torch.int32}[got.dtype]      # (bit for bit: 0 / 0 of a row without windows is a NaN in both)
+        assert torch.equal(got.view(bits), ref.view(bits)), (key, c)
+        assert int(got.ne(0).sum()) > 0, (key, c)
