@@ -1,6 +1,7 @@
 // mid_fwd_device.h -- the stages of the NetLinear step's forward middle (bias, ReLU + Dropout of layer 1, lat = r1 W2^T + b2 on fp32 MFMA over 16 K-slices,
 // normalise, ReLU + Dropout of the latent, logits on MFMA, row softmax), each defined once for the kernels of train_step.hip that run them: mid_fwd_body (a
-// 16-row tile from a1 in place), sums_fwd_kernel (8 rows straight from layer 1's partial sums) and the unfused pair relu_dropout_fwd_kernel / head_row.  The
+// 16-row tile from a1 in place), sums_fwd_kernel (8 rows straight from layer 1's partial sums) and the unfused pair relu_dropout_fwd_kernel / head_row -- and
+// for predict.hip's predict_mid_kernel, the eval forward (train = 0) that leaves the raw latent and the row's largest z instead of f / inv / r2.  The
 // tests hold those kernels to each other bit for bit; here is what makes that hold.  What differs between them -- where a lane's eight values come from, where
 // r1 goes, which rows of the tile are valid, the LDS layouts -- is written out in each body.
 // Operands travel by value, or by references that inlining dissolves, and the loads only load: a body can issue every global read before its first dependent
@@ -140,7 +141,8 @@ __device__ __forceinline__ RowLogits load_logits(const float *lgrow, int lane, i
     }
     return lg;
 }
-__device__ __forceinline__ void softmax_row(RowLogits lg, int row, int lane, int C, bool valid, float *z)      // z[row][.] is written if `valid`
+struct RowSoftmax { RowLogits e; float den; };      // e.v[t] = exp(logit - the row's largest) of class 64 t + lane < C; den = their sum over the row
+__device__ __forceinline__ RowSoftmax softmax_terms(RowLogits lg, int lane, int C)
 {
     float mx = -INFINITY;
 #pragma unroll
@@ -152,14 +154,46 @@ __device__ __forceinline__ void softmax_row(RowLogits lg, int row, int lane, int
         const int c = t * 64 + lane;
         if (c < C) { lg.v[t] = __expf(lg.v[t] - mx); den += lg.v[t]; }
     }
-    den = idl_dev::wave_sum_f(den);
+    return RowSoftmax{lg, idl_dev::wave_sum_f(den)};
+}
+__device__ __forceinline__ void softmax_row(RowLogits lg, int row, int lane, int C, bool valid, float *z)      // z[row][.] is written if `valid`
+{
+    const RowSoftmax s = softmax_terms(lg, lane, C);
     if (valid) {
 #pragma unroll
         for (int t = 0; t < MAX_CPL; ++t) {
             const int c = t * 64 + lane;
-            if (c < C) z[(int64_t)row * C + c] = lg.v[t] / den;
+            if (c < C) z[(int64_t)row * C + c] = s.e.v[t] / s.den;
         }
     }
+}
+// ... of the eval forward (predict.hip): the same z (written where z != NULL), prob[row] = the row's largest z and unit[row] = the lowest class that attains
+// it (torch.max's choice among equal values; a row whose logits are not numbers leaves prob = -1, unit = C - 1)
+__device__ __forceinline__ void softmax_row_top(RowLogits lg, int row, int lane, int C, float *z, float *prob, int32_t *unit)
+{
+    const RowSoftmax s = softmax_terms(lg, lane, C);
+    float zt[MAX_CPL], best = -1.f;
+#pragma unroll
+    for (int t = 0; t < MAX_CPL; ++t) {
+        zt[t] = -1.f;
+        if (t * 64 + lane < C) { zt[t] = s.e.v[t] / s.den; best = fmaxf(best, zt[t]); }
+    }
+    best = idl_dev::wave_max_f(best);
+    uint64_t first = (uint64_t)(C - 1);
+#pragma unroll
+    for (int t = MAX_CPL - 1; t >= 0; --t) {
+        const int c = t * 64 + lane;
+        if (c < C && zt[t] == best) first = (uint64_t)c;
+    }
+    first = idl_dev::wave_min_u64(first);
+    if (z != nullptr) {
+#pragma unroll
+        for (int t = 0; t < MAX_CPL; ++t) {
+            const int c = t * 64 + lane;
+            if (c < C) z[(int64_t)row * C + c] = zt[t];
+        }
+    }
+    if (lane == 0) { prob[row] = best; unit[row] = (int32_t)first; }
 }
 
 }  // namespace mid_dev

@@ -264,16 +264,28 @@ class FittedEnsemble:
             nets.append(net.to(dev).eval())
         return nets
 
-    def voter_outputs(self, sequence_file, device=None, chunk_rows=None):
+    def _predict_mode(self, predict):
+        """predict=None or 'torch': the voters run as nn.Modules; 'native': through predict_native.NativeLinearPredictor -- linear models
+        of the shapes IID_model._predict_mode accepts; anything else raises ValueError."""
+        from .models import IID_model
+        return IID_model._predict_mode({'predict': predict, 'model_size': self.model_size, 'k': self.k, 'n_clusters': self.n_units})
+
+    def voter_outputs(self, sequence_file, device=None, chunk_rows=None, predict=None):
         """The saved voters' eval forward on a file's rows, standardised with the TRAINING file's statistics, a chunk at a time (there is
         no [M, F] matrix) -> (names, units int64 [V, M] on the device: every voter's argmax, latent float32 [M, 64] on the device: the
-        last voter's)."""
+        last voter's).  predict: the mode the run predicted with ('native': a row's outputs are the training run's bit for bit whatever
+        chunk_rows is, and no library product is involved)."""
+        native = self._predict_mode(predict) == 'native'
         _lib.require_gpu()
         dev = utils._device(device)
-        from . import gemm_tuning
-        gemm_tuning.maybe_enable(0)                 # the products run on the solutions a training run's predict runs on (nothing is tuned)
+        if not native:
+            from . import gemm_tuning
+            gemm_tuning.maybe_enable(0)             # the products run on the solutions a training run's predict runs on (nothing is tuned)
         stats = (self.mean.to(dev), self.scale.to(dev))
         nets = self._networks(dev)
+        if native:
+            from .predict_native import NativeLinearPredictor
+            predictors = [NativeLinearPredictor(net) for net in nets]
         din, ff = _open_input(sequence_file, dev)
         try:
             m = din.n
@@ -282,21 +294,26 @@ class FittedEnsemble:
             with torch.no_grad():
                 for lo, hi, x in utils.feature_chunks_of_input(din, self.k, self.reduce, None, chunk_rows, stats=stats):
                     for v, net in enumerate(nets):
-                        out, lat = net(x)
-                        units[v, lo:hi] = torch.max(out, 1)[1]             # (as IID_model.predict)
+                        if native:
+                            lat, _, unit, _ = predictors[v].forward(x)
+                            units[v, lo:hi] = unit
+                        else:
+                            out, lat = net(x)
+                            units[v, lo:hi] = torch.max(out, 1)[1]         # (as IID_model.predict)
                     latent[lo:hi] = lat
             torch.cuda.current_stream().synchronize()                      # (the reader's arenas are reused by the next file)
         finally:
             ff.close()
         return ff.names, units, latent
 
-    def assign(self, sequence_file, device=None):
+    def assign(self, sequence_file, device=None, predict=None):
         """The sequences of a file -> (names, y_pred int64 [M], confidence float64 [M]) in the clusters of the training run.
         mode 'ensemble': every voter's argmax through its unit map (a unit that never won on the training file: no vote), then
         votes_to_clusters -- confidence 1.0 where the record sits on its centre (the reference's inf / inf is NaN there).
         mode 'fine': labels[nn], prob[nn] * min(1, spacing[nn] / dist) with nn the nearest training latent (dist == 0: the factor is 1),
-        so a sequence of the training file gets its training label and probability."""
-        names, units, latent = self.voter_outputs(sequence_file, device)
+        so a sequence of the training file gets its training label and probability.
+        predict: as voter_outputs -- assign with the mode the run predicted with."""
+        names, units, latent = self.voter_outputs(sequence_file, device, predict=predict)
         dev = units.device
         if self.mode == "ensemble":
             maps = self.unit_maps.to(dev).long()

@@ -128,6 +128,26 @@ class IID_model():
         # where the training rows live: 'resident' (the [views, N, F] store in HBM) or 'streamed' (utils.StreamedFeatureStore: every batch vectorised
         # from the packed bases when it is needed; no N x F buffer in the run, predict included)
         self._streamed_store = self._store_mode(args) == 'streamed'
+        # the eval forward of predict / calculate_probs / predict_latent_shard: self.net (hipBLASLt), or, opt-in, this package's own launches
+        self._native_predict = self._predict_mode(args) == 'native'
+        self._predictor = None
+
+    @staticmethod
+    def _predict_mode(args):
+        """args['predict']: 'torch' (absent or None) or 'native' (model_size='linear', 4 <= k <= 9, n_clusters in 1..256: the shapes
+        idl_l1_fwd and idl_predict_mid take); anything else raises ValueError.  Independent of optimizer, store mode, step form and scheduler."""
+        mode = args.get('predict') or 'torch'
+        if mode not in ('torch', 'native'):
+            raise ValueError(f"predict must be 'torch' or 'native', not {mode!r}")
+        if mode == 'torch':
+            return mode
+        if args['model_size'] != 'linear':
+            raise ValueError(f"predict='native' runs NetLinear's eval forward only (model_size='linear', got {args['model_size']!r})")
+        if not 4 <= args['k'] <= _lib.MAX_K:
+            raise ValueError(f"predict='native' supports 4 <= k <= {_lib.MAX_K} (got k={args['k']}): layer 1's tiles take rows of 4^k >= 192 entries")
+        if not 1 <= args['n_clusters'] <= 256:
+            raise ValueError(f"predict='native' supports n_clusters in 1..256 (got n_clusters={args['n_clusters']})")
+        return mode
 
     @staticmethod
     def _store_mode(args):
@@ -392,47 +412,63 @@ class IID_model():
             return True
         return self.store is not None and self.store.n * self.n_features * 4 > PREDICT_CACHE_BYTES
 
-    def _predict_outputs_streamed(self, rows):
-        outs, lats = [], []
+    def _forward_of(self, want_z):
+        """The eval forward of one chunk of rows -> a tuple of per-row tensors: (outputs, latent) through self.net (predict='torch'), or
+        (latent, prob, unit, z or None) from the native predictor (predict='native': predict_native.NativeLinearPredictor, built at first use)."""
+        if not self._native_predict:
+            return self.net
+        if self._predictor is None:
+            from .predict_native import NativeLinearPredictor
+            self._predictor = NativeLinearPredictor(self.net)
+        return lambda x: self._predictor.forward(x, want_z)
+
+    def _predict_outputs_streamed(self, rows, want_z=True):
+        outs = []
+        forward = self._forward_of(want_z)
         with torch.no_grad():
             self.net.eval()
             # the forward runs on the generator's whole buffer, every row where it stands in the chunk grid of the file: each chunk is the
             # same product shape and a row's place in it does not depend on `rows`, so a row shard has the bits of those rows in a full predict
+            # (predict='native': a row's outputs depend on nothing else, so only the rows asked for are run)
             if self._streamed_store and self.store is not None:     # the packed bases are on the device already: predict_feature_chunks' passes on them
                 chunks = utils.feature_chunks_of_input(self.store.din, self.k, self.reduce, rows, self.predict_chunk_rows, padded=True)
             else:
                 chunks = utils.predict_feature_chunks(self.sequence_file, k=self.k, reduce=self.reduce, device=self.device, rows=rows,
                                                       chunk_rows=self.predict_chunk_rows, padded=True)
             for lo, hi, x, at in chunks:
-                o, l = self.net(x)
-                outs.append(o[at:at + hi - lo])
-                lats.append(l[at:at + hi - lo])
+                if self._native_predict:
+                    outs.append(forward(x[at:at + hi - lo]))
+                else:
+                    outs.append(tuple(t[at:at + hi - lo] for t in forward(x)))
             if not outs:
-                o, l = self.net(torch.zeros((1, self.n_features), dtype=torch.float32, device=self.device))
-                return o[:0], l[:0]
-        return torch.cat(outs), torch.cat(lats)
+                return tuple(t if t is None else t[:0] for t in forward(torch.zeros((1, self.n_features), dtype=torch.float32, device=self.device)))
+        return tuple(None if col[0] is None else torch.cat(col) for col in zip(*outs))
 
-    def _predict_outputs(self, rows=None):
+    def _predict_outputs(self, rows=None, want_z=True):
+        """predict='torch': (outputs, latent); predict='native': (latent, prob, unit, z -- None unless want_z)."""
         if self._predict_streams():
-            return self._predict_outputs_streamed(rows)
+            return self._predict_outputs_streamed(rows, want_z)
         feats = self._predict_inputs(rows)
-        outs, lats = [], []
+        outs = []
+        forward = self._forward_of(want_z)
         with torch.no_grad():
             self.net.eval()
             # (the reference walks predict in batch_sz rows, models.py:158-170; every op of the eval forward is row-wise, so the chunk
             #  only sets the launch count: 32768 rows per chunk, 3.08 ms per 100 000 rows against 3.32 at 8192 and ~10 at 512)
             chunk = max(int(self.batch_sz), 32768)
             for i in range(0, feats.shape[0], chunk):
-                o, l = self.net(feats[i:i + chunk])
-                outs.append(o)
-                lats.append(l)
-        return torch.cat(outs), torch.cat(lats)
+                outs.append(tuple(forward(feats[i:i + chunk])))
+        return tuple(None if col[0] is None else torch.cat(col) for col in zip(*outs))
 
     def predict(self, data=None):
         """Reference models.py:145-172 -> (int64 y_pred[N], float64 probs[N], float64 latent[N,64])."""
-        outputs, latent = self._predict_outputs()
-        self._check_planes()
-        probs, predicted = torch.max(outputs, 1)
+        if self._native_predict:            # the kernel's own largest z and its lowest class: torch.max's choice
+            latent, probs, predicted, _ = self._predict_outputs(want_z=False)
+            self._check_planes()
+        else:
+            outputs, latent = self._predict_outputs()
+            self._check_planes()
+            probs, predicted = torch.max(outputs, 1)
         return (predicted.cpu().numpy().astype(np.int64), probs.double().cpu().numpy(),
                 latent.double().cpu().numpy())
 
@@ -441,9 +477,11 @@ class IID_model():
         predict is sharded by sequence and the shards are all-gathered, idelucs_amd.dist.all_gather_rows)."""
         if hi <= lo:
             return torch.empty((0, 64), dtype=torch.float32, device=self.device)
+        if self._native_predict:
+            return self._predict_outputs(rows=(lo, hi), want_z=False)[0].contiguous()
         return self._predict_outputs(rows=(lo, hi))[1].float().contiguous()
 
     def calculate_probs(self, data=None):
         """Reference models.py:175-195 -> float64 [N, n_clusters] softmax outputs."""
-        outputs, _ = self._predict_outputs()
+        outputs = self._predict_outputs()[3 if self._native_predict else 0]
         return outputs.double().cpu().numpy()
