@@ -433,9 +433,19 @@ __device__ __forceinline__ void rms_momentum(float g, float &p, float &v, float 
     p = p - h[0] * buf;                               // param.add_(buf, alpha=-lr)
 }
 
-// (MOM: the momentum form, buf = the tensor's momentum_buffer; the momentum-free instantiation is the code it was before the template)
-template <bool MOM>
-__device__ __forceinline__ void grad_tile(const GradJob &j, int t, int m, const float *hyper, float *lds, float *buf)
+// The four kernels of this launch (RMSprop, RMSprop with momentum, SGD, Adam) differ in the update of one element and in nothing else.
+// What they share is written once, below: grad_tile_sum (operand loads, product loop, cross-wave reduction, C/D index map),
+// bias_cols_sum (the bias column sums) and loss_or_gather (step loss, step counter, next batch).  The per-element update is a callable
+// epi(e, g), called once per owned element e with its summed gradient g, behind the optional grad[e] = g store.
+// What stays in each __global__ function: its __shared__ array, its by-value struct parameters and the role dispatch (the two unrolled
+// loops over a.g[t] / a.b[t]).  A shared body that takes SmallWgArgs by reference and holds the dispatch was tried: the argument block
+// is then copied to scratch (the RMSprop kernels: 124 VGPRs and 616 / 680 bytes of scratch a lane, against 118 and 0 as written here).
+// The epilogue callables capture POINTERS BY VALUE (W, v, buf, st1, st2, hyper, copied into locals inside the role's branch first; the
+// Coef may be captured by reference): one that reads j.W through a captured GradJob & makes the compiler load the kernel argument again
+// for every element (31 more scalar loads and 32 more waits a kernel).  loss_or_gather's after() runs once in one thread and may read
+// the kernel's struct parameter directly.
+template <class Epi>
+__device__ __forceinline__ void grad_tile_sum(const GradJob &j, int t, int m, float *lds, Epi epi)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l = lane & 15, q = lane >> 4;
     const int i0 = (t / j.tiles_n) * WG_TM, j0 = (t % j.tiles_n) * WG_TN;
@@ -498,21 +508,13 @@ __device__ __forceinline__ void grad_tile(const GradJob &j, int t, int m, const 
                 if (i < j.M && jj < j.N) {
                     const int64_t e = (int64_t)i * j.N + jj;
                     if (j.grad != nullptr) j.grad[e] = g;
-                    float p = j.W[e], v = j.v[e];
-                    if constexpr (MOM) {
-                        float bu = buf[e];
-                        rms_momentum(g, p, v, bu, hyper);
-                        buf[e] = bu;
-                    } else {
-                        rms(g, p, v, hyper);
-                    }
-                    j.W[e] = p; j.v[e] = v;
+                    epi(e, g);
                 }
             }
 }
 
-template <bool MOM>
-__device__ __forceinline__ void bias_cols(const BiasJob &j, int t, int m, const float *hyper, float *lds, float *buf)
+template <class Epi>
+__device__ __forceinline__ void bias_cols_sum(const BiasJob &j, int t, int m, float *lds, Epi epi)
 {
     const int tid = threadIdx.x, c = tid & (BIAS_COLS - 1), rg = tid / BIAS_COLS;       // 8 row groups
     const int col = t * BIAS_COLS + c;
@@ -526,15 +528,62 @@ __device__ __forceinline__ void bias_cols(const BiasJob &j, int t, int m, const 
     float g = red[0][c];
     for (int w = 1; w < WG_THREADS / BIAS_COLS; ++w) g += red[w][c];
     if (j.grad != nullptr) j.grad[col] = g;
-    float p = j.b[col], v = j.v[col];
+    epi(col, g);
+}
+
+// The update of element e of one tensor: parameter and state loads, the update, the stores in the order W then v (RMSprop), states then
+// parameter (SGD / Adam).  (MOM: the momentum form, buf = the tensor's momentum_buffer.)
+template <bool MOM, class I>
+__device__ __forceinline__ void rms_at(float *P, float *V, float *buf, I e, float g, const float *hyper)
+{
+    float p = P[e], v = V[e];
     if constexpr (MOM) {
-        float bu = buf[col];
+        float bu = buf[e];
         rms_momentum(g, p, v, bu, hyper);
-        buf[col] = bu;
+        buf[e] = bu;
     } else {
         rms(g, p, v, hyper);
     }
-    j.b[col] = p; j.v[col] = v;
+    P[e] = p; V[e] = v;
+}
+
+// opt_update<KIND> of opt_update_device.h (KIND 1: SGD with momentum and weight decay, 2: Adam) on (g, p, state1, state2)
+template <int KIND, class I>
+__device__ __forceinline__ void opt_at(float *P, float *st1, float *st2, I e, float g, const idl_dev::Coef<KIND> &c)
+{
+    float p = P[e], a = st1[e], b = 0.f;
+    if constexpr (KIND == idl_dev::KIND_ADAM) b = st2[e];
+    idl_dev::opt_update<KIND>(g, p, a, b, c);
+    st1[e] = a;
+    if constexpr (KIND == idl_dev::KIND_ADAM) st2[e] = b;
+    P[e] = p;
+}
+
+// The blocks behind the bias columns: the step loss and ctl[0] += 1 in one wave of one workgroup, then the gather rider.  after() runs
+// in the ONE thread that advances ctl[0].
+template <class After>
+__device__ __forceinline__ void loss_or_gather(const SmallWgArgs &a, int bid, After after)
+{
+    if (bid == a.loss_blk) {
+        if (threadIdx.x >= 64) return;
+        const int lane = threadIdx.x;
+        float s = 0.f;
+        if (a.loss_rows != nullptr)
+            for (int r = lane; r < a.m; r += 64) s += a.loss_rows[r];
+        s = idl_dev::wave_sum_f(s);
+        if (lane == 0) {
+            if (a.loss_rows != nullptr) {
+                const float nce = s / (float)a.m;
+                const float tot = a.w_nce * nce + a.w_iic * a.out[3];
+                a.out[2] = nce; a.out[0] = tot; a.out[1] += tot;
+            }
+            a.ctl[0] += 1;
+            after();
+        }
+        return;
+    }
+    const int blk = 2 * (bid - a.loss_blk - 1) + (int)(threadIdx.x >> 8);
+    if (blk < a.gather_end) idl_dev::gather_block(a.gth, (int64_t)blk, (int)(threadIdx.x & 255));
 }
 
 struct MomBufs { float *g[4], *b[4]; };               // momentum_buffer of the four weights / the four biases
@@ -546,37 +595,28 @@ __global__ __launch_bounds__(WG_THREADS) void small_wgrad_rms_kernel(SmallWgArgs
     int lo = 0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        if (bid < a.g_end[t]) { grad_tile<false>(a.g[t], bid - lo, a.m, a.hyper, lds, nullptr); return; }
+        if (bid < a.g_end[t]) {
+            float *const W = a.g[t].W, *const v = a.g[t].v;
+            const float *const hyper = a.hyper;
+            grad_tile_sum(a.g[t], bid - lo, a.m, lds, [=](int64_t e, float g) { rms_at<false>(W, v, (float *)nullptr, e, g, hyper); });
+            return;
+        }
         lo = a.g_end[t];
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        if (bid < a.b_end[t]) { bias_cols<false>(a.b[t], bid - lo, a.m, a.hyper, lds, nullptr); return; }
+        if (bid < a.b_end[t]) {
+            float *const b = a.b[t].b, *const v = a.b[t].v;
+            const float *const hyper = a.hyper;
+            bias_cols_sum(a.b[t], bid - lo, a.m, lds, [=](int col, float g) { rms_at<false>(b, v, (float *)nullptr, col, g, hyper); });
+            return;
+        }
         lo = a.b_end[t];
     }
-    if (bid == a.loss_blk) {
-        if (threadIdx.x >= 64) return;
-        const int lane = threadIdx.x;
-        float s = 0.f;
-        if (a.loss_rows != nullptr)
-            for (int r = lane; r < a.m; r += 64) s += a.loss_rows[r];
-        s = idl_dev::wave_sum_f(s);
-        if (lane == 0) {
-            if (a.loss_rows != nullptr) {
-                const float nce = s / (float)a.m;
-                const float tot = a.w_nce * nce + a.w_iic * a.out[3];
-                a.out[2] = nce; a.out[0] = tot; a.out[1] += tot;
-            }
-            a.ctl[0] += 1;
-        }
-        return;
-    }
-    const int blk = 2 * (bid - a.loss_blk - 1) + (int)(threadIdx.x >> 8);
-    if (blk < a.gather_end) idl_dev::gather_block(a.gth, (int64_t)blk, (int)(threadIdx.x & 255));
+    loss_or_gather(a, bid, [] {});
 }
 
-// The momentum form of the launch above: the same grid and roles, one more stream (momentum_buffer) per tensor.  (A kernel of its own,
-// not a shared body taking the arguments by reference: that copies the argument block to scratch.)
+// The momentum form of the launch above: the same grid and roles, one more stream (momentum_buffer) per tensor.
 __global__ __launch_bounds__(WG_THREADS) void small_wgrad_momentum_kernel(SmallWgArgs a, MomBufs mb)
 {
     __shared__ float lds[(WG_WAVES - 1) * WG_RB * WG_CB * 256];
@@ -584,43 +624,33 @@ __global__ __launch_bounds__(WG_THREADS) void small_wgrad_momentum_kernel(SmallW
     int lo = 0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        if (bid < a.g_end[t]) { grad_tile<true>(a.g[t], bid - lo, a.m, a.hyper, lds, mb.g[t]); return; }
+        if (bid < a.g_end[t]) {
+            float *const W = a.g[t].W, *const v = a.g[t].v, *const buf = mb.g[t];
+            const float *const hyper = a.hyper;
+            grad_tile_sum(a.g[t], bid - lo, a.m, lds, [=](int64_t e, float g) { rms_at<true>(W, v, buf, e, g, hyper); });
+            return;
+        }
         lo = a.g_end[t];
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        if (bid < a.b_end[t]) { bias_cols<true>(a.b[t], bid - lo, a.m, a.hyper, lds, mb.b[t]); return; }
+        if (bid < a.b_end[t]) {
+            float *const b = a.b[t].b, *const v = a.b[t].v, *const buf = mb.b[t];
+            const float *const hyper = a.hyper;
+            bias_cols_sum(a.b[t], bid - lo, a.m, lds, [=](int col, float g) { rms_at<true>(b, v, buf, col, g, hyper); });
+            return;
+        }
         lo = a.b_end[t];
     }
-    if (bid == a.loss_blk) {
-        if (threadIdx.x >= 64) return;
-        const int lane = threadIdx.x;
-        float s = 0.f;
-        if (a.loss_rows != nullptr)
-            for (int r = lane; r < a.m; r += 64) s += a.loss_rows[r];
-        s = idl_dev::wave_sum_f(s);
-        if (lane == 0) {
-            if (a.loss_rows != nullptr) {
-                const float nce = s / (float)a.m;
-                const float tot = a.w_nce * nce + a.w_iic * a.out[3];
-                a.out[2] = nce; a.out[0] = tot; a.out[1] += tot;
-            }
-            a.ctl[0] += 1;
-        }
-        return;
-    }
-    const int blk = 2 * (bid - a.loss_blk - 1) + (int)(threadIdx.x >> 8);
-    if (blk < a.gather_end) idl_dev::gather_block(a.gth, (int64_t)blk, (int)(threadIdx.x & 255));
+    loss_or_gather(a, bid, [] {});
 }
 
 // ---------------------------------------------------------------- the last launch with torch's SGD or Adam (models.py:89-92)
-// small_wgrad_opt_kernel<KIND>: the grid, roles and block order of small_wgrad_rms_kernel; the epilogue is opt_update<KIND> of
-// opt_update_device.h (KIND 1: SGD with momentum and weight decay, 2: Adam) on (g, p, state1, state2), its coefficients from a DEVICE
-// double[5] (make_coef: Adam's bias corrections in double).  Adam's step count is the optimizer's own, not ctl[0] (the dropout counter, which
-// restarts with every voter): every workgroup that updates reads *step_in, and the ONE thread that advances ctl[0] writes *step_in + 1 to
-// *step_out, a different word -- no word read in this launch is written in it (not all workgroups are resident before the first one ends).
-// (grad_tile_opt / bias_cols_opt are grad_tile / bias_cols with that epilogue: siblings, because the two RMSprop kernels' code is pinned
-//  as it is and moves with any change to the templates they instantiate -- a fix to the product loop is made in both.)
+// small_wgrad_opt_kernel<KIND>: the grid, roles and block order of small_wgrad_rms_kernel; the epilogue is opt_at<KIND>, its coefficients
+// from a DEVICE double[5] (make_coef: Adam's bias corrections in double).  Adam's step count is the optimizer's own, not ctl[0] (the
+// dropout counter, which restarts with every voter): every workgroup that updates reads *step_in, and the ONE thread that advances ctl[0]
+// writes *step_in + 1 to *step_out, a different word -- no word read in this launch is written in it (not all workgroups are resident
+// before the first one ends).
 struct OptBufs {
     float *g1[4], *b1[4];             // SGD: momentum_buffer, Adam: exp_avg, of the four weights / the four biases
     float *g2[4], *b2[4];             // Adam: exp_avg_sq
@@ -629,104 +659,8 @@ struct OptBufs {
     int64_t *step_out;
 };
 
-template <int KIND>
-__device__ __forceinline__ void grad_tile_opt(const GradJob &j, int t, int m, const idl_dev::Coef<KIND> &c, float *lds, float *st1, float *st2)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l = lane & 15, q = lane >> 4;
-    const int i0 = (t / j.tiles_n) * WG_TM, j0 = (t % j.tiles_n) * WG_TN;
-    const int ks = (m + 3) / 4, s0 = wv * ks / WG_WAVES, s1 = (wv + 1) * ks / WG_WAVES;
-    int ia[WG_RB], jb[WG_CB];
-#pragma unroll
-    for (int rb = 0; rb < WG_RB; ++rb) ia[rb] = min(i0 + 16 * rb + l, j.M - 1);
-#pragma unroll
-    for (int cb = 0; cb < WG_CB; ++cb) jb[cb] = min(j0 + 16 * cb + l, j.N - 1);
-    f32x4_t acc[WG_RB][WG_CB];
-#pragma unroll
-    for (int rb = 0; rb < WG_RB; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < WG_CB; ++cb) acc[rb][cb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    // (the product loop of grad_tile: clamped rows, a step past this wave's share contributes zero through A)
-    constexpr int U = 8;
-    for (int s = s0; s < s1; s += U) {
-        float av[U][WG_RB], bv[U][WG_CB];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = 4 * (s + u) + q;
-            const bool ok = s + u < s1 && k < m;
-            const int kr = min(k, m - 1);
-#pragma unroll
-            for (int rb = 0; rb < WG_RB; ++rb) {
-                const float t = j.dy[(int64_t)kr * j.M + ia[rb]];
-                av[u][rb] = ok ? t : 0.f;
-            }
-#pragma unroll
-            for (int cb = 0; cb < WG_CB; ++cb) bv[u][cb] = j.xin[(int64_t)kr * j.N + jb[cb]];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int rb = 0; rb < WG_RB; ++rb)
-#pragma unroll
-                for (int cb = 0; cb < WG_CB; ++cb) acc[rb][cb] = mfma(av[u][rb], bv[u][cb], acc[rb][cb]);
-    }
-    float (*red)[WG_RB * WG_CB][4][64] = (float (*)[WG_RB * WG_CB][4][64])lds;
-    if (wv > 0) {
-#pragma unroll
-        for (int rb = 0; rb < WG_RB; ++rb)
-#pragma unroll
-            for (int cb = 0; cb < WG_CB; ++cb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) red[wv - 1][rb * WG_CB + cb][r][lane] = acc[rb][cb][r];
-    }
-    __syncthreads();
-    if (wv != 0) return;
-#pragma unroll
-    for (int rb = 0; rb < WG_RB; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < WG_CB; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float g = acc[rb][cb][r];
-                for (int w = 0; w < WG_WAVES - 1; ++w) g += red[w][rb * WG_CB + cb][r][lane];
-                const int i = i0 + 16 * rb + 4 * q + r, jj = j0 + 16 * cb + l;       // C/D: row 4q + r, column l
-                if (i < j.M && jj < j.N) {
-                    const int64_t e = (int64_t)i * j.N + jj;
-                    if (j.grad != nullptr) j.grad[e] = g;
-                    float p = j.W[e], a = st1[e], b = 0.f;
-                    if constexpr (KIND == idl_dev::KIND_ADAM) b = st2[e];
-                    idl_dev::opt_update<KIND>(g, p, a, b, c);
-                    st1[e] = a;
-                    if constexpr (KIND == idl_dev::KIND_ADAM) st2[e] = b;
-                    j.W[e] = p;
-                }
-            }
-}
-
-template <int KIND>
-__device__ __forceinline__ void bias_cols_opt(const BiasJob &j, int t, int m, const idl_dev::Coef<KIND> &c, float *lds, float *st1, float *st2)
-{
-    const int tid = threadIdx.x, cc = tid & (BIAS_COLS - 1), rg = tid / BIAS_COLS;      // 8 row groups
-    const int col = t * BIAS_COLS + cc;
-    const int ccol = min(col, j.N - 1);
-    float s = 0.f;
-    for (int r = rg; r < m; r += WG_THREADS / BIAS_COLS) s += j.dy[(int64_t)r * j.N + ccol];
-    float (*red)[BIAS_COLS] = (float (*)[BIAS_COLS])lds;
-    red[rg][cc] = s;
-    __syncthreads();
-    if (rg != 0 || col >= j.N) return;
-    float g = red[0][cc];
-    for (int w = 1; w < WG_THREADS / BIAS_COLS; ++w) g += red[w][cc];
-    if (j.grad != nullptr) j.grad[col] = g;
-    float p = j.b[col], a = st1[col], b = 0.f;
-    if constexpr (KIND == idl_dev::KIND_ADAM) b = st2[col];
-    idl_dev::opt_update<KIND>(g, p, a, b, c);
-    st1[col] = a;
-    if constexpr (KIND == idl_dev::KIND_ADAM) st2[col] = b;
-    j.b[col] = p;
-}
-
-// (A kernel of its own for the reason small_wgrad_momentum_kernel is one.  a.hyper, RMSprop's float hyperparameters, is not read here;
-//  GradJob::v / BiasJob::v, RMSprop's running averages, are not either: the states come in ob.)
+// (a.hyper, RMSprop's float hyperparameters, is not read here; GradJob::v / BiasJob::v, RMSprop's running averages, are not either: the
+//  states come in ob.)
 template <int KIND>
 __global__ __launch_bounds__(WG_THREADS) void small_wgrad_opt_kernel(SmallWgArgs a, OptBufs ob)
 {
@@ -737,35 +671,24 @@ __global__ __launch_bounds__(WG_THREADS) void small_wgrad_opt_kernel(SmallWgArgs
         int lo = 0;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            if (bid < a.g_end[t]) { grad_tile_opt<KIND>(a.g[t], bid - lo, a.m, c, lds, ob.g1[t], ob.g2[t]); return; }
+            if (bid < a.g_end[t]) {
+                float *const W = a.g[t].W, *const st1 = ob.g1[t], *const st2 = ob.g2[t];
+                grad_tile_sum(a.g[t], bid - lo, a.m, lds, [=, &c](int64_t e, float g) { opt_at<KIND>(W, st1, st2, e, g, c); });
+                return;
+            }
             lo = a.g_end[t];
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            if (bid < a.b_end[t]) { bias_cols_opt<KIND>(a.b[t], bid - lo, a.m, c, lds, ob.b1[t], ob.b2[t]); return; }
+            if (bid < a.b_end[t]) {
+                float *const b = a.b[t].b, *const st1 = ob.b1[t], *const st2 = ob.b2[t];
+                bias_cols_sum(a.b[t], bid - lo, a.m, lds, [=, &c](int col, float g) { opt_at<KIND>(b, st1, st2, col, g, c); });
+                return;
+            }
             lo = a.b_end[t];
         }
     }
-    if (bid == a.loss_blk) {
-        if (threadIdx.x >= 64) return;
-        const int lane = threadIdx.x;
-        float s = 0.f;
-        if (a.loss_rows != nullptr)
-            for (int r = lane; r < a.m; r += 64) s += a.loss_rows[r];
-        s = idl_dev::wave_sum_f(s);
-        if (lane == 0) {
-            if (a.loss_rows != nullptr) {
-                const float nce = s / (float)a.m;
-                const float tot = a.w_nce * nce + a.w_iic * a.out[3];
-                a.out[2] = nce; a.out[0] = tot; a.out[1] += tot;
-            }
-            a.ctl[0] += 1;
-            *ob.step_out = *ob.step_in + 1;
-        }
-        return;
-    }
-    const int blk = 2 * (bid - a.loss_blk - 1) + (int)(threadIdx.x >> 8);
-    if (blk < a.gather_end) idl_dev::gather_block(a.gth, (int64_t)blk, (int)(threadIdx.x & 255));
+    loss_or_gather(a, bid, [&ob] { *ob.step_out = *ob.step_in + 1; });
 }
 
 // ---------------------------------------------------------------- the two dropout masks of a step (tests)

@@ -22,28 +22,30 @@ from ._lib import lib as _L
 from .fused import STEPS_PER_GRAPH, _LinearStepParts, _launch, _mm_now, _p, _stream
 
 KIND_SGD, KIND_ADAM, KIND_RMSPROP = 1, 2, 3
+_OPTIMIZERS = ((KIND_SGD, "SGD"), (KIND_ADAM, "Adam"), (KIND_RMSPROP, "RMSprop"))      # a kind and its class in torch.optim
 
 
-class FusedLinearOptTrainer(_LinearStepParts):
-    def __init__(self, net, optimizer, weight, lamb, seed=0):
-        """optimizer: the torch.optim.SGD / torch.optim.Adam / torch.optim.RMSprop object whose first group holds the hyperparameters (its state is not used)."""
-        if isinstance(optimizer, torch.optim.SGD):
-            self.kind = KIND_SGD
-        elif isinstance(optimizer, torch.optim.Adam):
-            self.kind = KIND_ADAM
-        elif isinstance(optimizer, torch.optim.RMSprop):
-            self.kind = KIND_RMSPROP
-        else:
-            raise ValueError("FusedLinearOptTrainer needs a torch.optim.SGD, torch.optim.Adam or torch.optim.RMSprop object")
+class _OptimizerState:
+    """What a native step keeps for the torch optimizer whose update its last launch applies (FusedLinearOptTrainer here,
+    fused_small.FusedSmallOptTrainer): the kind, one or two state tensors per parameter, the hyperparameters as a device double[5] and the
+    step count in two words that swap roles from step to step (the launch reads one and writes the other)."""
+
+    def _init_optimizer(self, optimizer, kinds, state2_kinds):
+        """kinds: the optimizers this trainer takes; state2_kinds: those of them whose update keeps a second state tensor.  After
+        _init_network (self.params, self.dev)."""
+        who = type(self).__name__
+        self.kind = next((k for k, name in _OPTIMIZERS if k in kinds and isinstance(optimizer, getattr(torch.optim, name))), None)
+        if self.kind is None:
+            names = [f"torch.optim.{name}" for k, name in _OPTIMIZERS if k in kinds]
+            raise ValueError(f"{who} needs a {', '.join(names[:-1])} or {names[-1]} object")
         grp = optimizer.param_groups[0]
         if self.kind == KIND_RMSPROP and (grp.get('centered') or grp.get('maximize')):
-            raise ValueError("FusedLinearOptTrainer: centered and maximize are not supported with RMSprop")
+            raise ValueError(f"{who}: centered and maximize are not supported with RMSprop")
         if grp.get('nesterov') or grp.get('dampening') or grp.get('amsgrad') or grp.get('maximize'):
-            raise ValueError("FusedLinearOptTrainer: nesterov, dampening, amsgrad and maximize are not supported")
+            raise ValueError(f"{who}: nesterov, dampening, amsgrad and maximize are not supported")
         self.optimizer = optimizer
-        self._init_network(net, weight, lamb, seed)     # (gradients as FusedLinearTrainer keeps them)
         self.state1 = [torch.zeros_like(p) for p in self.params]             # SGD: momentum_buffer; Adam: exp_avg; RMSprop: square_avg
-        self.state2 = [torch.zeros_like(p) for p in self.params] if self.kind != KIND_SGD else []      # Adam: exp_avg_sq; RMSprop: momentum_buffer
+        self.state2 = [torch.zeros_like(p) for p in self.params] if self.kind in state2_kinds else []      # Adam: exp_avg_sq; RMSprop: momentum_buffer
         self.hyper64 = torch.zeros(5, dtype=torch.float64, device=self.dev)      # [lr, momentum | beta1, beta2 | alpha, eps, weight_decay]
         self._hyper_host = [None] * 5
         self.steps = torch.zeros(2, dtype=torch.int64, device=self.dev)          # the optimizer's step count: steps[_tpar] is current
@@ -53,7 +55,6 @@ class FusedLinearOptTrainer(_LinearStepParts):
         self._s2p = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.state2]) if self.state2 else None
         self.sync_hyper()
 
-    # ------------------------------------------------------------------ state and hyperparameters
     def state_tensors(self):
         return list(self.state1) + list(self.state2)
 
@@ -61,12 +62,8 @@ class FusedLinearOptTrainer(_LinearStepParts):
         """The optimizer's step count (waits for the device)."""
         return int(self.steps[self._tpar].item())
 
-    def begin_voter(self, voter, keep_state=False):
-        """Dropout stream of voter v as FusedLinearTrainer.begin_voter sets it (ctl[0] starts at v << 24: voter v draws what it draws under
-        RMSprop).  keep_state: the previous voter's optimizer state stays (IDELUCS_VOTER_STATE=carry); the step count is part of it."""
-        self.ctl[0:1].fill_((int(voter) & 0xFF) << 24)
-        if keep_state:
-            return
+    def _reset_state(self):
+        """A new voter that does not carry the previous one's state: zero states, step count 0."""
         for v in self.state_tensors():
             v.zero_()
         self.steps.zero_()
@@ -87,6 +84,27 @@ class FusedLinearOptTrainer(_LinearStepParts):
                 self.hyper64[i:i + 1].fill_(v)    # (fill_ on a view: no host-to-device copy from pageable memory, FusedLinearTrainer.begin_voter)
                 self._hyper_host[i] = v
 
+    def _step_words(self):
+        """(step_in, step_out) of the next last launch; _step_taken() after it swaps their roles."""
+        return _p(self.steps[self._tpar:]), _p(self.steps[1 - self._tpar:])
+
+    def _step_taken(self):
+        self._tpar ^= 1
+
+
+class FusedLinearOptTrainer(_OptimizerState, _LinearStepParts):
+    def __init__(self, net, optimizer, weight, lamb, seed=0):
+        """optimizer: the torch.optim.SGD / torch.optim.Adam / torch.optim.RMSprop object whose first group holds the hyperparameters (its state is not used)."""
+        self._init_network(net, weight, lamb, seed)     # (gradients as FusedLinearTrainer keeps them)
+        self._init_optimizer(optimizer, kinds=(KIND_SGD, KIND_ADAM, KIND_RMSPROP), state2_kinds=(KIND_ADAM, KIND_RMSPROP))
+
+    def begin_voter(self, voter, keep_state=False):
+        """Dropout stream of voter v as FusedLinearTrainer.begin_voter sets it (ctl[0] starts at v << 24: voter v draws what it draws under
+        RMSprop).  keep_state: the previous voter's optimizer state stays (IDELUCS_VOTER_STATE=carry); the step count is part of it."""
+        self.ctl[0:1].fill_((int(voter) & 0xFF) << 24)
+        if not keep_state:
+            self._reset_state()
+
     def layer1_output(self, bf):
         """Layer 1's ReLU (+ Dropout) output of the last step on bf as an [m, 512] tensor (tests): the step forms whose layer-1 product is
         W1 x^T keep it transposed."""
@@ -100,10 +118,10 @@ class FusedLinearOptTrainer(_LinearStepParts):
         gather = (None, 0, 0, 0, None, 0, 0, None, None, None, None) if st is None else (
             _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs, m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.x))
         _launch(_L.idl_opt_step_gather_wgrad, self.kind, len(self.params), self._pp, self._gp, self._parts, self._s1p, self._s2p, self._sz,
-                _p(self.hyper64), _p(self.steps[self._tpar:]), _p(self.steps[1 - self._tpar:]), _p(self.ctl),
+                _p(self.hyper64), *self._step_words(), _p(self.ctl),
                 _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out), *gather,
                 2, _p(bf.dlat), _p(r1), transposed, m, self.H2, self.H1, _p(self.grads[2]), advance, _stream())
-        self._tpar ^= 1
+        self._step_taken()
 
     def _dw1(self, bf, x):
         m, H1, F = bf.m, self.H1, self.F

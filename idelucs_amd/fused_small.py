@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from ._lib import lib as _L
 from .fused import TEMPERATURE, _launch, _p, _stream, launch_losses
+from .fused_opt import KIND_ADAM, KIND_SGD, _OptimizerState  # (KIND_* stay names of this module)
 
 H1, H2, LAT = 400, 128, 64  # myNet's widths (reference PytorchUtils.py:12-18)
 MAX_C = 256
@@ -221,76 +222,31 @@ class FusedSmallTrainer:
         return self.out[1], n_full + (1 if rem else 0)
 
 
-KIND_SGD, KIND_ADAM = 1, 2
-
-
-class FusedSmallOptTrainer(FusedSmallTrainer):
+class FusedSmallOptTrainer(_OptimizerState, FusedSmallTrainer):
     """The step of FusedSmallTrainer with torch.optim.SGD or torch.optim.Adam (reference models.py:89-92) in its last launch,
     idl_small_wgrad_opt.  Opt-in: IID_model(args) with args['small_opt_step'] = 'native' (CLI: --small_opt_step native).  Nothing in the
     five launches in front of it knows which optimizer follows; buffers, dropout streams, dropout_masks(), keep_grads, partial batches and
     the epoch loop are inherited.  SGD keeps momentum_buffer per tensor, Adam exp_avg and exp_avg_sq plus its step count in two words that
-    swap roles from step to step (the launch reads one and writes the other).  The hyperparameters are copied from the torch optimizer's
-    group before every epoch (sync_hyper): the schedulers keep acting on that object, CyclicLR on momentum / beta1 as well as the rate."""
+    swap roles from step to step (fused_opt._OptimizerState, which FusedLinearOptTrainer shares).  The hyperparameters are copied from
+    the torch optimizer's group before every epoch (sync_hyper): the schedulers keep acting on that object, CyclicLR on momentum / beta1
+    as well as the rate."""
 
     def __init__(self, net, optimizer, weight, lamb, seed=0):
         """optimizer: the torch.optim.SGD / torch.optim.Adam object whose first group holds the hyperparameters (its state is not used)."""
-        if isinstance(optimizer, torch.optim.SGD):
-            self.kind = KIND_SGD
-        elif isinstance(optimizer, torch.optim.Adam):
-            self.kind = KIND_ADAM
-        else:
-            raise ValueError("FusedSmallOptTrainer needs a torch.optim.SGD or torch.optim.Adam object")
-        grp = optimizer.param_groups[0]
-        if grp.get('nesterov') or grp.get('dampening') or grp.get('amsgrad') or grp.get('maximize'):
-            raise ValueError("FusedSmallOptTrainer: nesterov, dampening, amsgrad and maximize are not supported")
-        self.optimizer = optimizer
         self._init_network(net, weight, lamb, seed)
-        self.state1 = [torch.zeros_like(p) for p in self.params]             # SGD: momentum_buffer; Adam: exp_avg
-        self.state2 = [torch.zeros_like(p) for p in self.params] if self.kind == KIND_ADAM else []      # Adam: exp_avg_sq
-        self.hyper64 = torch.zeros(5, dtype=torch.float64, device=self.dev)      # [lr, momentum | beta1, beta2, eps, weight_decay]
-        self._hyper_host = [None] * 5
-        self.steps = torch.zeros(2, dtype=torch.int64, device=self.dev)          # the optimizer's step count: steps[_tpar] is current
-        self._tpar = 0
-        n = len(self.params)
-        self._s1p = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.state1])
-        self._s2p = (ctypes.c_void_p * n)(*[v.data_ptr() for v in self.state2]) if self.state2 else None
-        self.sync_hyper()
-
-    def state_tensors(self):
-        return list(self.state1) + list(self.state2)
-
-    def step_count(self):
-        """The optimizer's step count (waits for the device)."""
-        return int(self.steps[self._tpar].item())
+        self._init_optimizer(optimizer, kinds=(KIND_SGD, KIND_ADAM), state2_kinds=(KIND_ADAM,))
 
     def begin_voter(self, voter, keep_state=False):
         """Dropout stream of voter v as FusedSmallTrainer.begin_voter sets it.  keep_state: the previous voter's optimizer state stays
         (IDELUCS_VOTER_STATE=carry); the step count is part of it."""
         self.ctl[0:1].fill_((int(voter) & 0xFF) << 24)
-        if keep_state:
-            return
-        for v in self.state_tensors():
-            v.zero_()
-        self.steps.zero_()
-        self._tpar = 0
-
-    def sync_hyper(self):
-        """Copy the torch optimizer's current group to the device (before every epoch: the schedulers act on that object)."""
-        grp = self.optimizer.param_groups[0]
-        if self.kind == KIND_SGD:
-            vals = [grp['lr'], grp['momentum'], 0.0, 0.0, grp['weight_decay']]
-        else:
-            vals = [grp['lr'], grp['betas'][0], grp['betas'][1], grp['eps'], grp['weight_decay']]
-        for i, v in enumerate(vals):
-            v = float(v)
-            if v != self._hyper_host[i]:
-                self.hyper64[i:i + 1].fill_(v)    # (fill_ on a view: no host-to-device copy from pageable memory)
-                self._hyper_host[i] = v
+        if not keep_state:
+            self._reset_state()
 
     def _last_launch(self, tail):
-        _lib.check(_L.idl_small_wgrad_opt(self.kind, self._pp, self._gp(), self._s1p, self._s2p, _p(self.hyper64),
-                                          _p(self.steps[self._tpar:]), _p(self.steps[1 - self._tpar:]), _p(self.ctl), *tail))
-        self._tpar ^= 1
+        _lib.check(_L.idl_small_wgrad_opt(self.kind, self._pp, self._gp(), self._s1p, self._s2p, _p(self.hyper64), *self._step_words(),
+                                          _p(self.ctl), *tail))
+        self._step_taken()
 
     def _graph_key_extra(self):
         """The role of the two step words: an epoch with an odd number of steps flips it, and a captured graph bakes their addresses."""
