@@ -50,7 +50,7 @@ def run_assign(args):
     ens = FittedEnsemble.load(args["model"])
     out_dir = _results_dir(args["assign"])
     os.makedirs(out_dir, exist_ok=False)
-    names, y_pred, probabilities = ens.assign(args["assign"], predict=args.get("predict"))
+    names, y_pred, probabilities = ens.assign(args["assign"], predict=args.get("predict"), small_predict=args.get("small_predict"))
     _write_assignments(out_dir, names, y_pred, probabilities)
     print(f"No. Sequences: \t {len(names):,}")
     for c, n_c in zip(*np.unique(y_pred, return_counts=True)):
@@ -306,6 +306,10 @@ def build_parser():
                    help="the eval forward behind the votes and the latent: nn.Linear on hipBLASLt (the default), or native -- this package's own "
                         "kernels, whose rows do not depend on chunking, sharding or the library's tuning (model_size='linear', 4 <= k <= 9, "
                         "n_clusters <= 256); with --assign: the mode the saved run predicted with")
+    p.add_argument("--small_predict", action="store", type=str, default=argparse.SUPPRESS, choices=["torch", "native"],
+                   help="model_size='small': the eval forward behind the votes and the latent on hipBLASLt (the default), or native -- this package's "
+                        "own kernels, whose rows do not depend on chunking, sharding or the library's tuning (n_clusters <= 256); with --assign: the "
+                        "mode the saved run predicted with")
     p.add_argument("--save_model", action="store", type=str, default=argparse.SUPPRESS, metavar="DIR",
                    help="a training run: keep the voters' weights, the predict scaler and the ensemble's vote tables (n_clusters = 0: the last "
                         "voter's latent with its clusters) in DIR/ensemble.pt, for --assign")

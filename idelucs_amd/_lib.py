@@ -124,6 +124,8 @@ SIGNATURES = {
     "idl_l1_fwd_supported": (_int, [_int, _int, _int]),
     "idl_l1_fwd": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
     "idl_predict_mid": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "idl_small_predict_l1": (_int, [_vp, _vp, _int, _int, _vp, _vp]),
+    "idl_small_predict_mid": (_int, [_vp] * 8 + [_int, _int, _vp, _vp, _vp, _vp, _vp]),
     "idl_debug_wgrad_clock": (_int, [_vp, _vp, _int, _int, _int, _vp, _int, _vp, _vp]),
     "idl_wgrad_rmsprop_step": (_int, [_vp, _vp, _int, _int, _int, _vp, _tail, _vp]),
     "idl_l1_fwd_rms": (_int, [_vp, _vp, _int, _int, _vp, _tail, _vp]),

@@ -270,12 +270,21 @@ class FittedEnsemble:
         from .models import IID_model
         return IID_model._predict_mode({'predict': predict, 'model_size': self.model_size, 'k': self.k, 'n_clusters': self.n_units})
 
-    def voter_outputs(self, sequence_file, device=None, chunk_rows=None, predict=None):
+    def _small_predict_mode(self, small_predict, predict=None):
+        """small_predict=None or 'torch': as _predict_mode decides; 'native': through predict_native.NativeSmallPredictor -- small models of the
+        shapes IID_model._small_predict_mode accepts; anything else raises ValueError."""
+        from .models import IID_model
+        return IID_model._small_predict_mode({'small_predict': small_predict, 'predict': predict, 'model_size': self.model_size, 'k': self.k,
+                                              'n_clusters': self.n_units})
+
+    def voter_outputs(self, sequence_file, device=None, chunk_rows=None, predict=None, small_predict=None):
         """The saved voters' eval forward on a file's rows, standardised with the TRAINING file's statistics, a chunk at a time (there is
         no [M, F] matrix) -> (names, units int64 [V, M] on the device: every voter's argmax, latent float32 [M, 64] on the device: the
         last voter's).  predict: the mode the run predicted with ('native': a row's outputs are the training run's bit for bit whatever
-        chunk_rows is, and no library product is involved)."""
+        chunk_rows is, and no library product is involved).  small_predict: the same for model_size='small'."""
         native = self._predict_mode(predict) == 'native'
+        small_native = self._small_predict_mode(small_predict, predict) == 'native'
+        native = native or small_native
         _lib.require_gpu()
         dev = utils._device(device)
         if not native:
@@ -284,8 +293,8 @@ class FittedEnsemble:
         stats = (self.mean.to(dev), self.scale.to(dev))
         nets = self._networks(dev)
         if native:
-            from .predict_native import NativeLinearPredictor
-            predictors = [NativeLinearPredictor(net) for net in nets]
+            from . import predict_native
+            predictors = [(predict_native.NativeSmallPredictor if small_native else predict_native.NativeLinearPredictor)(net) for net in nets]
         din, ff = _open_input(sequence_file, dev)
         try:
             m = din.n
@@ -306,14 +315,14 @@ class FittedEnsemble:
             ff.close()
         return ff.names, units, latent
 
-    def assign(self, sequence_file, device=None, predict=None):
+    def assign(self, sequence_file, device=None, predict=None, small_predict=None):
         """The sequences of a file -> (names, y_pred int64 [M], confidence float64 [M]) in the clusters of the training run.
         mode 'ensemble': every voter's argmax through its unit map (a unit that never won on the training file: no vote), then
         votes_to_clusters -- confidence 1.0 where the record sits on its centre (the reference's inf / inf is NaN there).
         mode 'fine': labels[nn], prob[nn] * min(1, spacing[nn] / dist) with nn the nearest training latent (dist == 0: the factor is 1),
         so a sequence of the training file gets its training label and probability.
-        predict: as voter_outputs -- assign with the mode the run predicted with."""
-        names, units, latent = self.voter_outputs(sequence_file, device, predict=predict)
+        predict / small_predict: as voter_outputs -- assign with the mode the run predicted with."""
+        names, units, latent = self.voter_outputs(sequence_file, device, predict=predict, small_predict=small_predict)
         dev = units.device
         if self.mode == "ensemble":
             maps = self.unit_maps.to(dev).long()

@@ -130,6 +130,9 @@ class IID_model():
         self._streamed_store = self._store_mode(args) == 'streamed'
         # the eval forward of predict / calculate_probs / predict_latent_shard: self.net (hipBLASLt), or, opt-in, this package's own launches
         self._native_predict = self._predict_mode(args) == 'native'
+        # ... and of model_size='small': self.net, or, opt-in, predict_native.NativeSmallPredictor (the branches below serve either predictor)
+        self._small_native_predict = self._small_predict_mode(args) == 'native'
+        self._native_predict = self._native_predict or self._small_native_predict
         self._predictor = None
 
     @staticmethod
@@ -147,6 +150,28 @@ class IID_model():
             raise ValueError(f"predict='native' supports 4 <= k <= {_lib.MAX_K} (got k={args['k']}): layer 1's tiles take rows of 4^k >= 192 entries")
         if not 1 <= args['n_clusters'] <= 256:
             raise ValueError(f"predict='native' supports n_clusters in 1..256 (got n_clusters={args['n_clusters']})")
+        return mode
+
+    @staticmethod
+    def _small_predict_mode(args):
+        """args['small_predict'] of a model_size='small' model: 'torch' (absent or None) or 'native' (a k whose canonical rows the streamed route
+        makes, utils.stream_route_ok(k, True), and n_clusters in 1..256: the shapes idl_small_predict_l1 and idl_small_predict_mid take, not
+        together with predict='native', which is NetLinear's); anything else raises ValueError."""
+        mode = args.get('small_predict') or 'torch'
+        if mode not in ('torch', 'native'):
+            raise ValueError(f"small_predict must be 'torch' or 'native', not {mode!r}")
+        if mode == 'torch':
+            return mode
+        if args.get('predict') == 'native':
+            raise ValueError("small_predict='native' and predict='native' exclude each other: predict='native' runs NetLinear's eval forward "
+                             "(model_size='linear'), small_predict='native' myNet's (model_size='small')")
+        if args['model_size'] != 'small':
+            raise ValueError(f"small_predict='native' runs myNet's eval forward only (model_size='small', got {args['model_size']!r}); "
+                             "model_size='linear' has predict='native'")
+        if not utils.stream_route_ok(args['k'], True):
+            raise ValueError(f"small_predict='native' supports the k of the streamed canonical rows (got k={args['k']})")
+        if not 1 <= args['n_clusters'] <= 256:
+            raise ValueError(f"small_predict='native' supports n_clusters in 1..256 (got n_clusters={args['n_clusters']})")
         return mode
 
     @staticmethod
@@ -414,12 +439,16 @@ class IID_model():
 
     def _forward_of(self, want_z):
         """The eval forward of one chunk of rows -> a tuple of per-row tensors: (outputs, latent) through self.net (predict='torch'), or
-        (latent, prob, unit, z or None) from the native predictor (predict='native': predict_native.NativeLinearPredictor, built at first use)."""
+        (latent, prob, unit, z or None) from the native predictor (predict='native': predict_native.NativeLinearPredictor; small_predict='native':
+        predict_native.NativeSmallPredictor; built at first use)."""
         if not self._native_predict:
             return self.net
         if self._predictor is None:
-            from .predict_native import NativeLinearPredictor
-            self._predictor = NativeLinearPredictor(self.net)
+            from . import predict_native
+            if self._small_native_predict:
+                self._predictor = predict_native.NativeSmallPredictor(self.net)
+            else:
+                self._predictor = predict_native.NativeLinearPredictor(self.net)
         return lambda x: self._predictor.forward(x, want_z)
 
     def _predict_outputs_streamed(self, rows, want_z=True):
