@@ -40,6 +40,11 @@ class idl_opt_tail_t(_c.Structure):
                 ("wg_n_out", _int), ("wg_n_in", _int), ("wg_grad", _vp), ("batch_advance", _i64)]
 
 
+class idl_opt_state_t(_c.Structure):
+    """SGD (kind 1), Adam (2) or RMSprop with momentum (3) in a step's last launch (include/idelucs_hip.h): its states, hyperparameters and step words."""
+    _fields_ = [("kind", _int), ("state1", _c.POINTER(_vp)), ("state2", _c.POINTER(_vp)), ("hyper", _vp), ("step_in", _vp), ("step_out", _vp)]
+
+
 class idl_vectorise_plan_t(_c.Structure):
     """What idl_vectorise would launch (include/idelucs_hip.h): kernel is one of VEC_*; redo != 0: a second pass on v2 follows."""
     _fields_ = [(name, _int) for name in ("kernel", "copies_log2", "other_modes", "diag", "threads", "lds_bytes", "wg_per_cu", "grid", "waves", "sc_slots",
@@ -47,7 +52,8 @@ class idl_vectorise_plan_t(_c.Structure):
 
 
 VEC_V1, VEC_V2, VEC_V2_B16, VEC_V3, VEC_V4, VEC_SLICES = 1, 2, 3, 4, 5, 6
-_nb, _tail = _c.POINTER(idl_next_batch_t), _c.POINTER(idl_opt_tail_t)
+_nb, _tail, _opt = _c.POINTER(idl_next_batch_t), _c.POINTER(idl_opt_tail_t), _c.POINTER(idl_opt_state_t)
+_SMALL_FROM_X = [_vp] * 8 + [_int, _int, _int, _vp, _c.c_float, _c.c_float, _vp, _nb, _vp]      # what idl_small_wgrad_* take from `x` on
 
 # name -> (restype, argtypes); kept in one table so tests can check every symbol the header declares
 SIGNATURES = {
@@ -186,16 +192,11 @@ SIGNATURES = {
     "idl_small_mid_fwd": (_int, [_vp] * 8 + [_int, _int, _int, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "idl_small_mid_bwd": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _c.c_float, _c.c_uint64,
                                  _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "idl_small_wgrad_rms": (_int, [_vp] * 5 + [_vp] * 8 + [_int, _int, _int, _vp, _c.c_float, _c.c_float, _vp,
-                                   _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "idl_small_wgrad_rms_momentum": (_int, [_vp] * 6 + [_vp] * 8 + [_int, _int, _int, _vp, _c.c_float, _c.c_float, _vp,
-                                            _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-    # (kind, params, grads, state1, state2, hyper, step_in, step_out, ctl, then idl_small_wgrad_rms's arguments from x on)
-    "idl_small_wgrad_opt": (_int, [_int] + [_vp] * 8 + [_vp] * 8 + [_int, _int, _int, _vp, _c.c_float, _c.c_float, _vp,
-                                   _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "idl_opt_step_gather_wgrad": (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float, _c.c_float, _vp,
-                                         _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
-                                         _int, _vp, _vp, _int, _int, _int, _int, _vp, _i64, _vp]),
+    # (params, grads, square_avg, [momentum_buffer,] hyper, ctl | opt, params, grads, ctl; then x .. dlogits, m, F, C, loss_rows, w_nce, w_iic, out, next_batch, stream)
+    "idl_small_wgrad_rms": (_int, [_vp] * 5 + _SMALL_FROM_X),
+    "idl_small_wgrad_rms_momentum": (_int, [_vp] * 6 + _SMALL_FROM_X),
+    "idl_small_wgrad_opt": (_int, [_opt, _vp, _vp, _vp] + _SMALL_FROM_X),
+    "idl_opt_step_gather_wgrad": (_int, [_tail, _opt, _nb, _vp]),
     "idl_small_dropout_masks": (_int, [_c.c_uint64, _i64, _int, _vp, _vp, _vp]),
 }
 

@@ -25,6 +25,7 @@
 #include "common.h"
 #include "opt_update_device.h"
 #include "scaler_device.h"
+#include "step_args.h"
 #include "wave_ops.h"
 
 namespace {
@@ -62,9 +63,9 @@ struct OptArgs {
 };
 
 // One 16 x 16 tile of dy^T x: the four waves take a quarter of the contraction index each.  red: 1024 floats of LDS.
-// (The three operand loops and the LDS reduction are train_step.hip's wgrad_tile_rms without its look-ahead and spin forms, and the
-//  streaming body below follows rmsprop_body: that file's kernels stay as they are -- their register, ISA and bit-for-bit tests pin them --
-//  so a fix to the tile loop is made in BOTH files until the loops move into a shared .inc, as at_b_tile.inc did.)
+// (The operand loops are dyT_x_tile16.inc, shared with train_step.hip's wgrad_tile_rms.  The LDS reduction here, and the streaming body and
+//  step-loss tail of opt_step_kernel below, follow wgrad_tile_rms and rmsprop_body as separate texts: merging them would move that file's
+//  kernels, which their register, ISA and bit-for-bit tests pin.)
 template <int KIND>
 __device__ __forceinline__ void wgrad_tile(const OptArgs &a, int tile, const Coef<KIND> &c, float *red, const int tid)
 {
@@ -76,45 +77,8 @@ __device__ __forceinline__ void wgrad_tile(const OptArgs &a, int tile, const Coe
     const int kb = wv * per, ke = (kb + per < m) ? kb + per : m;
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
     const float *pa = a.wg_dy + i0 + l, *pb = a.wg_x + j0 + l;    // A[i = l][k = q] = dy[k][i0 + l], B[k = q][j = l] = x[k][j0 + l]
-    if (a.wg_xt && (per & 127) == 0 && kb + per <= m) {
-        // x stored transposed ([n_in, m]): lane (l, q) walks 32 consecutive k of ITS column per batch (16-byte reads), and MFMA step
-        // u takes k = k0 + 32 q + u on both operands -- any assignment of k to (step, q) is a valid order of the same sum
-        const float *pbt = a.wg_x + (int64_t)(j0 + l) * m;
-        for (int k0 = kb; k0 < ke; k0 += 128) {
-            float av[32], bv[32];
-#pragma unroll
-            for (int u4 = 0; u4 < 8; ++u4) {
-                const float4 t4 = *(const float4 *)(pbt + k0 + 32 * q + 4 * u4);
-                bv[4 * u4] = t4.x; bv[4 * u4 + 1] = t4.y; bv[4 * u4 + 2] = t4.z; bv[4 * u4 + 3] = t4.w;
-            }
-#pragma unroll
-            for (int u = 0; u < 32; ++u) av[u] = pa[(k0 + 32 * q + u) * lda];
-#pragma unroll
-            for (int u = 0; u < 32; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
-        }
-    } else if (a.wg_xt) {
-        for (int k0 = kb; k0 < ke; k0 += 4) {
-            const int k = k0 + q;
-            const bool ok = k < ke;
-            const float ta = ok ? pa[k * lda] : 0.f, tb = ok ? a.wg_x[(int64_t)(j0 + l) * m + k] : 0.f;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ta, tb, acc, 0, 0, 0);
-        }
-    } else {
-        for (int k0 = kb; k0 < ke; k0 += 128) {              // 64 independent loads in flight per lane, then 32 MFMAs
-            float av[32], bv[32];
-#pragma unroll
-            for (int u = 0; u < 32; ++u) {
-                const int k = k0 + 4 * u + q;
-                const bool ok = k < ke;
-                const int kc = ok ? k : ke - 1;              // clamped, not predicated: inside the operands, the loads stay unconditional
-                const float ta = pa[kc * lda], tb = pb[kc * ldb];
-                av[u] = ok ? ta : 0.f;
-                bv[u] = ok ? tb : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 32; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
-        }
-    }
+    constexpr bool AHEAD = false;                            // (no look-ahead form here: the streaming blocks want the registers)
+#include "dyT_x_tile16.inc"
     const int o = (i0 + (tid >> 4)) * ldb + j0 + (tid & 15);      // this thread's element of the tile in the epilogue
     float *p = a.p[a.wg_t], *s1 = a.s1[a.wg_t], *s2 = a.s2[a.wg_t];
     float pi = p[o], ai = s1[o], bi = KIND != KIND_SGD ? s2[o] : 0.f;      // (requested before the barrier: beside the LDS round trip)
@@ -221,52 +185,42 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(OptArgs a, int n_
 
 extern "C" {
 
-int idl_opt_step_gather_wgrad(int kind, int count, float *const *params, const float *const *grads, const int32_t *grad_parts,
-                              float *const *state1, float *const *state2, const int64_t *sizes, const double *hyper,
-                              const int64_t *step_in, int64_t *step_out, int64_t *ctl,
-                              const float *loss_rows, int loss_m, float w_nce, float w_iic, float *out,
-                              const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx, int64_t n_pairs,
-                              int64_t batch, const double *mean, const double *scale, const double *inv_scale, float *y,
-                              int wg_index, const float *wg_dy, const float *wg_x, int wg_x_transposed, int wg_m, int wg_n_out, int wg_n_in,
-                              float *wg_grad, int64_t batch_advance, void *stream)
+int idl_opt_step_gather_wgrad(const idl_opt_tail_t *tail, const idl_opt_state_t *opt, const idl_next_batch_t *next_batch, void *stream)
 {
-    IDL_REQUIRE(kind == KIND_SGD || kind == KIND_ADAM || kind == KIND_RMSPROP, "opt_step: kind 1 (SGD with momentum), 2 (Adam) or 3 (RMSprop with momentum)");
-    IDL_REQUIRE(count >= 1 && count <= 8 && params && grads && state1 && sizes && hyper && ctl, "opt_step: 1..8 tensors");
-    IDL_REQUIRE(kind == KIND_SGD || state2 != nullptr, "opt_step: Adam needs exp_avg_sq, RMSprop momentum_buffer (state2)");
-    IDL_REQUIRE(step_in && step_out && step_in != step_out, "opt_step: the step count is read from one word and written to another");
-    IDL_REQUIRE((const void *)step_in != (const void *)ctl && (const void *)step_in != (const void *)(ctl + 1),
-                "opt_step: step_in must not be a word this launch writes");
-    IDL_REQUIRE((((uintptr_t)hyper) & 7u) == 0, "opt_step: hyper is a device double[5]");
+    IDL_REQUIRE(tail != nullptr, "opt_step: NULL tail");
+    const idl_opt_tail_t &t = *tail;
+    const int count = t.count, wg_index = t.wg_index;
+    IDL_REQUIRE(count >= 1 && count <= 8 && t.params && t.grads && t.sizes && t.ctl, "opt_step: 1..8 tensors");
+    IDL_REQUIRE(t.square_avg == nullptr && t.hyper == nullptr, "opt_step: tail->square_avg and tail->hyper must be NULL (the optimizer is opt)");
+    IDL_REQUIRE(t.skip_index == -1, "opt_step: tail->skip_index must be -1");
+    if (const int rc = idl_step::opt_state_of("opt_step", opt, t.ctl, 1u << KIND_SGD | 1u << KIND_ADAM | 1u << KIND_RMSPROP, count)) return rc;
+    const int kind = opt->kind;
     OptArgs a{};
     a.count = count;
-    IDL_REQUIRE(loss_rows == nullptr || (out != nullptr && loss_m > 0), "opt_step: loss_rows given without out or with loss_m < 1");
-    a.loss_rows = loss_rows; a.out = loss_rows != nullptr ? out : nullptr; a.loss_m = loss_m; a.w_nce = w_nce; a.w_iic = w_iic;
-    a.hyper = hyper; a.step_in = step_in; a.step_out = step_out; a.ctl = ctl; a.batch_advance = batch_advance;
+    IDL_REQUIRE(t.loss_rows == nullptr || (t.out != nullptr && t.loss_m > 0), "opt_step: tail->loss_rows given without out or with loss_m < 1");
+    a.loss_rows = t.loss_rows; a.out = t.loss_rows != nullptr ? t.out : nullptr; a.loss_m = t.loss_m; a.w_nce = t.w_nce; a.w_iic = t.w_iic;
+    a.hyper = opt->hyper; a.step_in = opt->step_in; a.step_out = opt->step_out; a.ctl = t.ctl; a.batch_advance = t.batch_advance;
     for (int i = 0; i < count; ++i) {
-        a.p[i] = params[i]; a.g[i] = grads[i]; a.s1[i] = state1[i]; a.s2[i] = kind != KIND_SGD ? state2[i] : nullptr; a.n[i] = sizes[i];
-        a.parts[i] = grad_parts ? grad_parts[i] : 1;
-        IDL_REQUIRE(a.parts[i] >= 1 && sizes[i] >= 0, "opt_step: grad_parts must be >= 1, sizes >= 0");
-        IDL_REQUIRE(sizes[i] == 0 || (a.p[i] && a.s1[i] && (kind == KIND_SGD || a.s2[i])), "opt_step: a tensor without its parameter or state pointer");
-        IDL_REQUIRE(sizes[i] == 0 || i == wg_index || a.g[i], "opt_step: a tensor without its gradient");
+        a.p[i] = t.params[i]; a.g[i] = t.grads[i]; a.s1[i] = opt->state1[i]; a.s2[i] = kind != KIND_SGD ? opt->state2[i] : nullptr; a.n[i] = t.sizes[i];
+        a.parts[i] = t.grad_parts ? t.grad_parts[i] : 1;
+        IDL_REQUIRE(a.parts[i] >= 1 && t.sizes[i] >= 0, "opt_step: tail->grad_parts must be >= 1, sizes >= 0");
+        IDL_REQUIRE(t.sizes[i] == 0 || a.p[i], "opt_step: a tensor without its parameter pointer");
+        IDL_REQUIRE(t.sizes[i] == 0 || i == wg_index || a.g[i], "opt_step: a tensor without its gradient");
     }
     if (wg_index >= 0) {
-        IDL_REQUIRE(wg_index < count && wg_dy && wg_x && wg_m >= 1 && wg_n_out >= 16 && (wg_n_out % 16) == 0 && wg_n_in >= 16 &&
-                    (wg_n_in % 16) == 0 && sizes[wg_index] == (int64_t)wg_n_out * wg_n_in && (int64_t)wg_m * wg_n_in < (1ll << 31) &&
-                    (int64_t)wg_m * wg_n_out < (1ll << 31),
+        IDL_REQUIRE(wg_index < count && t.wg_dy && t.wg_x && t.wg_m >= 1 && t.wg_n_out >= 16 && (t.wg_n_out % 16) == 0 && t.wg_n_in >= 16 &&
+                    (t.wg_n_in % 16) == 0 && t.sizes[wg_index] == (int64_t)t.wg_n_out * t.wg_n_in && (int64_t)t.wg_m * t.wg_n_in < (1ll << 31) &&
+                    (int64_t)t.wg_m * t.wg_n_out < (1ll << 31),
                     "opt_step: in-launch weight gradient needs n_out, n_in multiples of 16 and sizes[wg_index] == n_out * n_in");
-        IDL_REQUIRE(!wg_x_transposed || ((wg_m & 3) == 0 && (((uintptr_t)wg_x) & 15u) == 0), "opt_step: transposed wg_x needs 4 | m and 16-byte alignment");
-        a.wg_t = wg_index; a.wg_dy = wg_dy; a.wg_x = wg_x; a.wg_grad = wg_grad; a.wg_m = wg_m; a.wg_n_out = wg_n_out; a.wg_n_in = wg_n_in;
-        a.wg_tiles = (wg_n_out / 16) * (wg_n_in / 16);
-        a.wg_xt = wg_x_transposed ? 1 : 0;
+        IDL_REQUIRE(!t.wg_x_transposed || ((t.wg_m & 3) == 0 && (((uintptr_t)t.wg_x) & 15u) == 0), "opt_step: transposed wg_x needs 4 | m and 16-byte alignment");
+        a.wg_t = wg_index; a.wg_dy = t.wg_dy; a.wg_x = t.wg_x; a.wg_grad = t.wg_grad; a.wg_m = t.wg_m; a.wg_n_out = t.wg_n_out; a.wg_n_in = t.wg_n_in;
+        a.wg_tiles = (t.wg_n_out / 16) * (t.wg_n_in / 16);
+        a.wg_xt = t.wg_x_transposed ? 1 : 0;
         a.n[wg_index] = 0;                  // its optimizer blocks have nothing to do: the tile workgroups update it
     }
     idl_dev::GatherArgs g{};
-    if (feats != nullptr) {
-        IDL_REQUIRE(pair_idx && mean && scale && y && n >= 1 && f >= 1 && batch >= 1 && n_pairs >= 0, "opt_step: bad gather arguments");
-        IDL_REQUIRE(batch_advance == 0, "opt_step: the launch that assembles the next batch reads ctl[1] and cannot advance it");
-        g = idl_dev::GatherArgs{feats, n, f, view_stride, pair_idx, ctl + 1, batch, n_pairs, mean, scale, inv_scale, y};
-        g.wt = idl_store::wt_mask();
-    }
+    if (const int rc = idl_step::whole_batch_of("opt_step", next_batch, t.ctl, g)) return rc;
+    IDL_REQUIRE(g.y == nullptr || t.batch_advance == 0, "opt_step: the launch that assembles the next batch reads ctl[1] and cannot advance it: tail->batch_advance must be 0");
     int nb_total = 0;
     for (int i = 0; i < count; ++i) {
         const uintptr_t al = ((uintptr_t)a.p[i]) | ((uintptr_t)a.g[i]) | ((uintptr_t)a.s1[i]) | ((uintptr_t)a.s2[i]);

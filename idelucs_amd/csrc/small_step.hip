@@ -25,6 +25,7 @@
 #include "opt_update_device.h"
 #include "philox_device.h"
 #include "scaler_device.h"
+#include "step_args.h"
 #include "wave_ops.h"
 
 namespace {
@@ -741,61 +742,68 @@ int idl_small_mid_bwd(const float *z, const float *f, const float *inv, const fl
     return IDL_OK;
 }
 
+// What every form of the step's last launch takes from `x` on.
+struct SmallStepIn {
+    const float *x, *dr1, *a1, *da2, *a2, *dh, *d2, *dlogits; int m, F, C; const float *loss_rows; float w_nce, w_iic; float *out;
+    const idl_next_batch_t *next_batch; void *stream;
+};
+
 // The forms of the step's last launch share everything but the optimizer's epilogue: momentum_buffer == NULL is idl_small_wgrad_rms;
-// kind != 0 is idl_small_wgrad_opt (SGD / Adam: ob holds its states, hyperparameters and step words; square_avg and hyper are not looked at).
+// opt != NULL (checked by the caller) is idl_small_wgrad_opt (SGD / Adam: its states, hyperparameters and step words; square_avg and hyper are not looked at).
 static int small_wgrad_launch(float *const *params, float *const *grads, float *const *square_avg, float *const *momentum_buffer,
-                              const float *hyper, int64_t *ctl,
-                              const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
-                              const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
-                              float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
-                              int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
-                              float *y_next, void *stream, int kind = 0, const OptBufs *ob = nullptr)
+                              const float *hyper, int64_t *ctl, const SmallStepIn &s, const idl_opt_state_t *opt = nullptr)
 {
-    IDL_REQUIRE(params && (kind != 0 || (square_avg && hyper)) && ctl && x && dr1 && a1 && da2 && a2 && dh && d2 && dlogits, "NULL buffer");
+    const int m = s.m, F = s.F, C = s.C;
+    IDL_REQUIRE(params && (opt != nullptr || (square_avg && hyper)) && ctl && s.x && s.dr1 && s.a1 && s.da2 && s.a2 && s.dh && s.d2 && s.dlogits, "NULL buffer");
     IDL_REQUIRE(m >= 1 && F >= 1 && C >= 1 && C <= SMAX_C, "small_wgrad_rms: m, F >= 1, n_clusters in 1..256");
-    for (int t = 0; t < 8; ++t) IDL_REQUIRE(params[t] && (kind != 0 || square_avg[t]), "small_wgrad_rms: NULL parameter or running average");
-    IDL_REQUIRE(gather_batch == 0 || (feats && pair_idx && mean && scale && y_next && n >= 1 && f == F),
-                "small_wgrad_rms: the next batch needs the store, the permutation and an output of width F");
+    for (int t = 0; t < 8; ++t) IDL_REQUIRE(params[t] && (opt != nullptr || square_avg[t]), "small_wgrad_rms: NULL parameter or running average");
     SmallWgArgs a{};
-    const float *dys[4] = {dr1, da2, dh, dlogits}, *xs[4] = {x, a1, a2, d2};
+    if (const int rc = idl_step::whole_batch_of("small_wgrad_rms", s.next_batch, ctl, a.gth)) return rc;
+    IDL_REQUIRE(a.gth.y == nullptr || a.gth.f == F, "small_wgrad_rms: the next batch's rows must have width F (next_batch->f)");
+    const float *dys[4] = {s.dr1, s.da2, s.dh, s.dlogits}, *xs[4] = {s.x, s.a1, s.a2, s.d2};
     const int Ms[4] = {SH1, SH2, SLAT, C}, Ns[4] = {F, SH1, SH2, SH2};
     int end = 0;
     for (int t = 0; t < 4; ++t) {
         GradJob &j = a.g[t];
         j.dy = dys[t]; j.xin = xs[t]; j.M = Ms[t]; j.N = Ns[t]; j.tiles_n = (Ns[t] + WG_TN - 1) / WG_TN;
-        j.W = params[2 * t]; j.v = kind == 0 ? square_avg[2 * t] : nullptr; j.grad = grads ? grads[2 * t] : nullptr;
+        j.W = params[2 * t]; j.v = opt == nullptr ? square_avg[2 * t] : nullptr; j.grad = grads ? grads[2 * t] : nullptr;
         end += ((Ms[t] + WG_TM - 1) / WG_TM) * j.tiles_n;
         a.g_end[t] = end;
     }
     for (int t = 0; t < 4; ++t) {
         BiasJob &j = a.b[t];
-        j.dy = dys[t]; j.N = Ms[t]; j.b = params[2 * t + 1]; j.v = kind == 0 ? square_avg[2 * t + 1] : nullptr; j.grad = grads ? grads[2 * t + 1] : nullptr;
+        j.dy = dys[t]; j.N = Ms[t]; j.b = params[2 * t + 1]; j.v = opt == nullptr ? square_avg[2 * t + 1] : nullptr; j.grad = grads ? grads[2 * t + 1] : nullptr;
         end += (Ms[t] + BIAS_COLS - 1) / BIAS_COLS;
         a.b_end[t] = end;
     }
     a.loss_blk = end++;
-    a.m = m; a.hyper = hyper; a.ctl = ctl; a.loss_rows = loss_rows; a.w_nce = w_nce; a.w_iic = w_iic; a.out = out;
-    IDL_REQUIRE(loss_rows == nullptr || out != nullptr, "small_wgrad_rms: the step loss needs out");
+    a.m = m; a.hyper = hyper; a.ctl = ctl; a.loss_rows = s.loss_rows; a.w_nce = s.w_nce; a.w_iic = s.w_iic; a.out = s.out;
+    IDL_REQUIRE(s.loss_rows == nullptr || s.out != nullptr, "small_wgrad_rms: the step loss needs out");
     a.gather_end = 0;
-    if (gather_batch > 0) {
-        a.gth = idl_dev::GatherArgs{feats, n, f, view_stride, pair_idx, ctl + 1, gather_batch, n_pairs, mean, scale, inv_scale, y_next, 0,
-                                    nullptr, nullptr, nullptr, idl_store::wt_mask()};
-        a.gather_end = (int)idl_dev::gather_blocks(f, gather_batch);
+    if (a.gth.y != nullptr) {
+        a.gather_end = (int)idl_dev::gather_blocks(a.gth.f, a.gth.batch);
         end += (a.gather_end + 1) / 2;
     }
-    if (kind == idl_dev::KIND_SGD) {
-        hipLaunchKernelGGL(small_wgrad_opt_kernel<idl_dev::KIND_SGD>, dim3((unsigned)end), dim3(WG_THREADS), 0, (hipStream_t)stream, a, *ob);
-    } else if (kind == idl_dev::KIND_ADAM) {
-        hipLaunchKernelGGL(small_wgrad_opt_kernel<idl_dev::KIND_ADAM>, dim3((unsigned)end), dim3(WG_THREADS), 0, (hipStream_t)stream, a, *ob);
+    const dim3 grid((unsigned)end), block(WG_THREADS);
+    const hipStream_t stream = (hipStream_t)s.stream;
+    if (opt != nullptr) {
+        OptBufs ob{};
+        for (int t = 0; t < 4; ++t) {
+            ob.g1[t] = opt->state1[2 * t]; ob.b1[t] = opt->state1[2 * t + 1];
+            if (opt->kind == idl_dev::KIND_ADAM) { ob.g2[t] = opt->state2[2 * t]; ob.b2[t] = opt->state2[2 * t + 1]; }
+        }
+        ob.hyper = opt->hyper; ob.step_in = opt->step_in; ob.step_out = opt->step_out;
+        if (opt->kind == idl_dev::KIND_SGD) hipLaunchKernelGGL(small_wgrad_opt_kernel<idl_dev::KIND_SGD>, grid, block, 0, stream, a, ob);
+        else hipLaunchKernelGGL(small_wgrad_opt_kernel<idl_dev::KIND_ADAM>, grid, block, 0, stream, a, ob);
     } else if (momentum_buffer != nullptr) {
         MomBufs mb{};
         for (int t = 0; t < 4; ++t) {
             IDL_REQUIRE(momentum_buffer[2 * t] && momentum_buffer[2 * t + 1], "small_wgrad_rms_momentum: NULL momentum buffer");
             mb.g[t] = momentum_buffer[2 * t]; mb.b[t] = momentum_buffer[2 * t + 1];
         }
-        hipLaunchKernelGGL(small_wgrad_momentum_kernel, dim3((unsigned)end), dim3(WG_THREADS), 0, (hipStream_t)stream, a, mb);
+        hipLaunchKernelGGL(small_wgrad_momentum_kernel, grid, block, 0, stream, a, mb);
     } else {
-        hipLaunchKernelGGL(small_wgrad_rms_kernel, dim3((unsigned)end), dim3(WG_THREADS), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(small_wgrad_rms_kernel, grid, block, 0, stream, a);
     }
     IDL_HIP_TRY(hipGetLastError());
     return IDL_OK;
@@ -804,56 +812,33 @@ static int small_wgrad_launch(float *const *params, float *const *grads, float *
 int idl_small_wgrad_rms(float *const *params, float *const *grads, float *const *square_avg, const float *hyper, int64_t *ctl,
                         const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
                         const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
-                        float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
-                        int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
-                        float *y_next, void *stream)
+                        float *out, const idl_next_batch_t *next_batch, void *stream)
 {
-    return small_wgrad_launch(params, grads, square_avg, nullptr, hyper, ctl, x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows, w_nce,
-                              w_iic, out, feats, n, f, view_stride, pair_idx, gather_batch, n_pairs, mean, scale, inv_scale, y_next, stream);
+    return small_wgrad_launch(params, grads, square_avg, nullptr, hyper, ctl,
+                              SmallStepIn{x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows, w_nce, w_iic, out, next_batch, stream});
 }
 
 int idl_small_wgrad_rms_momentum(float *const *params, float *const *grads, float *const *square_avg, float *const *momentum_buffer,
                                  const float *hyper, int64_t *ctl,
                                  const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
                                  const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
-                                 float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
-                                 int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
-                                 float *y_next, void *stream)
+                                 float *out, const idl_next_batch_t *next_batch, void *stream)
 {
     IDL_REQUIRE(momentum_buffer != nullptr, "small_wgrad_rms_momentum: NULL momentum buffers");
-    return small_wgrad_launch(params, grads, square_avg, momentum_buffer, hyper, ctl, x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows,
-                              w_nce, w_iic, out, feats, n, f, view_stride, pair_idx, gather_batch, n_pairs, mean, scale, inv_scale, y_next, stream);
+    return small_wgrad_launch(params, grads, square_avg, momentum_buffer, hyper, ctl,
+                              SmallStepIn{x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows, w_nce, w_iic, out, next_batch, stream});
 }
 
-int idl_small_wgrad_opt(int kind, float *const *params, float *const *grads, float *const *state1, float *const *state2,
-                        const double *hyper, const int64_t *step_in, int64_t *step_out, int64_t *ctl,
+int idl_small_wgrad_opt(const idl_opt_state_t *opt, float *const *params, float *const *grads, int64_t *ctl,
                         const float *x, const float *dr1, const float *a1, const float *da2, const float *a2, const float *dh,
                         const float *d2, const float *dlogits, int m, int F, int C, const float *loss_rows, float w_nce, float w_iic,
-                        float *out, const float *feats, int64_t n, int64_t f, int64_t view_stride, const int64_t *pair_idx,
-                        int64_t gather_batch, int64_t n_pairs, const double *mean, const double *scale, const double *inv_scale,
-                        float *y_next, void *stream)
+                        float *out, const idl_next_batch_t *next_batch, void *stream)
 {
-    IDL_REQUIRE(kind == idl_dev::KIND_SGD || kind == idl_dev::KIND_ADAM, "small_wgrad_opt: kind 1 (SGD with momentum) or 2 (Adam)");
-    IDL_REQUIRE(state1 != nullptr && (kind == idl_dev::KIND_SGD || state2 != nullptr),
-                "small_wgrad_opt: SGD needs momentum_buffer (state1), Adam exp_avg (state1) and exp_avg_sq (state2)");
-    IDL_REQUIRE(hyper != nullptr && (((uintptr_t)hyper) & 7u) == 0, "small_wgrad_opt: hyper is a device double[5]");
-    IDL_REQUIRE(step_in && step_out && step_in != step_out, "small_wgrad_opt: the step count is read from one word and written to another");
-    IDL_REQUIRE(ctl == nullptr || ((const void *)step_in != (const void *)ctl && (const void *)step_in != (const void *)(ctl + 1)),
-                "small_wgrad_opt: step_in must not be a word this launch writes");
-    OptBufs ob{};
-    for (int t = 0; t < 4; ++t) {
-        ob.g1[t] = state1[2 * t]; ob.b1[t] = state1[2 * t + 1];
-        IDL_REQUIRE(ob.g1[t] && ob.b1[t], "small_wgrad_opt: NULL entry in state1");
-        if (kind == idl_dev::KIND_ADAM) {
-            ob.g2[t] = state2[2 * t]; ob.b2[t] = state2[2 * t + 1];
-            IDL_REQUIRE(ob.g2[t] && ob.b2[t], "small_wgrad_opt: NULL entry in state2");
-        }
-    }
-    ob.hyper = hyper; ob.step_in = step_in; ob.step_out = step_out;
-    return small_wgrad_launch(params, grads, nullptr, nullptr, nullptr, ctl, x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows, w_nce,
-                              w_iic, out, feats, n, f, view_stride, pair_idx, gather_batch, n_pairs, mean, scale, inv_scale, y_next, stream,
-                              kind, &ob);
+    if (const int rc = idl_step::opt_state_of("small_wgrad_opt", opt, ctl, 1u << idl_dev::KIND_SGD | 1u << idl_dev::KIND_ADAM, 8)) return rc;
+    return small_wgrad_launch(params, grads, nullptr, nullptr, nullptr, ctl,
+                              SmallStepIn{x, dr1, a1, da2, a2, dh, d2, dlogits, m, F, C, loss_rows, w_nce, w_iic, out, next_batch, stream}, opt);
 }
+
 
 int idl_small_dropout_masks(uint64_t seed, int64_t step, int m, float *mask1, float *mask2, void *stream)
 {

@@ -27,6 +27,7 @@
 #include "iic_device.h"
 #include "nce_device.h"
 #include "scaler_device.h"
+#include "step_args.h"
 #include "wave_ops.h"
 #include "wgrad_device.h"
 #include "l1_device.h"
@@ -887,7 +888,9 @@ __device__ __forceinline__ void tail_sync(const int tix, unsigned int *spin)
     }
 }
 
-// (opt_step.hip's wgrad_tile carries a copy of the operand loops and the reduction below: a fix here is made there too.)
+// (The operand loops are dyT_x_tile16.inc, which opt_step.hip's wgrad_tile includes too.  The reduction and the epilogue below, rmsprop_body's streaming
+//  update and its step-loss tail have counterparts in opt_step.hip that stay separate texts: merging them would move this file's kernels, which
+//  their register, ISA and bit-for-bit tests pin.)
 template <bool AHEAD, bool SPIN = false>
 __device__ __forceinline__ void wgrad_tile_rms(const RmsArgs &a, int tile, float lr, float alpha, float eps, float wd, float oma, float *red, const int tix,
                                                unsigned int *spin)
@@ -903,59 +906,7 @@ __device__ __forceinline__ void wgrad_tile_rms(const RmsArgs &a, int tile, float
     const int oo = (i0 + (tid >> 4)) * ldb + j0 + (tid & 15);     // this thread's element of the tile in the epilogue
     float pi = 0.f, vi = 0.f;
     if (AHEAD) { pi = a.p[a.wg_t][oo]; vi = a.v[a.wg_t][oo]; }
-    if (AHEAD && a.wg_xt && per == 256 && kb + per <= m) {
-        const float *pbt = a.wg_x + (int64_t)(j0 + l) * m;
-        float av[64], bv[64];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-#pragma unroll
-            for (int u4 = 0; u4 < 8; ++u4) {
-                const float4 t4 = *(const float4 *)(pbt + kb + 128 * h + 32 * q + 4 * u4);
-                bv[32 * h + 4 * u4] = t4.x; bv[32 * h + 4 * u4 + 1] = t4.y; bv[32 * h + 4 * u4 + 2] = t4.z; bv[32 * h + 4 * u4 + 3] = t4.w;
-            }
-#pragma unroll
-            for (int u = 0; u < 32; ++u) av[32 * h + u] = pa[(kb + 128 * h + 32 * q + u) * lda];
-        }
-#pragma unroll
-        for (int u = 0; u < 64; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
-    } else if (a.wg_xt && (per & 127) == 0 && kb + per <= m) {
-        // x stored transposed ([n_in, m]): lane (l, q) walks 32 consecutive k of ITS column per batch (16-byte reads), and MFMA step
-        // u takes k = k0 + 32 q + u on both operands -- any assignment of k to (step, q) is a valid order of the same sum
-        const float *pbt = a.wg_x + (int64_t)(j0 + l) * m;
-        for (int k0 = kb; k0 < ke; k0 += 128) {
-            float av[32], bv[32];
-#pragma unroll
-            for (int u4 = 0; u4 < 8; ++u4) {
-                const float4 t4 = *(const float4 *)(pbt + k0 + 32 * q + 4 * u4);
-                bv[4 * u4] = t4.x; bv[4 * u4 + 1] = t4.y; bv[4 * u4 + 2] = t4.z; bv[4 * u4 + 3] = t4.w;
-            }
-#pragma unroll
-            for (int u = 0; u < 32; ++u) av[u] = pa[(k0 + 32 * q + u) * lda];
-#pragma unroll
-            for (int u = 0; u < 32; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
-        }
-    } else if (a.wg_xt) {
-        for (int k0 = kb; k0 < ke; k0 += 4) {
-            const int k = k0 + q;
-            const bool ok = k < ke;
-            const float ta = ok ? pa[k * lda] : 0.f, tb = ok ? a.wg_x[(int64_t)(j0 + l) * m + k] : 0.f;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ta, tb, acc, 0, 0, 0);
-        }
-    } else
-    for (int k0 = kb; k0 < ke; k0 += 128) {                  // 64 independent loads in flight per lane, then 32 MFMAs
-        float av[32], bv[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            const int k = k0 + 4 * u + q;
-            const bool ok = k < ke;
-            const int kc = ok ? k : ke - 1;
-            const float ta = pa[kc * lda], tb = pb[kc * ldb];
-            av[u] = ok ? ta : 0.f;
-            bv[u] = ok ? tb : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 32; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
-    }
+#include "dyT_x_tile16.inc"
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[wv * 256 + (4 * q + r) * 16 + l] = acc[r];          // C/D: row = 4 q + reg, col = l
     tail_sync<SPIN>(tix, spin);
@@ -1822,15 +1773,7 @@ int idl_rmsprop_step(const idl_opt_tail_t *tail, const idl_next_batch_t *next_ba
 {
     IDL_REQUIRE(tail != nullptr, "rmsprop_step: NULL tail");
     idl_dev::GatherArgs g{};
-    if (const idl_next_batch_t *nb = next_batch; nb != nullptr && nb->feats != nullptr) {
-        IDL_REQUIRE(tail->ctl != nullptr && nb->base == tail->ctl + 1, "rmsprop_step: the optimizer launch assembles the batch at ctl[1]: next_batch->base must be ctl + 1");
-        IDL_REQUIRE(nb->y_hi == nullptr && nb->y_lo == nullptr, "rmsprop_step: the optimizer launch writes no planes of the next batch");
-        IDL_REQUIRE(nb->base_add == 0, "rmsprop_step: the optimizer launch takes no base_add");
-        IDL_REQUIRE(nb->part == 0 && nb->part_end == nb->parts, "rmsprop_step: the optimizer launch assembles the whole batch, not a share");
-        IDL_REQUIRE(nb->pair_idx && nb->mean && nb->scale && nb->y && nb->n >= 1 && nb->f >= 1 && nb->batch >= 1 && nb->n_pairs >= 0, "rmsprop_step: bad gather arguments");
-        g = idl_dev::GatherArgs{nb->feats, nb->n, nb->f, nb->view_stride, nb->pair_idx, tail->ctl + 1, nb->batch, nb->n_pairs, nb->mean, nb->scale, nb->inv_scale, nb->y};
-        g.wt = idl_store::wt_mask();
-    }
+    if (const int rc = idl_step::whole_batch_of("rmsprop_step", next_batch, tail->ctl, g)) return rc;
     return rmsprop_launch(*tail, g, stream, TailCarrier{});
 }
 

@@ -306,6 +306,20 @@ class _LinearStepParts:
                                      st.n_pairs, m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(y), _p(planes[0]), _p(planes[1]), _p(flag),
                                      part, part_end, parts)
 
+    _vp, hyper = None, None              # RMSprop's running averages and float hyperparameters (FusedLinearTrainer); another optimizer travels as idl_opt_state_t
+
+    def _tail(self, bf, *, skip=-1, advance=0, **wg):
+        """The optimizer's tail of the step on bf (idl_opt_tail_t): every tensor's RMSprop but tensor `skip`'s (0: W1, which dW1 tiles update), the
+        step loss, the batch offset's advance, and the in-launch dW2 tiles where the caller adds them (**self._wg(...))."""
+        return _lib.idl_opt_tail_t(count=len(self.params), params=self._pp, grads=self._gp, grad_parts=self._parts, square_avg=self._vp, sizes=self._sz,
+                                   hyper=_p(self.hyper), ctl=_p(self.ctl), loss_rows=_p(bf.loss_rows), loss_m=bf.m, w_nce=1.0 - self.weight,
+                                   w_iic=self.weight, out=_p(self.out), skip_index=skip, batch_advance=advance, **(wg or {"wg_index": -1}))
+
+    def _wg(self, bf, r1, transposed):
+        """The dW2 = dlat^T r1 tiles of an optimizer launch: idl_opt_tail_t's wg_* fields."""
+        return dict(wg_index=2, wg_dy=_p(bf.dlat), wg_x=_p(r1), wg_x_transposed=transposed, wg_m=bf.m, wg_n_out=self.H2, wg_n_in=self.H1,
+                    wg_grad=_p(self.grads[2]))
+
     def _mid_fwd_tensors(self, bf, tr):
         """The forward middle's weights, shape and dropout seed, and its outputs (the step counter goes between the two)."""
         return (_p(self.W2), _p(self.b2), _p(self.W3), _p(self.b3), bf.m, self.C, tr, self.seed), (_p(bf.f), _p(bf.inv), _p(bf.r2), _p(bf.z))
@@ -547,18 +561,6 @@ class FusedLinearTrainer(_LinearStepParts):
             self._step_tiles(bf, tr, st, xi, defer_tail)
         else:
             self._step_general(bf, tr, batch_advance, st, xi)
-
-    def _tail(self, bf, *, skip=-1, advance=0, **wg):
-        """The optimizer's tail of the step on bf (idl_opt_tail_t): every tensor's RMSprop but tensor `skip`'s (0: W1, which dW1 tiles update), the
-        step loss, the batch offset's advance, and the in-launch dW2 tiles where the caller adds them (**self._wg(...))."""
-        return _lib.idl_opt_tail_t(count=len(self.params), params=self._pp, grads=self._gp, grad_parts=self._parts, square_avg=self._vp, sizes=self._sz,
-                                   hyper=_p(self.hyper), ctl=_p(self.ctl), loss_rows=_p(bf.loss_rows), loss_m=bf.m, w_nce=1.0 - self.weight,
-                                   w_iic=self.weight, out=_p(self.out), skip_index=skip, batch_advance=advance, **(wg or {"wg_index": -1}))
-
-    def _wg(self, bf, r1, transposed):
-        """The dW2 = dlat^T r1 tiles of an optimizer launch: idl_opt_tail_t's wg_* fields."""
-        return dict(wg_index=2, wg_dy=_p(bf.dlat), wg_x=_p(r1), wg_x_transposed=transposed, wg_m=bf.m, wg_n_out=self.H2, wg_n_in=self.H1,
-                    wg_grad=_p(self.grads[2]))
 
     def _gw1(self):
         return _p(self.grads[0]) if self._keep_w1_grad else None

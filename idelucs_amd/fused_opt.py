@@ -18,6 +18,7 @@ import ctypes
 
 import torch
 
+from . import _lib
 from ._lib import lib as _L
 from .fused import STEPS_PER_GRAPH, _LinearStepParts, _launch, _mm_now, _p, _stream
 
@@ -84,9 +85,10 @@ class _OptimizerState:
                 self.hyper64[i:i + 1].fill_(v)    # (fill_ on a view: no host-to-device copy from pageable memory, FusedLinearTrainer.begin_voter)
                 self._hyper_host[i] = v
 
-    def _step_words(self):
-        """(step_in, step_out) of the next last launch; _step_taken() after it swaps their roles."""
-        return _p(self.steps[self._tpar:]), _p(self.steps[1 - self._tpar:])
+    def _opt_state(self):
+        """The idl_opt_state_t of the next last launch: it reads the step count from steps[_tpar] and writes the other word; _step_taken() after it
+        swaps their roles."""
+        return _lib.idl_opt_state_t(self.kind, self._s1p, self._s2p, _p(self.hyper64), _p(self.steps[self._tpar:]), _p(self.steps[1 - self._tpar:]))
 
     def _step_taken(self):
         self._tpar ^= 1
@@ -113,14 +115,9 @@ class FusedLinearOptTrainer(_OptimizerState, _LinearStepParts):
     # ------------------------------------------------------------------ one step on a filled bf.xs[xi]
     def _opt(self, bf, r1, transposed, advance, st=None):
         """The step's last launch: dW2 = dlat^T r1 tiles + the optimizer on every tensor + step loss + counters (+ with st, the next batch from
-        that store into bf.x).  idl_opt_step_gather_wgrad takes the batch assembly as eleven positional arguments: all empty for none."""
-        m = bf.m
-        gather = (None, 0, 0, 0, None, 0, 0, None, None, None, None) if st is None else (
-            _p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), st.n_pairs, m // 2, _p(st.mean), _p(st.scale), _p(st.inv_scale), _p(bf.x))
-        _launch(_L.idl_opt_step_gather_wgrad, self.kind, len(self.params), self._pp, self._gp, self._parts, self._s1p, self._s2p, self._sz,
-                _p(self.hyper64), *self._step_words(), _p(self.ctl),
-                _p(bf.loss_rows), m, 1.0 - self.weight, self.weight, _p(self.out), *gather,
-                2, _p(bf.dlat), _p(r1), transposed, m, self.H2, self.H1, _p(self.grads[2]), advance, _stream())
+        that store into bf.x: the whole batch, at the offset ctl[1] itself)."""
+        nb = None if st is None else self._next_batch(st, bf.m, y=bf.x, base_add=0)
+        _launch(_L.idl_opt_step_gather_wgrad, self._tail(bf, advance=advance, **self._wg(bf, r1, transposed)), self._opt_state(), nb, _stream())
         self._step_taken()
 
     def _dw1(self, bf, x):

@@ -156,10 +156,12 @@ class FusedSmallTrainer:
                                  _p(W2), _p(Wi), _p(Wc), m, C, tr, nce_coef, self.seed, _p(self.ctl), adv,
                                  _p(bf.dlogits), _p(bf.dh), _p(bf.da2), _p(bf.dr1), _stream()))
         st = next_from
-        gth = ((_p(st.feats), st.n, st.f, st.n * st.f, _p(self._perm), m // 2, st.n_pairs, _p(st.mean), _p(st.scale), _p(st.inv_scale),
-                _p(bf.xs[1 - xi])) if st is not None else (None, 0, 0, 0, None, 0, 0, None, None, None, None))
+        # the whole next batch as fp32 rows, at the offset ctl[1] that the middle backward advanced
+        nb = None if st is None else _lib.idl_next_batch_t(
+            feats=_p(st.feats), n=st.n, f=st.f, view_stride=st.n * st.f, pair_idx=_p(self._perm), base=_p(self.ctl[1:]), base_add=0, n_pairs=st.n_pairs,
+            batch=m // 2, mean=_p(st.mean), scale=_p(st.scale), inv_scale=_p(st.inv_scale), y=_p(bf.xs[1 - xi]), part=0, part_end=1, parts=1)
         self._last_launch((_p(x), _p(bf.dr1), _p(bf.a1), _p(bf.da2), _p(bf.a2), _p(bf.dh), _p(bf.d2), _p(bf.dlogits), m, F, C,
-                           _p(bf.loss_rows), 1.0 - self.weight, self.weight, _p(self.out), *gth, _stream()))
+                           _p(bf.loss_rows), 1.0 - self.weight, self.weight, _p(self.out), nb, _stream()))
 
     def _last_launch(self, tail):
         """The step's last launch: every gradient with the optimizer's update in its epilogue, the step loss, the step counter, the next batch.
@@ -244,8 +246,7 @@ class FusedSmallOptTrainer(_OptimizerState, FusedSmallTrainer):
             self._reset_state()
 
     def _last_launch(self, tail):
-        _lib.check(_L.idl_small_wgrad_opt(self.kind, self._pp, self._gp(), self._s1p, self._s2p, _p(self.hyper64), *self._step_words(),
-                                          _p(self.ctl), *tail))
+        _lib.check(_L.idl_small_wgrad_opt(self._opt_state(), self._pp, self._gp(), _p(self.ctl), *tail))
         self._step_taken()
 
     def _graph_key_extra(self):

@@ -107,10 +107,10 @@ def test_opt_step_kind_3_matches_torch_rmsprop(dev, mu, wg_m, transposed):
         x = torch.randn((wg_m, 32), device=dev, generator=gen)
         xk = x.t().contiguous() if transposed else x
         par = it % 2
-        _lib.check(_lib.lib.idl_opt_step_gather_wgrad(
-            KIND_RMSPROP, 4, pp, gp, pt, s1, s2, sz, _p(hyper), _p(steps[par:]), _p(steps[1 - par:]), _p(ctl),
-            None, 0, 0.0, 0.0, None, None, 0, 0, 0, None, 0, 0, None, None, None, None,
-            3, _p(dy), _p(xk), transposed, wg_m, 16, 32, _p(wg_grad), 7, _stream()))
+        tail = _lib.idl_opt_tail_t(count=4, params=pp, grads=gp, grad_parts=pt, sizes=sz, ctl=_p(ctl), skip_index=-1, wg_index=3, wg_dy=_p(dy),
+                                   wg_x=_p(xk), wg_x_transposed=transposed, wg_m=wg_m, wg_n_out=16, wg_n_in=32, wg_grad=_p(wg_grad), batch_advance=7)
+        opt = _lib.idl_opt_state_t(KIND_RMSPROP, s1, s2, _p(hyper), _p(steps[par:]), _p(steps[1 - par:]))
+        _lib.check(_lib.lib.idl_opt_step_gather_wgrad(tail, opt, None, _stream()))
         torch.cuda.synchronize()
         want = (dy.double().t() @ x.double()).reshape(-1)
         _within(wg_grad.double(), want, f"step {it} dy^T x", rel=2e-3)          # (the gradient bar of the step tests)
@@ -163,7 +163,7 @@ def test_small_wgrad_rms_momentum_matches_torch_rmsprop(dev, mu, m, F):
         dr1, da2, dh, dlogits = rnd(m, H1), rnd(m, H2), rnd(m, LAT), rnd(m, C)
         _lib.check(_lib.lib.idl_small_wgrad_rms_momentum(
             pp, gp, vp, mp, _p(hyper), _p(ctl), _p(x), _p(dr1), _p(a1), _p(da2), _p(a2), _p(dh), _p(d2), _p(dlogits), m, F, C,
-            None, 0.0, 0.0, None, None, 0, 0, 0, None, 0, 0, None, None, None, None, _stream()))
+            None, 0.0, 0.0, None, None, _stream()))
         torch.cuda.synchronize()
         print(f"m = {m}, F = {F}, step {it}, momentum {hyper[5].item()}:")
         for i, (dy, xin) in enumerate(((dr1, x), (da2, a1), (dh, a2), (dlogits, d2))):

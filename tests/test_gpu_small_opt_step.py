@@ -123,9 +123,9 @@ def test_small_wgrad_opt_matches_torch_optim(dev, opt, start, m, F):
         dr1, da2, dh, dlogits = rnd(m, 400), rnd(m, 128), rnd(m, 64), rnd(m, C)
         par = it % 2
         _lib.check(_lib.lib.idl_small_wgrad_opt(
-            KIND[opt], pp, gp, s1p, s2p, _p(hyper), _p(steps[par:]), _p(steps[1 - par:]), _p(ctl),
+            _lib.idl_opt_state_t(KIND[opt], s1p, s2p, _p(hyper), _p(steps[par:]), _p(steps[1 - par:])), pp, gp, _p(ctl),
             _p(x), _p(dr1), _p(a1), _p(da2), _p(a2), _p(dh), _p(d2), _p(dlogits), m, F, C,
-            None, 0.0, 0.0, None, None, 0, 0, 0, None, 0, 0, None, None, None, None, _stream()))
+            None, 0.0, 0.0, None, None, _stream()))
         torch.cuda.synchronize()
         print(f"{opt} m = {m}, F = {F}, step {start + it + 1}, lr {hyper[0].item()}, momentum / beta1 {hyper[1].item()}:")
         for i, (dy, xin) in enumerate(((dr1, x), (da2, a1), (dh, a2), (dlogits, d2))):
@@ -161,9 +161,8 @@ def test_small_wgrad_opt_refuses_what_it_cannot_run(dev):
     ops = [rnd(m, F), rnd(m, 400), rnd(m, 400), rnd(m, 128), rnd(m, 128), rnd(m, 64), rnd(m, 128), rnd(m, C)]
 
     def call(kind, s2, step_in, step_out):
-        return _lib.lib.idl_small_wgrad_opt(kind, _arr(params), _arr(grads), _arr(st1), s2, _p(hyper), step_in, step_out, _p(ctl),
-                                            *[_p(t) for t in ops], m, F, C, None, 0.0, 0.0, None,
-                                            None, 0, 0, 0, None, 0, 0, None, None, None, None, _stream())
+        return _lib.lib.idl_small_wgrad_opt(_lib.idl_opt_state_t(kind, _arr(st1), s2, _p(hyper), step_in, step_out), _arr(params), _arr(grads), _p(ctl),
+                                            *[_p(t) for t in ops], m, F, C, None, 0.0, 0.0, None, None, _stream())
     assert call(2, None, _p(steps), _p(steps[1:])) != 0                  # Adam without exp_avg_sq
     assert "state2" in _lib.last_error()
     assert call(1, None, _p(steps), _p(steps)) != 0                      # the step count read and written in one word

@@ -346,7 +346,7 @@ class _Wgrad:
         o = self.ops
         tail = (_p(self.hyper), _p(self.ctl), _p(o["x"]), _p(o["dr1"]), _p(o["a1"]), _p(o["da2"]), _p(o["a2"]), _p(o["dh"]), _p(o["d2"]),
                 _p(o["dlogits"]), self.m, self.F, self.C, _p(loss_rows), w_nce, w_iic, _p(out),
-                *(gather or (None, 0, 0, 0, None, 0, 0, None, None, None, None)), _stream())
+                gather, _stream())
         if self.mom:
             _lib.check(_lib.lib.idl_small_wgrad_rms_momentum(arr(self.params), gp, arr(self.sq), arr(self.buf), *tail))
         else:
@@ -460,7 +460,8 @@ def test_wgrad_riding_assembly_is_gather_pairs_at(dev, gb, F, at, mom):
     w.ctl[1] = at
     y = _Guarded((2 * gb, F), dev)
     y.t.fill_(SENTINEL)
-    w.launch(gather=(_p(feats), n, F, n * F, _p(perm), gb, n_pairs, _p(mean), _p(scale), _p(inv_scale), _p(y.t)))
+    w.launch(gather=_lib.idl_next_batch_t(feats=_p(feats), n=n, f=F, view_stride=n * F, pair_idx=_p(perm), base=_p(w.ctl[1:]), base_add=0, n_pairs=n_pairs,
+                                          batch=gb, mean=_p(mean), scale=_p(scale), inv_scale=_p(inv_scale), y=_p(y.t), part=0, part_end=1, parts=1))
     assert y.intact() and w.ctl.tolist() == [STEP + 1, at]
     want = torch.empty((2 * gb, F), device=dev)
     _lib.check(_lib.lib.idl_gather_pairs_at(_p(feats), n, F, n * F, _p(perm), _p(w.ctl[1:]), gb, _p(mean), _p(scale), _p(inv_scale),

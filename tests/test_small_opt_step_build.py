@@ -2,6 +2,7 @@
 without scratch and within their launch bounds (hipcc cross-compiles), no kernel's name collides with another wgrad kernel's, the entry
 point is declared, the update's one definition is the header both step files include, the CLI flag leaves no trace when it is not given,
 and the golden's own float32-against-float64 figures stay under the caps its generator kept the weight seed by."""
+import ctypes
 import json
 import os
 import re
@@ -72,9 +73,11 @@ def test_small_wgrad_opt_is_declared():
     from idelucs_amd import _lib
     sig = _lib.SIGNATURES
     assert "idl_small_wgrad_opt" in sig
-    # kind in front, state2 and hyper where the RMSprop form has momentum_buffer and its float hyper, then step_in and step_out: three more
-    assert len(sig["idl_small_wgrad_opt"][1]) == len(sig["idl_small_wgrad_rms_momentum"][1]) + 3 == 36
-    assert sig["idl_small_wgrad_opt"][1][9:] == sig["idl_small_wgrad_rms_momentum"][1][6:]         # from x on: the same arguments
+    # the optimizer's state, hyperparameters and step words travel as one idl_opt_state_t in front, where the RMSprop form has square_avg,
+    # momentum_buffer and its float hyper: two fewer
+    assert len(sig["idl_small_wgrad_opt"][1]) == len(sig["idl_small_wgrad_rms_momentum"][1]) - 2 == 21
+    assert sig["idl_small_wgrad_opt"][1][0] == ctypes.POINTER(_lib.idl_opt_state_t)
+    assert sig["idl_small_wgrad_opt"][1][4:] == sig["idl_small_wgrad_rms_momentum"][1][6:]         # from x on: the same arguments
     assert hasattr(_lib.lib, "idl_small_wgrad_opt")                                                    # exported by the library
 
 

@@ -8,7 +8,8 @@ alone: two builds whose lines agree compute the same bits.)
 
 tests/small_last_launch_parent.jsonl is this tool's output on the library as it was before the four kernels were put on one tile body
 (IDELUCS_LIB_PATH=<that build> python tools/small_last_launch_bits.py --out tests/small_last_launch_parent.jsonl);
-tests/test_gpu_small_last_launch_bits.py replays the cases on the current build and compares line for line.
+tests/test_gpu_small_last_launch_bits.py replays the cases on the current build and compares line for line.  (That recording was made when the
+entries took the next batch and the optimizer's state as loose arguments; the calls below are the struct forms of the same launches.)
 
 Usage:  python tools/small_last_launch_bits.py [--out FILE]
 """
@@ -60,16 +61,17 @@ def run_case(form, m, F, C, rider, dev):
     ctl = torch.tensor([STEP, AT], dtype=torch.int64, device=dev)
     steps = torch.tensor([STEPS_TAKEN, -1], dtype=torch.int64, device=dev)
     y_next = torch.full((m, F), SENTINEL, dtype=torch.float32, device=dev)
-    gather = (None, 0, 0, 0, None, 0, 0, None, None, None, None)
+    gather = None
     if rider:
         n, n_pairs = STORE_ROWS, STORE_ROWS * VIEWS
         fh = rs.random_sample(((VIEWS + 1) * n, F)).astype(np.float32)
         sh = np.maximum(fh[:n].astype(np.float64).std(0), 1e-3)
         feats, mean, scale, inv_scale = (torch.from_numpy(v).to(dev) for v in (fh, fh[:n].astype(np.float64).mean(0), sh, 1.0 / sh))
         perm = torch.from_numpy(rs.permutation(n_pairs).astype(np.int64)).to(dev)
-        gather = (_p(feats), n, F, n * F, _p(perm), m // 2, n_pairs, _p(mean), _p(scale), _p(inv_scale), _p(y_next))
+        gather = _lib.idl_next_batch_t(feats=_p(feats), n=n, f=F, view_stride=n * F, pair_idx=_p(perm), base=_p(ctl[1:]), base_add=0, n_pairs=n_pairs,
+                                       batch=m // 2, mean=_p(mean), scale=_p(scale), inv_scale=_p(inv_scale), y=_p(y_next), part=0, part_end=1, parts=1)
     arr = lambda ts: (ctypes.c_void_p * 8)(*[t.data_ptr() for t in ts])
-    tail = (_p(ctl), *[_p(o) for o in ops], m, F, C, _p(loss_rows), 0.75, 0.25, _p(out), *gather, _stream())
+    tail = (_p(ctl), *[_p(o) for o in ops], m, F, C, _p(loss_rows), 0.75, 0.25, _p(out), gather, _stream())
     L = _lib.lib
     if form == "rms":
         hyper = torch.tensor(HYPER_RMS[:5], dtype=torch.float32, device=dev)
@@ -80,8 +82,8 @@ def run_case(form, m, F, C, rider, dev):
     else:
         hyper = torch.tensor(HYPER_OPT[form], dtype=torch.float64, device=dev)
         kind = 1 if form == "SGD" else 2
-        _lib.check(L.idl_small_wgrad_opt(kind, arr(params), arr(grads), arr(state1), arr(state2), _p(hyper), _p(steps[0:]), _p(steps[1:]),
-                                         *tail))
+        opt = _lib.idl_opt_state_t(kind, arr(state1), arr(state2), _p(hyper), _p(steps[0:]), _p(steps[1:]))
+        _lib.check(L.idl_small_wgrad_opt(opt, arr(params), arr(grads), *tail))
     torch.cuda.synchronize()
     named = ([(f"param{i}", t) for i, t in enumerate(params)] + [(f"state1_{i}", t) for i, t in enumerate(state1)]
              + [(f"state2_{i}", t) for i, t in enumerate(state2)] + [(f"grad{i}", t) for i, t in enumerate(grads)]
